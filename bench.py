@@ -6,7 +6,9 @@ already resident in HBM.  Default workload (--config 2) = BASELINE.json configs[
 reference (bluerov2_path/config/traj/circle.py formulas), per-instance x0 noise (seed 1), nominal
 hydrodynamic parameters; the reference window advances one row per step and is sliced on the device.
 
-    python bench.py                          1 GPU, config 2 (the headline), + forced-IPM / mixed-batch / CPU legs
+    python bench.py                          1 GPU, config 2 (the headline): set-up, warm-up, the timed steps, one JSON line
+    python bench.py --full                   the same headline, + roofline pass / forced-IPM / mixed-batch / other configs / CPU legs
+    python bench.py --dump-outputs DIR       + the last timed step's records and iterate as DIR/<name>.npy (float64)
     python bench.py --gpus 8                 spawns its own 8 ranks (re-exec under torch.distributed.run) when WORLD_SIZE is
                                              not set; under `python -m torch.distributed.run ... bench.py --gpus 8` it is a rank
     python bench.py --gpus 8 --config 4      65 536 lemniscate candidates, 8192 per GPU, all-gather + global arg-min every step
@@ -20,10 +22,12 @@ Multi-GPU: one process per GPU (torch.distributed, backend "nccl"
 communication during the solve, ONE all-gather of the 104-byte result records per step (u0, cost, KKT,
 status, thrusts), arg-min of cost on the gathered records for the candidate workload.
 
-Prints ONE JSON line on rank 0 (contract in the round prompt) including `roofline` (dominant kernel; bound = FP64 MFMA),
+Prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype, ms_per_step (one timed step; --steps of them are
+timed) and the solver status of the workload.  With --full the line also holds `roofline` (dominant kernel; bound = FP64 MFMA),
 `roofline_hbm`, `cpu_baseline` (the C oracle timed on the host cores -- never the thing measured as `value`) and, for the
 default single-GPU run, `forced_ipm`, `mixed_batch_25pct_saturated[_shuffled]`, `batch1_tick` (BASELINE configs[0] on the GPU: one instance, host
-buffers in, record out), `host_boundary` (the headline workload with inputs from and records to host buffers: PCIe-inclusive) and `cpu_baseline_single_thread`.
+buffers in, record out), `host_boundary` (the headline workload with inputs from and records to host buffers: PCIe-inclusive), `configs`
+and `cpu_baseline_single_thread`.
 """
 import argparse
 import json
@@ -85,6 +89,31 @@ def saturate(x0, frac, seed):
     x0[:n, :3] += rng.uniform(-4, 4, size=(n, 3))
     x0[:n, 5] += rng.uniform(-0.3, 0.3, size=n)
     return x0
+
+
+DUMP_MAX_BYTES = 64 * 10**6
+
+
+def step_outputs(s, res):
+    """what a caller of the timed path holds after a step, as float64 arrays: the result records (u0, cost, KKT, status, QP
+    iterations, thrusts) and the iterate the next step starts from (x, u and the multipliers pi, lam)"""
+    x, u, pi, lam = s.get_iterate()
+    out = {f: np.ascontiguousarray(res[f], dtype=np.float64) for f in ("u0", "cost", "kkt", "status", "qp_iter", "thrust")}
+    out.update(x=x, u=u, pi=pi, lam=lam)
+    return out
+
+
+def write_outputs(d, outputs):
+    """--dump-outputs: DIR/<prefix><name>.npy for every (prefix, step_outputs()) pair.  Over DUMP_MAX_BYTES in all, every array keeps the
+    same fixed sample of instances (numpy default_rng(0), in ascending order), as large as the budget allows."""
+    os.makedirs(d, exist_ok=True)
+    total = sum(a.nbytes for _, arrs in outputs for a in arrs.values())
+    frac = min(1.0, (DUMP_MAX_BYTES - 4096 * sum(len(arrs) for _, arrs in outputs)) / total)
+    for prefix, arrs in outputs:
+        B = len(arrs["cost"])
+        keep = np.arange(B) if frac >= 1.0 else np.sort(np.random.default_rng(0).choice(B, int(B * frac), replace=False))
+        for name, a in arrs.items():
+            np.save(os.path.join(d, f"{prefix}{name}.npy"), np.ascontiguousarray(a[keep]))
 
 
 def batch1_tick(ba, ticks=300, warm=30):
@@ -464,7 +493,7 @@ def live_pmc(fwd, kernel, passes, timeout=60):
         for n, group in enumerate(passes):
             d = os.path.join(tmp, f"p{n}")
             cmd = [tool, "--pmc", *group, "--kernel-trace", "--output-format", "csv", "-d", d, "-o", "c", "--", sys.executable, os.path.join(ROOT, "bench.py"),
-                   "--steps", "10", "--warmup", "5", "--no-cpu-baseline", "--no-extra", "--no-traffic"] + list(fwd)
+                   "--steps", "10", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-extra", "--no-traffic"] + list(fwd)
             r = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, timeout=timeout)
             vals = {c: [] for c in group}
             for f in glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True):
@@ -517,6 +546,64 @@ def valu_roofline(counts, kernel):
             "note": "one wave per SIMD: the fraction of the wave's cycles in which the SIMD's vector issue port is taken; the rest is dependent-issue latency "
                     "(the Riccati stage is a chain), LDS / MFMA result waits and s_waitcnt stalls that a second resident wave would fill and this "
                     "kernel's register / LDS footprint does not admit (DESIGN.md section 7)"}
+
+
+def roofline_block(args, lg, B, K, world, n_legs):
+    """the --full line's kernel times (HIP events of the second pass), FP64 MFMA / HBM rooflines of the slowest leg's dominant kernel and,
+    for one rank and one leg, the counter child runs (traffic, VALU issue)"""
+    N = lg["N"]
+    qp_fl = qp_flops(lg["qp_iter"], N)
+    lin_fl = B * N * F_LIN
+    ksec = lg["ksec"]
+    if lg["path"] in KERNEL_NAMES:  # one kernel does both phases
+        dom, dom_fl, dom_t = KERNEL_NAMES[lg["path"]], qp_fl + lin_fl, ksec[1]
+        if lg["path"] == 3 and 2 * lg["pit"] > B:
+            dom = PIT_KERNELS
+        kernel_ms = {dom: ksec[1] * 1e3}
+    else:
+        dom = "qp_kernel" if ksec[1] >= ksec[0] else "lin_wave_kernel"
+        dom_fl, dom_t = (qp_fl, ksec[1]) if dom == "qp_kernel" else (lin_fl, ksec[0])
+        kernel_ms = {"lin_wave_kernel": ksec[0] * 1e3, "qp_kernel": ksec[1] * 1e3}
+    achieved = dom_fl / dom_t / 1e12
+    alg_bytes = algorithmic_bytes(N, lg["shared"])
+    traffic, traffic_src = None, None
+    why_not_live = None
+    profiled = bool(os.environ.get("ROCP_TOOL_LIBRARIES")) or "rocprofiler" in os.environ.get("LD_PRELOAD", "")   # this run is itself under rocprofv3
+    roof_valu = None
+    if world == 1 and n_legs == 1 and not args.no_traffic and not args.no_extra and not profiled and not os.environ.get("BROV_BENCH_PMC_CHILD"):
+        cal = pmc_calibration()
+        pmc, why = live_pmc(fwd_args(args), dom, (("FETCH_SIZE",), ("WRITE_SIZE",), SQ_PASS)) if cal else (None, "no committed counter calibration")
+        if pmc is None:
+            why_not_live = why
+        else:
+            traffic, traffic_src = traffic_from_counts(pmc, cal)
+            roof_valu = valu_roofline(pmc, dom)
+    for pj in (() if traffic is not None else ("r4_pmc_summary.json", "r3_pmc_summary.json", "r2_pmc_summary.json", "r1_pmc_summary.json")):
+        try:
+            pm = json.load(open(os.path.join(ROOT, "profiles", pj)))
+            ent = pm.get("runs", {}).get(f"cfg{args.config}_N{N}", pm if (pm.get("batch") == B and pm.get("N") == N) else {})
+            t = ent.get("hbm_bytes_per_launch", {}).get(dom) if B == BATCH_PER_GPU and not args.force_ipm and args.path == 0 else None
+            if t is not None:
+                traffic, traffic_src = t, (f"profiles/{pj}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, not this run" +
+                                           (f" (live passes: {why_not_live})" if why_not_live else ""))
+                break
+        except Exception:
+            pass
+    per_gpu_rate = B * K / lg["dt"]
+    return {"kernel_ms": kernel_ms, "device_bytes": lg["device_bytes"],
+            "roofline": {"kernel": dom, "bound": "mfma", "achieved": achieved, "peak": PEAK_FP64_MFMA_TFLOPS,
+                         "unit": "TFLOP/s", "frac": achieved / PEAK_FP64_MFMA_TFLOPS, "traffic": traffic, "traffic_source": traffic_src,
+                         "N": N, "algorithmic_flops_per_launch": dom_fl,
+                         "note": "FP64; algorithmic flops = factorisations/solves actually required by each instance "
+                                 "(DESIGN.md Accounting), not the MFMA-issued flops"},
+            **({"roofline_valu": roof_valu} if roof_valu else {}),
+            "roofline_hbm": {"bound": "hbm", "achieved": per_gpu_rate * alg_bytes / 1e9, "peak": PEAK_HBM_GBS,
+                             "unit": "GB/s", "frac": per_gpu_rate * alg_bytes / 1e9 / PEAK_HBM_GBS,
+                             "algorithmic_bytes_per_solve": alg_bytes,
+                             "algorithmic_bytes_survey_general": survey_bytes(N)["general"],
+                             "algorithmic_bytes_survey_shared_constant": survey_bytes(N)["shared_constant"],
+                             **(traffic_ratios(traffic, B, N) if traffic else {}),
+                             "formula": "8*[12 + (0 if one window is shared by the batch else 16(N+1)) + 16(N+1) + 2*(12(N+1)+4N)] + 104"}}
 
 
 def configs_block(ba, args, device):
@@ -825,6 +912,12 @@ def parse_args(argv=None):
     ap.add_argument("--force-gather", action="store_true", help="run the result all-gather even with one rank")
     ap.add_argument("--path", type=int, default=0, help="0 auto (LDS-resident kernels), 1 streaming, 2 fused")
     ap.add_argument("--dry-run", action="store_true", help="no GPU, no solver: launcher + gloo collectives on synthetic records")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: per-kernel / roofline pass, counter child runs, forced-IPM / mixed-batch / "
+                         "batch-1 / host-boundary legs, the other BASELINE configs, the multi-rank strong legs and the CPU baselines "
+                         "(--no-cpu-baseline / --no-extra / --no-traffic still trim it)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (result records and iterate) as DIR/<name>.npy")
     ap.add_argument("--_cpu_worker", default="", help=argparse.SUPPRESS)
     return ap.parse_args(argv)
 
@@ -1103,9 +1196,10 @@ def main(argv=None):
         sys.stdout.write(json.dumps(line) + "\n")
         sys.stdout.flush()
 
-    def measure(args, extras_ok=True, solve_only=False):
+    def measure(args, extras_ok=True, solve_only=False, outputs=None):
         """one workload (args.config / args.scaling / ...) on this rank's GPU, all ranks together: (rank 0: the result line as a dict, else None).
-        solve_only: no record all-gather in the steps (the pre-measurement a multi-rank run takes before it touches any data-plane collective)"""
+        solve_only: no record all-gather in the steps (the pre-measurement a multi-rank run takes before it touches any data-plane collective).
+        outputs: a list that receives (name prefix, step_outputs()) of the last timed step of every horizon"""
         rank, world = mrank, mworld
         wl = workload(args, rank, world)
         gather = (gather0 or (wl.get("always_gather", False) and dist.is_initialized())) and not solve_only and coll is not None
@@ -1215,12 +1309,16 @@ def main(argv=None):
                 s0 = ba.BatchSolver(1, ba.SolverOptions(N, Ts), device=local_rank)
                 s0.set_params(ba.P_NOMINAL); s0.solve(sync=True); s0.close()
             # pass 1: the timed region that defines `value` (no per-kernel events inside)
-            dt, _, (_, _, info) = run(s, tick, K, W, False, select)
-            n_bad = int((s.results()["status"] != 0).sum())
-            # pass 2: same steps again with HIP events around each kernel for the roofline numbers
-            _, ksec, (gathered, best, info2) = run(s, tick, K, W, True, select)
-            info["gather_ms"], info["select_ms"] = info2.get("gather_ms"), info2.get("select_ms")   # per-step event pairs exist in this pass only
+            dt, ksec, (gathered, best, info) = run(s, tick, K, W, False, select)
             res2 = s.results()
+            n_bad = int((res2["status"] != 0).sum())
+            if outputs is not None:
+                outputs.append((f"N{N}_" if len(wl["horizons"]) > 1 else "", step_outputs(s, res2)))
+            if args.full:
+                # pass 2: same steps again with HIP events around each kernel for the roofline numbers
+                _, ksec, (gathered, best, info2) = run(s, tick, K, W, True, select)
+                info["gather_ms"], info["select_ms"] = info2.get("gather_ms"), info2.get("select_ms")   # per-step event pairs exist in this pass only
+                res2 = s.results()
             legs.append(dict(N=N, Ts=Ts, dt=dt, ksec=ksec, n_bad=n_bad, info=info, qp_iter=res2["qp_iter"].copy(), path=s.last_kernel_path(),
                              lds=s.lds_kernel_info(), pit=int(s.pit_last().sum()), shared=shared, device_bytes=s.device_bytes, status_hist=np.bincount(res2["status"], minlength=5).tolist()))
             last = (s, gathered, best)
@@ -1239,44 +1337,6 @@ def main(argv=None):
         if rank == 0:
             lg = legs[-1] if len(legs) == 1 else max(legs, key=lambda l: l["dt"])   # roofline: the (slowest) leg's dominant kernel
             N = lg["N"]
-            qp_fl = qp_flops(lg["qp_iter"], N)
-            lin_fl = B * N * F_LIN
-            ksec = lg["ksec"]
-            if lg["path"] in KERNEL_NAMES:  # one kernel does both phases
-                dom, dom_fl, dom_t = KERNEL_NAMES[lg["path"]], qp_fl + lin_fl, ksec[1]
-                if lg["path"] == 3 and 2 * lg["pit"] > B:
-                    dom = PIT_KERNELS
-                kernel_ms = {dom: ksec[1] * 1e3}
-            else:
-                dom = "qp_kernel" if ksec[1] >= ksec[0] else "lin_wave_kernel"
-                dom_fl, dom_t = (qp_fl, ksec[1]) if dom == "qp_kernel" else (lin_fl, ksec[0])
-                kernel_ms = {"lin_wave_kernel": ksec[0] * 1e3, "qp_kernel": ksec[1] * 1e3}
-            achieved = dom_fl / dom_t / 1e12
-            alg_bytes = algorithmic_bytes(N, lg["shared"])
-            traffic, traffic_src = None, None
-            why_not_live = None
-            profiled = bool(os.environ.get("ROCP_TOOL_LIBRARIES")) or "rocprofiler" in os.environ.get("LD_PRELOAD", "")   # this run is itself under rocprofv3
-            roof_valu = None
-            if world == 1 and len(legs) == 1 and not args.no_traffic and not args.no_extra and not profiled and not os.environ.get("BROV_BENCH_PMC_CHILD"):
-                cal = pmc_calibration()
-                pmc, why = live_pmc(fwd_args(args), dom, (("FETCH_SIZE",), ("WRITE_SIZE",), SQ_PASS)) if cal else (None, "no committed counter calibration")
-                if pmc is None:
-                    why_not_live = why
-                else:
-                    traffic, traffic_src = traffic_from_counts(pmc, cal)
-                    roof_valu = valu_roofline(pmc, dom)
-            for pj in (() if traffic is not None else ("r4_pmc_summary.json", "r3_pmc_summary.json", "r2_pmc_summary.json", "r1_pmc_summary.json")):
-                try:
-                    pm = json.load(open(os.path.join(ROOT, "profiles", pj)))
-                    ent = pm.get("runs", {}).get(f"cfg{args.config}_N{N}", pm if (pm.get("batch") == B and pm.get("N") == N) else {})
-                    t = ent.get("hbm_bytes_per_launch", {}).get(dom) if B == BATCH_PER_GPU and not args.force_ipm and args.path == 0 else None
-                    if t is not None:
-                        traffic, traffic_src = t, (f"profiles/{pj}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, not this run" +
-                                                   (f" (live passes: {why_not_live})" if why_not_live else ""))
-                        break
-                except Exception:
-                    pass
-            per_gpu_rate = B * K / lg["dt"]
             out = {
                 "metric": "NMPC RTI solves/s (N=20, 12 states / 4 inputs), batch 4096 per GPU" if args.config == 2 and N == 20 and B == 4096
                 else f"NMPC RTI solves/s (12 states / 4 inputs), config {args.config}",
@@ -1298,21 +1358,11 @@ def main(argv=None):
                    if world > torch.cuda.device_count() else {}),
                 "solver_status_nonzero": lg["n_bad"], "status_histogram": lg["status_hist"],
                 "mean_qp_iter": float(lg["qp_iter"].mean()), "ipm_instance_fraction": float((lg["qp_iter"] > 0).mean()),
-                "kernel_ms": kernel_ms, "device_bytes": lg["device_bytes"],
-                "roofline": {"kernel": dom, "bound": "mfma", "achieved": achieved, "peak": PEAK_FP64_MFMA_TFLOPS,
-                             "unit": "TFLOP/s", "frac": achieved / PEAK_FP64_MFMA_TFLOPS, "traffic": traffic, "traffic_source": traffic_src,
-                             "N": N, "algorithmic_flops_per_launch": dom_fl,
-                             "note": "FP64; algorithmic flops = factorisations/solves actually required by each instance "
-                                     "(DESIGN.md Accounting), not the MFMA-issued flops"},
-                **({"roofline_valu": roof_valu} if roof_valu else {}),
-                "roofline_hbm": {"bound": "hbm", "achieved": per_gpu_rate * alg_bytes / 1e9, "peak": PEAK_HBM_GBS,
-                                 "unit": "GB/s", "frac": per_gpu_rate * alg_bytes / 1e9 / PEAK_HBM_GBS,
-                                 "algorithmic_bytes_per_solve": alg_bytes,
-                                 "algorithmic_bytes_survey_general": survey_bytes(N)["general"],
-                                 "algorithmic_bytes_survey_shared_constant": survey_bytes(N)["shared_constant"],
-                                 **(traffic_ratios(traffic, B, N) if traffic else {}),
-                                 "formula": "8*[12 + (0 if one window is shared by the batch else 16(N+1)) + 16(N+1) + 2*(12(N+1)+4N)] + 104"},
             }
+            if args.full:   # kernel times of pass 2, the roofline figures and (one rank, one leg) the counter child runs
+                out.update(roofline_block(args, lg, B, K, world, len(legs)))
+            else:
+                out["device_bytes"] = lg["device_bytes"]
             if len(legs) > 1:
                 out["sweep"] = {f"N{l['N']}": dict(solves_per_s=total * K / l["dt"], ms_per_step=l["dt"] / K * 1e3,
                                                    per_rank_ms=l["info"]["per_rank_ms"], gather_ms=l["info"].get("gather_ms"),
@@ -1342,7 +1392,7 @@ def main(argv=None):
                     out["select_best"]["last_step_index_on_device"] = D.padded_to_global(int(best[0].item()), counts)
         s.close()
 
-        extra = extras_ok and rank == 0 and world == 1 and args.config == 2 and not args.force_ipm and not args.no_extra
+        extra = extras_ok and args.full and rank == 0 and world == 1 and args.config == 2 and not args.force_ipm and not args.no_extra
         if extra:
             # the headline never runs an interior-point iteration (no bound is active on the nominal circle): report the legs that do
             (N, Ts) = wl["horizons"][0]
@@ -1464,11 +1514,14 @@ def main(argv=None):
                     cancel_guard()
                 emit(pre)
             os._exit(0)   # (a probe may be left hanging on its thread, and a collective kernel on the device: no interpreter shutdown)
-    out = measure(args)
+    outputs = [] if (args.dump_outputs and rank == 0) else None
+    out = measure(args, outputs=outputs)
+    if outputs is not None:
+        write_outputs(args.dump_outputs, outputs)
     if gather0 and rank == 0:
         out["solve_only"] = {"value": pre["value"], "unit": "solves/s", "ms_per_step": pre["ms_per_step"], "per_rank_ms": pre["per_rank_ms"],
                              "note": "the same steps without the per-step all-gather (measured first, control-plane barrier only)"}
-    default_run = args.config == 2 and args.scaling == "weak" and not args.force_ipm and not args.no_extra and not args.batch and not args.horizon
+    default_run = args.full and args.config == 2 and args.scaling == "weak" and not args.force_ipm and not args.no_extra and not args.batch and not args.horizon
     if default_run and world == 1 and rank == 0 and os.environ.get("BROV_BENCH_STRONG_LEGS") != "1":
         # BASELINE.json configs[2..4] in the SAME line the driver records (round 3 had them in builder-run side files only)
         out["configs"] = configs_block(ba, args, local_rank)
@@ -1486,7 +1539,7 @@ def main(argv=None):
                 out[f"config{cfg}_strong"] = {k: leg[k] for k in keep if k in leg}
                 out[f"config{cfg}_strong"]["workload"] = leg["config"]["workload"]
     extra = default_run and rank == 0 and world == 1
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(BATCH_PER_GPU)
         if extra:
             out["cpu_baseline_single_thread"] = cpu_single_thread()

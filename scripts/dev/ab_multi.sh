@@ -7,7 +7,7 @@ cp $L/libbluerov2_nmpc.so /tmp/keep.so
 for rep in $(seq $REPS); do for f in $L/libbluerov2_nmpc_*.so; do
   tag=$(basename $f .so); tag=${tag#libbluerov2_nmpc_}
   cp $f $L/libbluerov2_nmpc.so
-  python bench.py --no-cpu-baseline --no-traffic --no-extra "$@" 2>/dev/null | python -c "
+  python bench.py --full --no-cpu-baseline --no-traffic --no-extra "$@" 2>/dev/null | python -c "
 import json,sys; o=json.loads(sys.stdin.read()); print('$tag rep $rep', round(o['value']/1e6,3), o.get('kernel_ms'), {k:round(v['solves_per_s']/1e6,3) for k,v in o.get('sweep',{}).items()})"
   if [ -n "$STAMPS" ]; then python scripts/dev/phase_stamps.py 4096 20 1 0 2>/dev/null | sed -n 1,8p | tr '\n' ' '; echo; fi
 done; done

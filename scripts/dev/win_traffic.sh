@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp
 for f in $L/libbluerov2_nmpc*.so; do
   tag=$(basename $f .so); [ "$f" != "$L/libbluerov2_nmpc.so" ] && cp $f $L/libbluerov2_nmpc.so
   for N in 80 40; do for c in FETCH_SIZE WRITE_SIZE; do
-    rm -rf /tmp/pm; rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/pm -o p -- python $R/bench.py --config 5 --horizon $N --no-cpu-baseline --no-extra --steps 10 > /dev/null 2>&1
+    rm -rf /tmp/pm; rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/pm -o p -- python $R/bench.py --full --config 5 --horizon $N --no-cpu-baseline --no-extra --steps 10 > /dev/null 2>&1
     python - "$tag" $N $c <<'PY'
 import csv,glob,sys
 tag,N,c=sys.argv[1:4]

@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R; O=gpurun_out/final; mkdir -p $O
 timeout 1800 python -m pytest tests -m gpu -q --timeout 900 > $O/suite.log 2>&1; echo "suite rc=$?"; grep -n "^E  \|FAILED\|passed\|failed" $O/suite.log | cut -c1-300 | tail -6; cp gpurun_out/parity_excused.json $O/
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
-python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; python - <<PY
+python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; python - <<PY
 import json
 o=json.loads(open("$O/bench.json").read().strip().splitlines()[-1])
 print('headline', round(o['value']/1e6,3), o['kernel_ms'], 'frac', round(o['roofline']['frac'],4), 'valu', round(o['roofline_valu']['frac'],4), 'traffic', o['roofline']['traffic'])

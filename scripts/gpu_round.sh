@@ -12,7 +12,7 @@ if [ -z "$SKIP_SUITE" ]; then
   cp gpurun_out/parity_excused.json $O/ 2>/dev/null
 fi
 if [ -z "$SKIP_BENCH" ]; then
-  python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; python - <<PY
+  python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; python - <<PY
 import json
 o=json.loads(open("$O/bench.json").read().strip().splitlines()[-1])
 print('headline', round(o['value']/1e6,3), o['kernel_ms'], 'frac', round(o['roofline']['frac'],4))

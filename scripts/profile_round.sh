@@ -10,17 +10,17 @@ mkdir -p $OUT
 # suite before this script would otherwise be what gets recorded)
 ( cd $R && timeout 2400 python -m pytest tests -m gpu -q --timeout 900 -rfE > $OUT/pytest_gpu.log 2>&1; tail -3 $OUT/pytest_gpu.log )
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py > $OUT/bench_plain.json 2> $OUT/bench_plain.err
-for c in 3 4 5; do python $R/bench.py --config $c --no-cpu-baseline > $OUT/bench_cfg$c.json 2> $OUT/bench_cfg$c.err; done
-python $R/bench.py --path 1 --no-cpu-baseline --no-extra > $OUT/bench_streaming.json 2> $OUT/bench_streaming.err
-python $R/bench.py --config 5 --path 1 --no-cpu-baseline > $OUT/bench_cfg5_streaming.json 2> $OUT/bench_cfg5_streaming.err
-python $R/bench.py --batch 16384 --no-cpu-baseline --no-extra > $OUT/bench_b16384.json 2> $OUT/bench_b16384.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o stats -- python $R/bench.py --no-cpu-baseline --no-extra > $OUT/bench_stats.json 2> $OUT/bench_stats.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_cfg5 -o stats -- python $R/bench.py --config 5 --no-cpu-baseline > $OUT/bench_cfg5_stats.json 2> $OUT/bench_cfg5_stats.err
+python $R/bench.py --full > $OUT/bench_plain.json 2> $OUT/bench_plain.err
+for c in 3 4 5; do python $R/bench.py --full --config $c --no-cpu-baseline > $OUT/bench_cfg$c.json 2> $OUT/bench_cfg$c.err; done
+python $R/bench.py --full --path 1 --no-cpu-baseline --no-extra > $OUT/bench_streaming.json 2> $OUT/bench_streaming.err
+python $R/bench.py --full --config 5 --path 1 --no-cpu-baseline > $OUT/bench_cfg5_streaming.json 2> $OUT/bench_cfg5_streaming.err
+python $R/bench.py --full --batch 16384 --no-cpu-baseline --no-extra > $OUT/bench_b16384.json 2> $OUT/bench_b16384.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o stats -- python $R/bench.py --full --no-cpu-baseline --no-extra > $OUT/bench_stats.json 2> $OUT/bench_stats.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_cfg5 -o stats -- python $R/bench.py --full --config 5 --no-cpu-baseline > $OUT/bench_cfg5_stats.json 2> $OUT/bench_cfg5_stats.err
 # small batches at the shipped horizon: the resident windowed kernel (one window = the whole horizon, four waves per block)
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_res -o stats -- python $R/bench.py --config 5 --horizon 80 --batch 64 --no-cpu-baseline > $OUT/bench_N80_B64_resident.json 2> $OUT/bench_N80_B64_resident.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_res -o stats -- python $R/bench.py --full --config 5 --horizon 80 --batch 64 --no-cpu-baseline > $OUT/bench_N80_B64_resident.json 2> $OUT/bench_N80_B64_resident.err
 # between one and two instances per CU at the shipped horizon: the parallel-in-time kernel with one block per instance
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_mid -o stats -- python $R/bench.py --config 5 --horizon 80 --batch 512 --no-cpu-baseline > $OUT/bench_N80_B512_rounds.json 2> $OUT/bench_N80_B512_rounds.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_mid -o stats -- python $R/bench.py --full --config 5 --horizon 80 --batch 512 --no-cpu-baseline > $OUT/bench_N80_B512_rounds.json 2> $OUT/bench_N80_B512_rounds.err
 # counters in their own runs, --kernel-trace only (no --stats / sys-trace together with --pmc on this pool)
 $R/scripts/pmc_pass.sh $OUT/pmc_cfg2_N20
 $R/scripts/pmc_pass.sh $OUT/pmc_cfg5_N80 --config 5 --horizon 80

@@ -75,15 +75,15 @@ def test_two_ranks_on_one_gpu_over_gloo_select_what_a_single_rank_selects():
 
 
 def test_the_drivers_default_command_with_four_ranks_on_the_visible_gpus_over_gloo():
-    """`python bench.py --gpus 4` exactly as the driver's SCALE run issues it (default config, weak scaling, plus the strong legs of configs 4 / 5 a
-    default multi-rank run appends), with the four ranks sharing whatever GPUs the box has and the collective over gloo: the first SCALE run on an
+    """`python bench.py --gpus 4 --full` (default config, weak scaling, plus the strong legs of configs 4 / 5 a
+    default multi-rank --full run appends), with the four ranks sharing whatever GPUs the box has and the collective over gloo: the first SCALE run on an
     8-GPU node must not be the first execution of this path with more than one rank"""
     import torch
     assert torch.cuda.is_available()
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env["BROV_BENCH_BACKEND"] = "gloo"
-    pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "5", "--warmup", "2"], stdout=subprocess.PIPE,
+    pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "5", "--warmup", "2", "--full"], stdout=subprocess.PIPE,
                         stderr=subprocess.PIPE, text=True, env=env, timeout=900)
     lines = [ln for ln in pr.stdout.splitlines() if ln.startswith("{")]
     assert pr.returncode == 0 and len(lines) == 1, (pr.returncode, pr.stdout[-2000:], pr.stderr[-3000:])

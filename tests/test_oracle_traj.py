@@ -1,12 +1,14 @@
 """Pin the trajectory/window oracle against the reference's own data files: the `%f` text of circle()/lemniscate() has the
 SHA-256 of bluerov2_path/config/traj/{circle,lemniscate}.txt (digests + leading/trailing rows in tests/golden/traj_head.npz)."""
+import gzip
 import hashlib
 import os
 
 import numpy as np
-import pytest
 
 from oracle import trajectory_oracle as T
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def _sha(b):
@@ -32,10 +34,12 @@ def test_lemniscate_reproduces_reference_file(golden_traj):
     assert T.to_text(m).decode().splitlines()[1].startswith("1.999375 0.049979 -20.000000 0.000000 0.000000 0.000000 -0.024997 0.998750")
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/bluerov2_path"), reason="reference tree not present")
 def test_against_reference_files_directly():
+    # bluerov2_path/config/traj/{circle,lemniscate}.txt, stored byte for byte (gzip) in tests/golden/
     for name, gen in (("circle", T.circle), ("lemniscate", T.lemniscate)):
-        ref = open(f"/root/reference/bluerov2_path/config/traj/{name}.txt", "rb").read()
+        with gzip.open(os.path.join(GOLDEN, f"{name}_txt.gz"), "rb") as f:
+            ref = f.read()
+        assert hashlib.sha256(ref).digest() == bytes(np.load(os.path.join(GOLDEN, "traj_head.npz"))[f"{name}_sha256"])
         assert T.to_text(gen()) == ref
 
 
