@@ -1311,6 +1311,14 @@ struct brov_ekf {
 
 extern "C" const char* brov_ekf_last_error(void) { return g_ekf_err.c_str(); }
 
+// for the RLS-FF estimator (rls_kernel.hip): `st` waits on the device for the observer's last update kernel -- the estimate it reads
+namespace brov {
+int ekf_wait_last_update(const brov_ekf* e, hipStream_t st) {
+    if (e->ev_valid) EKFCHK(hipStreamWaitEvent(st, e->ev[1], 0));
+    return BROV_OK;
+}
+}  // namespace brov
+
 extern "C" void brov_ekf_default_params(brov_ekf_params* p) {
     // bluerov2_dob.h:171-183,208; bluerov2_dob.cpp:52-62
     static const double am[6] = {1.7182, 0, 5.468, 0, 1.2481, 0.4006};

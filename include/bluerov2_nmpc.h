@@ -428,6 +428,67 @@ int brov_ekf_apply_to_solver(brov_ekf* e, brov_solver* s, void* stream);
 /* seconds of the last update kernel (HIP events on its stream) */
 int brov_ekf_last_update_seconds(brov_ekf* e, double* seconds);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Batched RLS-FF parameter estimator of the adaptive MPC node: B independent copies of the reference's recursive least squares
+ * with a variable forgetting factor BLUEROV2_AMPC::RLSFF() (bluerov2_dobmpc/src/bluerov2_ampc.cpp:731-1046), which the node runs
+ * every tick between the EKF and the solve (bluerov2_ampc_node.cpp:28-30).  Four independent axes a = X, Y, Z, N (surge, sway,
+ * heave, yaw; the reference's K / M axes are never updated), each with theta in R^4 (0 at start), P in R^4x4 (p0 I), lambda (lambda0)
+ * and two windows of prediction errors (n_short = FF_n, n_long = FF_d, bluerov2_ampc.h:239-240).  One tick of axis a:
+ *     x = [acc_a, v_a, 1, v_a |v_a|]  (acc = (v - v_prev)/dt of pose_cb, :163-168),  y = the EKF's disturbance estimate esti_x(12|13|14|17)
+ *     e = y - x.theta;  e pushed onto both windows;  F = var_short / var_long  (mean = sum / size, var = sum (v - mean)^2 / size)
+ *     F > threshold: lambda -= step, not below lambda_min;  else lambda += step, not above lambda_max   (:776-793; the first tick's
+ *                    0/0 = NaN is not > threshold)
+ *     K = P x / (lambda + x.(P x)),  theta += K e,  P = (P - (K x^T) P) / lambda
+ * and the world-frame environmental disturbance wf_env from theta(2) and the measured Euler angles (:1000-1005, rows 4-6 as written
+ * there).  theta, P, lambda, F and e are bit-identical to a scalar restatement of these formulas (sums in index order, no FMA
+ * contraction, no reciprocals); wf_env goes through sin / cos.  State instance-major on the host side, axis order X, Y, Z, N, FP64.
+ * ------------------------------------------------------------------------------------------------------------------- */
+typedef struct brov_rls brov_rls;
+typedef struct brov_rls_params { /* defaults: bluerov2_ampc.h:171-180,239-240 and bluerov2_ampc.cpp:735,776-793 */
+    int32_t n_short, n_long;       /* window lengths, 5 / 50; each in [1, 256] */
+    double  threshold;             /* 0.8 */
+    double  lambda_step;           /* 0.01 */
+    double  lambda_min, lambda_max;/* 0.5, 1 */
+    double  lambda0;               /* 0.9; 0 < lambda_min <= lambda0 <= lambda_max */
+    double  p0;                    /* 1: P = p0 I after brov_rls_reset */
+    double  dt;                    /* 0.05: the accelerations of brov_rls_update_from_ekf; > 0 */
+    double  compensate_coef, rotor_constant;   /* AMPC's scaling of theta(2) into the NMPC parameters p[0..3] (:346-349) */
+} brov_rls_params;
+#define BROV_RLS_APPLY_DISTURBANCE 0   /* the shipped AMPC: p[0..3] only */
+#define BROV_RLS_APPLY_MODEL 1         /* also p[4..15] = theta(0), theta(1), theta(3) of X, Y, Z, N (the commented-out :355-378) */
+void brov_rls_default_params(brov_rls_params* p);
+const char* brov_rls_last_error(void); /* message of the last failing brov_rls_* call on this thread */
+int  brov_rls_create(brov_rls** out, int device, int batch, const brov_rls_params* p /* NULL: defaults */);
+void brov_rls_destroy(brov_rls* r);
+int  brov_rls_batch(const brov_rls* r);
+/* every instance: theta = 0, P = p0 I, lambda = lambda0, both windows empty, v_prev = 0 */
+int brov_rls_reset(brov_rls* r);
+/* HOST state; NULL skips that block.  set_state empties the windows. */
+int brov_rls_set_state_host(brov_rls* r, const double* theta /*[B][4][4]*/, const double* P /*[B][4][4][4]*/, const double* lambda /*[B][4]*/);
+int brov_rls_get_state_host(brov_rls* r, double* theta /*[B][4][4]*/, double* P /*[B][4][4][4]*/, double* lambda /*[B][4]*/,
+                            double* F /*[B][4], last tick*/, double* e /*[B][4], last tick*/);
+/* one RLS-FF tick of every instance and axis.  y = target (the EKF's body-frame disturbance estimate), acc / vel = body
+ * acceleration and velocity (u, v, w, r), rpy = measured Euler angles (wf_env only).  HOST or DEVICE pointers respectively. */
+int brov_rls_update_host(brov_rls* r, const double* y /*[B][4]*/, const double* acc /*[B][4]*/, const double* vel /*[B][4]*/,
+                         const double* rpy /*[B][3]*/, void* stream);
+int brov_rls_update_device(brov_rls* r, const double* y, const double* acc, const double* vel, const double* rpy, void* stream);
+/* the on-device AMPC tick (no host round trip): measurement = the solver's x0 (the plant state after brov_plant_step: u, v, w, r and
+ * the Euler angles), acc = (v - v_prev)/dt with v_prev kept here, target = the EKF's estimate x[12, 13, 14, 17]; ordered behind the
+ * solver's last stream (brov_order_stream) and behind the EKF's last update. */
+int brov_rls_update_from_ekf(brov_rls* r, const brov_ekf* ekf, brov_solver* s, void* stream);
+/* AMPC's parameter hand-off to every stage of instance b (:346-349): p[0] = theta_X(2)/compensate_coef, p[1] = theta_Y(2)/compensate_coef,
+ * p[2] = theta_Z(2)/rotor_constant, p[3] = theta_N(2)/rotor_constant.  BROV_RLS_APPLY_DISTURBANCE leaves p[4..15] and the 6-disturbance
+ * variant's roll / pitch values alone; BROV_RLS_APPLY_MODEL also writes p[4+a] = theta_a(0), p[8+a] = theta_a(1), p[12+a] = theta_a(3).
+ * (The reference with COMPENSATE_D == false leaves p[4..15] indeterminate: not reproduced.)  On the device plant the estimator, like
+ * the EKF, is created with compensate_coef = rotor_constant = 1 (see brov_ekf_apply_to_solver). */
+int brov_rls_apply_to_solver(brov_rls* r, brov_solver* s, int mode, void* stream);
+/* outputs of the last tick; NULL skips.  status 0 ok, 2 non-finite theta or P (a NaN input propagates as in the reference, in its
+ * own instance only) */
+int brov_rls_get_outputs_host(brov_rls* r, double* mpc_p /*[B][4]*/, double* wf_env /*[B][6]*/, int* status /*[B]*/);
+const double* brov_rls_theta_device(const brov_rls* r);   /* DEVICE theta, [4 components][B][4 axes] */
+/* seconds of the last update kernel (HIP events on its stream) */
+int brov_rls_last_update_seconds(brov_rls* r, double* seconds);
+
 #ifdef __cplusplus
 }
 #endif
