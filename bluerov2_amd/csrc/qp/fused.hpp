@@ -42,15 +42,11 @@ __device__ __forceinline__ bool rti_fused_step(const DevParams& P, int b, int la
     setup_inst(P, I, b, lane, W == 1 ? &lc : nullptr, yoff);
     // partial refactorisation of the active-set tries (riccati_backward_tries): checkpoint stage = ceil(N / 4); off for horizons too
     // short to gain from it and for instances the previous solve did not list as expensive
-#ifndef BROV_EXP_NO_SPLIT
     // (`listed` arrives in a vector register -- a plain load, requested ahead of the linearisation.  It is the same in every lane, and saying so
     // here keeps the checkpoint, hence the bounds of the factor sweep's stage loop, in scalar registers: with a vector bound the compiler
     // drives that loop, and every guard inside it, through exec masks)
     const bool listed_u = __builtin_amdgcn_readfirstlane((int)listed) != 0;
     I.ckpt = (N >= 8 && P.partial_refactor && listed_u) ? (N + 3) >> 2 : 0;
-#else
-    I.ckpt = 0; (void)listed;
-#endif
     I.lds_ba = (const lds_f64*)ba_s;
     I.lds_bv = (const lds_f64*)bv_s;
     I.lds_kt = (lds_f64*)kt_s;

@@ -88,9 +88,6 @@ __device__ __forceinline__ void qp_body(const DevParams& P, IT& I, int b, double
             if (lane + 64 * t < nv) ureg[t] = I.u[lane + 64 * t];
     }
     int status = 0, iters = 0;
-#if BROV_EXP_WIN_FUSE
-    WinFast wfast;   // (large-batch windowed kernel: see win_forward_fast)
-#endif
     double mu = 0.0, rho = 0.0;
     bool early = false, polished = false, use_vhat = false;
     int sched_p = -1;   // this instance's place in the next solve's list of expensive instances (work ordering; wave-uniform)
@@ -100,9 +97,7 @@ __device__ __forceinline__ void qp_body(const DevParams& P, IT& I, int b, double
     constexpr bool PART = EL || LDS >= 3;   // fused kernels and the windowed kernel's resident mode: stage checkpoint; windowed kernel: window-0 checkpoint
     bool illc0 = pre_illc;
     bool split0 = false;
-#ifndef BROV_EXP_NO_SPLIT
     if constexpr (EL) split0 = I.ckpt > 0;   // set by the kernel body: only instances that ran the QP loop in the previous solve
-#endif
     if constexpr (EL) { if (split0) {
         // the step-0 factor sweep in two parts with the checkpoint between them.  Measured: inside the stage loop a wave-uniform
         // `if (i == ckpt)` with the six stores costs the loop 7 % (registers and scheduling, taken or not); the split sweep still
@@ -167,14 +162,7 @@ __device__ __forceinline__ void qp_body(const DevParams& P, IT& I, int b, double
     if (__ballot(!ok) != 0ull) {
         status = BROV_STATUS_QP_FAILURE;
     } else {
-        // (large-batch windowed kernel, development build -DBROV_EXP_WIN_FUSE=1: forward sweep, check, adjoint sweep and full step in ONE pass over
-        // the windows when the answer stays inside the box -- win_forward_fast in qp/window.hpp, measured and not shipped)
-        bool fast_pass = false;
-#if BROV_EXP_WIN_FUSE
-        if constexpr (LDS == 3) fast_pass = P.early_exit != 0 && !robust;
-        if constexpr (LDS == 3) { if (fast_pass) wfast = win_forward_fast(P, I, *W, b, d0); }
-#endif
-        if (!fast_pass) sw_forward<LDS>(I, W, d0, cst);
+        sw_forward<LDS>(I, W, d0, cst);
         DBG_STAMP(3);
         bool feas = true;
         if constexpr (LDS >= 3) {
@@ -663,11 +651,6 @@ __device__ __forceinline__ void qp_body(const DevParams& P, IT& I, int b, double
         if constexpr (LDS >= 3) {
             if (W->nan) {
                 status = BROV_STATUS_NAN;
-#if BROV_EXP_WIN_FUSE
-            } else if (LDS == 3 && wfast.committed) {   // win_forward_fast has taken the step window by window
-                cost = wfast.cost_lane; u0v = wfast.u0_lane;
-                wrote_u0 = true;
-#endif
             } else {
                 win_adjoint_commit<LDS == 4>(P, I, *W, b, vfin, early, cost, u0v, P.mail != nullptr && P.mail_early != 0,
                                              [&](double cost_lane, double u0_lane) __attribute__((always_inline)) { emit_record(cost_lane, u0_lane, true); });

@@ -213,13 +213,9 @@ __device__ __forceinline__ void bwd_chunk(const IT& I, BwdState& S, int hi = -1,
     // parked lanes of the per-stage LDS stores write their value to a slot nobody reads (lds_tr[16]) with stride 0
     lds_f64* const kt_st0 = (LDS != 0 && cl < NX) ? I.lds_kt + rg * NX + cl : I.lds_tr + 16;
     const int kt_ststr = (cl < NX) ? kKtStage : 0;
-    // (kKffT, below: the feed-forward term comes out of column 12 of the gain product)
-#ifndef BROV_EXP_NO_KFF_IN_T
-    constexpr bool kKffT = kR6;   // (both fused families: ks carries kff in column 12 with the right sign in either)
-#else
-    constexpr bool kKffT = false;
-#endif
-    constexpr int kKffCol = kKffT ? 12 : 0;
+    // (kR6, below: the feed-forward term comes out of column 12 of the gain product -- both fused families: ks carries kff there with
+    // the right sign in either)
+    constexpr int kKffCol = kR6 ? 12 : 0;
     lds_f64* const kf_st0 = (LDS != 0 && cl == kKffCol) ? I.lds_kff + rg : I.lds_tr + 16;
     const int kf_ststr = (cl == kKffCol) ? 4 : 0;
     lds_f64* ktp = kt_st0 + lmul(N - 1, kt_ststr);   // kR6: running store addresses (the stages are visited in order N-1 .. lo)
@@ -379,10 +375,8 @@ __device__ __forceinline__ void bwd_chunk(const IT& I, BwdState& S, int hi = -1,
                     m11 = e11 - (m21 * x10 + m31 * x11);                          // M11 = E^-1 - M12 X'
                 }
                 // the relative pivots of the elimination (kPivotRho): four compares, off the chain
-#ifndef BROV_EXP_NO_WATCH
                 if constexpr (kR6) illm |= __ballot(detE < kPivotRho * aa) | __ballot(s00 < kPivotRho * a22) | __ballot(s11 < kPivotRho * a33) | __ballot(detS < kPivotRho * ss);
                 else illc = illc | (detE < kPivotRho * aa) | (s00 < kPivotRho * a22) | (s11 < kPivotRho * a33) | (detS < kPivotRho * ss);
-#endif
             }
             if constexpr (!kR6Z) {
                 // Mtile: lane (rg = m, cl = n < 4) = M[m][n]; msel: the same element for every column n = cl & 3
@@ -418,7 +412,7 @@ __device__ __forceinline__ void bwd_chunk(const IT& I, BwdState& S, int hi = -1,
                 T = tn1(li, Y[0], z4);               // L^-T Y = M Hu through the factor, not through the explicit inverse
                 ks = -T[0];
             } else {
-                if constexpr (kKffT) {
+                if constexpr (kR6) {
                     // Round 6.  kff = -M g_u rides in the gain product: columns 12..15 of T = -M Hu are -M Huu = -I, known without
                     // computing them, and nothing reads them (S and p use rows / columns 0..11 of what they feed) -- so column 12 of
                     // the right operand carries g_u instead of Huu(:, 0) (one row broadcast of column 0 of g, one select), and the
@@ -448,7 +442,7 @@ __device__ __forceinline__ void bwd_chunk(const IT& I, BwdState& S, int hi = -1,
             } else if constexpr (LDS == 3) {
                 const d4 gC = {g[0], g[1], g[2], 0.0};
                 pn = tn1(xt2, g[3], gC);
-            } else if constexpr (kKffT) {
+            } else if constexpr (kR6) {
                 pn = tn1(ks, g[3], g);
                 pn[3] = ks;   // lanes of column 12: kff (stored from there)
             } else {
@@ -477,7 +471,7 @@ __device__ __forceinline__ void bwd_chunk(const IT& I, BwdState& S, int hi = -1,
             }
             if constexpr (LDS) {  // only column 0 of rows 12..15 is M gu: the other lanes are parked on the constant-zero slot
                 if constexpr (kR6) {
-                    *kfp = (kR6Z || kKffT) ? pn[3] : -pn[3]; kfp -= kf_ststr;   // (kR6Z: the operand tile carries -M; kKffT: pn[3] is ks, the gain operand itself)
+                    *kfp = pn[3]; kfp -= kf_ststr;   // (pn[3] is ks, the gain operand itself: its column 12 carries kff)
                 } else {
                     lds_f64* kp = (cl == 0) ? I.lds_kff + i * 4 + rg : I.lds_zero;
                     *kp = (cl == 0) ? -pn[3] : 0.0;

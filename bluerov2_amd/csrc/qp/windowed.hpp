@@ -24,9 +24,8 @@ __host__ __device__ inline size_t win_ws_doubles(int N, int L) {
     return (size_t)((N + L - 1) / L) * win_img_doubles(L)                  // parked window images
            + (size_t)N * 4 + (size_t)(N + 1) * NX                          // vhat, dx (flat over the horizon)
            + (size_t)N * (64 + 64 + NX) + (size_t)IPM_NARR * 4 * N         // Ks Mt Pb | interior-point vectors
-           + kWinCk                                                        // (P, p) entering window 0 (resident mode: stage ckpt): checkpoint of the partial
+           + kWinCk;                                                       // (P, p) entering window 0 (resident mode: stage ckpt): checkpoint of the partial
                                                                            // refactorisation; resident mode: + the step-0 feed-forward terms (4 N <= 512)
-           + (size_t)((N + L - 1) / L) * 384 + win_stage_doubles(N);       // development build BROV_EXP_WIN_FUSE: (P, p) at the inner window boundaries, staged rows (win_forward_fast)
 }
 // RES: resident mode -- one window = the whole horizon (N <= 81) in a slice of up to 160 KB, one block per CU; for batches of at most
 // one instance per CU.  Nothing is parked and no window is fetched.  A separate instantiation (rti_window_kernel_res), so that the
@@ -271,13 +270,6 @@ __device__ __forceinline__ void rti_window_body(const DevParams& P) {
             } else {
                 bwd_chunk<true, 3, false, true>(I, S);
             }
-#if BROV_EXP_WIN_FUSE
-            if (!RES && c >= 1) {   // round 6: (P, p) as they cross the boundary into window c - 1 (win_forward_fast: the costate there)
-                double* bd = ws_ck + kWinCk + (size_t)(c - 1) * 384;
-#pragma unroll
-                for (int r = 0; r < 3; r++) { bd[r * 64 + lane] = S.P[r]; bd[192 + r * 64 + lane] = S.pv[r]; }
-            }
-#endif
             if (!RES && c == 1 && I.ckpt > 0) {   // (P, p) as they enter window 0: six coalesced 512-byte stores, never waited for
 #pragma unroll
                 for (int r = 0; r < 3; r++) { ws_ck[r * 64 + lane] = S.P[r]; ws_ck[192 + r * 64 + lane] = S.pv[r]; }
@@ -322,9 +314,7 @@ __device__ __forceinline__ void rti_window_body(const DevParams& P) {
 #ifdef BROV_DBG_WIN
         W.t_fetch = 0; W.n_fetch = 0;
 #endif
-#if !defined(BROV_WIN_EXP) || BROV_WIN_EXP != 1
         qp_body<(RES ? 4 : 3), InstT, false, LONG>(P, I, b, part, nanp, &W, S.ok, S.illc);
-#endif
 #ifdef BROV_DBG_WIN
         if (P.dbg && lane == 0) { P.dbg[(size_t)P.B * 8 + (size_t)b * 8 + 3] = W.t_fetch; P.dbg[(size_t)P.B * 8 + (size_t)b * 8 + 4] = W.n_fetch; }
 #endif

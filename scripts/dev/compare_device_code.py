@@ -27,11 +27,18 @@ def kernels(path):
                 name_prev, body_prev = name, body
             continue
         t = ln.split("//")[0].strip()
-        if name and t:
+        if name and t and "file format" not in t:   # (the header of the next code object's listing names a temporary file)
             body.append(t)
     if name:
         out[name] = body
-    return out
+    return {k: renumber_labels(v) for k, v in out.items()}
+
+
+def renumber_labels(body):
+    """the disassembler numbers the labels of a code object in sequence over its functions: a kernel's labels shift when a kernel
+    in front of it is added or removed.  Number them per function, in order of first appearance."""
+    ids = {}
+    return [re.sub(r"\bL(\d+)\b", lambda m: "L%d" % ids.setdefault(m.group(1), len(ids)), t) for t in body]
 
 
 a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
@@ -41,6 +48,7 @@ for k in sorted(set(a) | set(b)):
     hb = hashlib.md5("\n".join(b.get(k, [])).encode()).hexdigest()[:12]
     ok = ha == hb
     same &= ok
-    print(f"{k[:70]:70s} {len(a.get(k, [])):7d} {ha}   {len(b.get(k, [])):7d} {hb}   {'same' if ok else 'DIFFERENT'}")
+    verdict = "same" if ok else ("DIFFERENT" if k in a and k in b else "missing in " + (sys.argv[1] if k not in a else sys.argv[2]))
+    print(f"{k[:70]:70s} {len(a.get(k, [])):7d} {ha}   {len(b.get(k, [])):7d} {hb}   {verdict}")
 print("IDENTICAL device code" if same else "device code DIFFERS")
 sys.exit(0 if same else 1)

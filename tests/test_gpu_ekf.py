@@ -2,6 +2,8 @@
 C ABI (brov_ekf_*).  Tolerances: the filter differentiates by forward differences with d = 1e-6 (last-bit differences of
 sin/cos and of FMA contraction are amplified by ~1e10 ulp in F and H) and inverts an innovation covariance of condition
 ~1e9-1e10 explicitly, exactly as the reference does; two correct FP64 implementations agree to ~1e-6 of the innovation."""
+import os
+
 import numpy as np
 import pytest
 
@@ -260,11 +262,12 @@ def test_batch_mismatch_is_rejected(ba):
     e.close(); s.close()
 
 
-def test_dpp_and_lds_broadcast_kernels_agree(ba, orc, monkeypatch):
-    """the default (structured DPP) kernel against the dense DPP row-broadcast kernel (BROV_EKF_VARIANT=1) and the first, LDS-broadcast
-    kernel (BROV_EKF_VARIANT=0): one tick from the same state.  (Over several ticks of a repeated measurement any two FP64 evaluations
-    drift apart -- the finite-difference Jacobians amplify last-bit differences of the RK4 map by ~1e10; scripts/dev/ekf_variant_diff.py
-    prints that drift for the three kernels and the oracle.)"""
+def test_dpp_and_lds_broadcast_kernels_agree(ba, orc):
+    """the shipped (structured DPP) kernel against the two kernels it replaced, one tick from the same state: the dense DPP
+    row-broadcast kernel (keys <field>_v1 of tests/golden/ekf_retired_kernels.npz) and the first, LDS-broadcast kernel
+    ekf_update_kernel (<field>_v0).  Their outputs were recorded on an MI355X at commit d7af66b, the last one that built them.
+    (Over several ticks of a repeated measurement any two FP64 evaluations drift apart -- the finite-difference Jacobians amplify
+    last-bit differences of the RK4 map by ~1e10.)"""
     c = T.np_consts(orc.par)
     rng = np.random.default_rng(31)
     B = 37
@@ -272,13 +275,11 @@ def test_dpp_and_lds_broadcast_kernels_agree(ba, orc, monkeypatch):
     A = rng.normal(size=(B, 18, 18)) * 0.2
     P = np.einsum("bij,bkj->bik", A, A) + np.eye(18) * 0.3
     thrust, y12, acc = consistent_inputs(c, rng, x)
-    out = {}
-    for variant in ("2", "1", "0"):
-        monkeypatch.setenv("BROV_EKF_VARIANT", variant)
-        e = ba.BatchEkf(B)
-        e.set_state(x, P); e.update(thrust, y12, acc)
-        out[variant] = e.state() + e.outputs()
-        e.close()
-    for other in ("1", "0"):
-        for a, b in zip(out["2"], out[other]):
-            np.testing.assert_allclose(a, b, rtol=1e-6, atol=1e-6)
+    e = ba.BatchEkf(B)
+    e.set_state(x, P); e.update(thrust, y12, acc)
+    out = e.state() + e.outputs()
+    e.close()
+    rec = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ekf_retired_kernels.npz"))
+    for variant in ("1", "0"):
+        for a, f in zip(out, ("x", "P", "wf", "mp", "status")):
+            np.testing.assert_allclose(a, rec[f"{f}_v{variant}"], rtol=1e-6, atol=1e-6)
