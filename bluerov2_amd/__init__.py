@@ -5,11 +5,13 @@ is the thin host-side mirror of that ABI; there is no CPU or PyTorch fallback --
 solver raises.
 """
 from .solver import (BatchSolver, SolverOptions, RESULT_DTYPE, P_NOMINAL, build_library, library_path,  # noqa: F401
-                     NoDeviceError, thrust_allocation, PATH_AUTO, PATH_STREAMING, PATH_FUSED, PATH_WINDOWED)
+                     NoDeviceError, thrust_allocation, PATH_AUTO, PATH_STREAMING, PATH_FUSED, PATH_WINDOWED,
+                     WRENCH_OFF, WRENCH_CONSTANT, WRENCH_PERIODIC, WRENCH_TABLE)
 
 from .ekf import BatchEkf, EkfParams  # noqa: F401,E402
 from .rls import BatchRls, RlsParams, APPLY_DISTURBANCE, APPLY_MODEL  # noqa: F401,E402
 from .group import SolverGroup, GATHER_RECORDS, GATHER_PACKED, rccl_version, unique_id  # noqa: F401,E402
 
 __all__ = ["SolverGroup", "GATHER_RECORDS", "GATHER_PACKED", "rccl_version", "unique_id", "BatchEkf", "EkfParams", "BatchRls", "RlsParams", "APPLY_DISTURBANCE", "APPLY_MODEL", "BatchSolver", "SolverOptions", "RESULT_DTYPE", "P_NOMINAL", "build_library", "library_path",
-           "NoDeviceError", "thrust_allocation", "PATH_AUTO", "PATH_STREAMING", "PATH_FUSED", "PATH_WINDOWED"]
+           "NoDeviceError", "thrust_allocation", "PATH_AUTO", "PATH_STREAMING", "PATH_FUSED", "PATH_WINDOWED",
+           "WRENCH_OFF", "WRENCH_CONSTANT", "WRENCH_PERIODIC", "WRENCH_TABLE"]

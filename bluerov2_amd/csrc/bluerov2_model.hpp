@@ -127,4 +127,46 @@ __device__ __forceinline__ void model_f(const double (&x)[NX], const Wrench& w, 
     f[11] = (w.k5 - (kIy - kIx) * sp.wp * sp.wq + m.dn + m.ln * sp.wr + m.qn * fabs(sp.wr) * sp.wr) * m.imn;
 }
 
+// A wrench given in the WORLD frame (the reference's applyBodyWrench(), bluerov2_dob.cpp:876-890: reference_frame = "world"), constant
+// over a control tick; its body-frame image turns with the vehicle.
+struct WorldWrench { double fx, fy, fz, tx, ty, tz; };
+
+// xdot = f(x,u,p) under an additional world-frame wrench: the plant of brov_plant_step with a wrench mode in force (plant_wrench.hip).
+// Force and torque are projected with THIS stage point's attitude, f_b = R^T f_w, t_b = R^T t_w -- from the trig values the model computes
+// anyway -- and enter where the model's own disturbances do: dx, dy, dz, k3, k4, dn, ahead of the mass scaling.  An overload with the rows
+// written out again, not a default argument of the function above: the solver kernels that inline that one sit at their register limit
+// behind the build's scratch gate and ISA checkers, and must compile to the code they compiled to before this overload existed.
+__device__ __forceinline__ void model_f(const double (&x)[NX], const Wrench& w, const ModelPar& m, const WorldWrench& ww, double (&f)[NX],
+                                        StagePoint& sp) {
+    sincos_pio2(x[3], &sp.sph, &sp.cph);
+    sincos_pio2(x[4], &sp.sth, &sp.cth);
+    sincos_pio2(x[5], &sp.sps, &sp.cps);
+    sp.icth = 1.0 / sp.cth;
+    sp.vu = x[6]; sp.vv = x[7]; sp.vw = x[8]; sp.wp = x[9]; sp.wq = x[10]; sp.wr = x[11];
+    const double r00 = sp.cps * sp.cth, r01 = sp.cps * sp.sth * sp.sph - sp.sps * sp.cph,
+                 r02 = sp.sps * sp.sph + sp.cps * sp.cph * sp.sth;
+    const double r10 = sp.sps * sp.cth, r11 = sp.cps * sp.cph + sp.sph * sp.sth * sp.sps,
+                 r12 = sp.sth * sp.sps * sp.cph - sp.cps * sp.sph;
+    const double r20 = -sp.sth, r21 = sp.cth * sp.sph, r22 = sp.cth * sp.cph;
+    const double dx = m.dx + (r00 * ww.fx + r10 * ww.fy + r20 * ww.fz);
+    const double dy = m.dy + (r01 * ww.fx + r11 * ww.fy + r21 * ww.fz);
+    const double dz = m.dz + (r02 * ww.fx + r12 * ww.fy + r22 * ww.fz);
+    const double k3 = w.k3 + (r00 * ww.tx + r10 * ww.ty + r20 * ww.tz);
+    const double k4 = w.k4 + (r01 * ww.tx + r11 * ww.ty + r21 * ww.tz);
+    const double dn = m.dn + (r02 * ww.tx + r12 * ww.ty + r22 * ww.tz);
+    f[0] = r00 * sp.vu + r01 * sp.vv + r02 * sp.vw;
+    f[1] = r10 * sp.vu + r11 * sp.vv + r12 * sp.vw;
+    f[2] = r20 * sp.vu + r21 * sp.vv + r22 * sp.vw;
+    const double tth = sp.sth * sp.icth;
+    f[3] = sp.wp + sp.sps * tth * sp.wq + sp.cph * tth * sp.wr;  // sin(psi): reference quirk, bluerov2.py:133
+    f[4] = sp.cph * sp.wq + sp.sph * sp.wr;
+    f[5] = (sp.sph * sp.wq + sp.cph * sp.wr) * sp.icth;
+    f[6] = (w.k0 - kBouy * sp.sth + dx + m.lx * sp.vu + m.qx * fabs(sp.vu) * sp.vu) * m.imx;
+    f[7] = (w.k1 + kBouy * r21 + dy + m.ly * sp.vv + m.qy * fabs(sp.vv) * sp.vv) * m.imy;
+    f[8] = (w.k2 + kBouy * r22 + dz + m.lz * sp.vw + m.qz * fabs(sp.vw) * sp.vw) * m.imz;
+    f[9] = (k3 + (kIy - kIz) * sp.wq * sp.wr - kMzg * r21) * (1.0 / kIx);
+    f[10] = (k4 + (kIz - kIx) * sp.wp * sp.wr - kMzg * sp.sth) * (1.0 / kIy);
+    f[11] = (w.k5 - (kIy - kIx) * sp.wp * sp.wq + dn + m.ln * sp.wr + m.qn * fabs(sp.wr) * sp.wr) * m.imn;
+}
+
 }  // namespace brov

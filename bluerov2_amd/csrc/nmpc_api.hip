@@ -57,6 +57,10 @@ struct brov_solver {
     bool dist6 = false, prp_plant_set = false;
     bool pplant_set = false;     // explicit plant parameters given (brov_plant_set_params_host)
     bool pplant_stale = true;    // controller parameters changed since the plant's copy of them was taken
+    WrenchGen wr;                // world-frame wrench of the plant (brov_plant_wrench_*): mode OFF = the plant kernel as it always was
+    double *wr_const = nullptr, *wr_gain = nullptr, *wr_eval = nullptr;   // [B][6], [B], [B][6] (brov_plant_wrench_eval_host): allocated on first use
+    double* wr_tab = nullptr;    // [rows][6], replaced by every brov_plant_wrench_table_host
+    long long wr_tick = 0;       // plant steps so far (brov_plant_wrench_seek sets it)
     bool cand_set = false;       // candidate shape parameters resident in scratch3
     int cand_kind = 0;
     bool dump_lin = false;
@@ -362,6 +366,7 @@ extern "C" void brov_destroy(brov_solver* s) {
     // (a caller's own stream is the caller's to drain -- it may not exist any more; hipFree below waits for the device in any case)
     for (void* p : s->allocs) hipFree(p);
     if (s->traj) hipFree(s->traj);
+    if (s->wr_tab) hipFree(s->wr_tab);
     if (s->dbg) hipFree(s->dbg);
     if (s->pin) hipHostFree(s->pin);
     if (s->copy_stream) hipStreamDestroy(s->copy_stream);
@@ -742,12 +747,92 @@ static int ensure_plant_params(brov_solver* s, hipStream_t st) {
     }
     return BROV_OK;
 }
+// ---- time-varying world-frame wrench of the plant (plant_wrench.hip) ----------------------------------------------------------------
+static const double kWrenchMaxHalfPeriods = 4194304.0;   // 2^22: the half-period index has 22 bits of the amplitude counter
+// the periodic generator's half-period index at `tick` must fit its counter field
+static int wrench_tick_ok(const brov_solver* s, long long tick, const char* who) {
+    if (tick < 0) { g_err = std::string(who) + ": negative wrench tick"; return BROV_ERR_ARG; }
+    if (s->wr.mode == BROV_WRENCH_PERIODIC) {
+        const double j = std::floor((s->wr.phase0 + (double)tick * s->wr.dphi) / 3.14159265358979323846);
+        if (!(j < kWrenchMaxHalfPeriods)) { g_err = std::string(who) + ": the periodic wrench's half-period index floor(t / pi) must stay below 2^22"; return BROV_ERR_ARG; }
+    }
+    return BROV_OK;
+}
+extern "C" int brov_plant_wrench_constant_host(brov_solver* s, const double* w) {
+    if (!s || !w) return BROV_ERR_ARG;
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(sync_last(s));   // a plant step in flight may still read the buffer
+    if (!s->wr_const) { if (int rc = dalloc(s, &s->wr_const, (size_t)s->B * 6)) return rc; }
+    HIPCHK(hipMemcpy(s->wr_const, w, (size_t)s->B * 6 * sizeof(double), hipMemcpyHostToDevice));
+    s->wr.mode = BROV_WRENCH_CONSTANT; s->wr.w = s->wr_const;
+    return BROV_OK;
+}
+extern "C" int brov_plant_wrench_periodic(brov_solver* s, uint64_t seed, double scale, double phase0, double dphi, double tz_div) {
+    if (!s || !std::isfinite(scale) || !(phase0 >= 0.0) || !(dphi >= 0.0) || !std::isfinite(phase0) || !std::isfinite(dphi) || !std::isfinite(tz_div) ||
+        tz_div == 0.0) {
+        g_err = "brov_plant_wrench_periodic: scale, phase0 >= 0, dphi >= 0 and tz_div != 0 must be finite";
+        return BROV_ERR_ARG;
+    }
+    const WrenchGen keep = s->wr;
+    s->wr.mode = BROV_WRENCH_PERIODIC; s->wr.seed = seed; s->wr.scale = scale; s->wr.phase0 = phase0; s->wr.dphi = dphi; s->wr.tz_div = tz_div;
+    if (int rc = wrench_tick_ok(s, s->wr_tick, "brov_plant_wrench_periodic")) { s->wr = keep; return rc; }
+    return BROV_OK;
+}
+extern "C" int brov_plant_wrench_table_host(brov_solver* s, const double* tab, int rows, const double* gain) {
+    if (!s || !tab || rows < 1) return BROV_ERR_ARG;
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(sync_last(s));
+    if (gain && !s->wr_gain) { if (int rc = dalloc(s, &s->wr_gain, (size_t)s->B)) return rc; }
+    double* nt = nullptr;
+    HIPCHK(hipMalloc((void**)&nt, (size_t)rows * 6 * sizeof(double)));
+    hipError_t e = hipMemcpy(nt, tab, (size_t)rows * 6 * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess && gain) e = hipMemcpy(s->wr_gain, gain, (size_t)s->B * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { hipFree(nt); g_err = hipGetErrorString(e); return BROV_ERR_HIP; }
+    if (s->wr_tab) hipFree(s->wr_tab);
+    s->wr_tab = nt;
+    s->wr.mode = BROV_WRENCH_TABLE; s->wr.tab = nt; s->wr.rows = rows; s->wr.gain = gain ? s->wr_gain : nullptr;
+    return BROV_OK;
+}
+extern "C" int brov_plant_wrench_off(brov_solver* s) {
+    if (!s) return BROV_ERR_ARG;
+    s->wr.mode = BROV_WRENCH_OFF;
+    return BROV_OK;
+}
+extern "C" int brov_plant_wrench_mode(const brov_solver* s) { return s ? s->wr.mode : BROV_WRENCH_OFF; }
+extern "C" int brov_plant_wrench_seek(brov_solver* s, int64_t tick) {
+    if (!s) return BROV_ERR_ARG;
+    if (int rc = wrench_tick_ok(s, (long long)tick, "brov_plant_wrench_seek")) return rc;
+    s->wr_tick = (long long)tick;
+    return BROV_OK;
+}
+extern "C" int64_t brov_plant_wrench_tick(const brov_solver* s) { return s ? (int64_t)s->wr_tick : 0; }
+extern "C" int brov_plant_wrench_eval_host(brov_solver* s, int64_t tick, double* w) {
+    if (!s || !w) return BROV_ERR_ARG;
+    if (int rc = wrench_tick_ok(s, (long long)tick, "brov_plant_wrench_eval_host")) return rc;
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(sync_last(s));
+    if (!s->wr_eval) { if (int rc = dalloc(s, &s->wr_eval, (size_t)s->B * 6)) return rc; }
+    launch_wrench_eval(s->wr, s->B, (long long)tick, s->wr_eval, s->last_stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s->last_stream));
+    HIPCHK(hipMemcpy(w, s->wr_eval, (size_t)s->B * 6 * sizeof(double), hipMemcpyDeviceToHost));
+    return BROV_OK;
+}
+// one plant step of the tick counter's tick on `st`, with optional DEVICE logs of this tick; mode OFF: the plant kernel as it always was
+static void plant_step_on(brov_solver* s, double dt, int substeps, double* xlog, double* ulog, double* wlog, hipStream_t st) {
+    if (s->wr.mode == BROV_WRENCH_OFF)
+        launch_plant(s->x0, s->res, s->pplant, plant_rp(s), plant_rp_stride(s), s->B, dt, substeps, xlog, ulog, st);
+    else
+        launch_plant_wrench(s->x0, s->res, s->pplant, plant_rp(s), plant_rp_stride(s), s->B, dt, substeps, xlog, ulog, s->wr, s->wr_tick, wlog, st);
+    s->wr_tick++;
+}
 extern "C" int brov_plant_step(brov_solver* s, double dt, int substeps, void* stream) {
     if (!s || !(dt > 0.0) || substeps < 1) return BROV_ERR_ARG;
+    if (int rc = wrench_tick_ok(s, s->wr_tick, "brov_plant_step")) return rc;
     HIPCHK(hipSetDevice(s->device));
     if (int rc = order_behind_last(s, (hipStream_t)stream)) return rc;
     ensure_plant_params(s, (hipStream_t)stream);
-    launch_plant(s->x0, s->res, s->pplant, plant_rp(s), plant_rp_stride(s), s->B, dt, substeps, nullptr, nullptr, (hipStream_t)stream);
+    plant_step_on(s, dt, substeps, nullptr, nullptr, nullptr, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return BROV_OK;
 }
@@ -761,49 +846,88 @@ extern "C" int brov_get_x0_host(brov_solver* s, double* x0) {
 static DevParams make_params(const brov_solver* s);
 static int ticks_kernel(const brov_solver* s);
 static void launch_ticks(brov_solver* s, DevParams& P, hipStream_t st, int which);
+// Device-side logs of the closed loops (brov_closed_loop_ex, brov_closed_loop_dob): a buffer per HOST log the caller asked for, the start
+// state and the zeroed wrench log enqueued on the loop's stream, everything copied back after the loop's one host wait.  Logs come back
+// only from a loop that completed: a failing call leaves the caller's arrays as they were.
+struct LoopLogs {
+    size_t B = 0, ticks = 0;
+    double *hx = nullptr, *hu = nullptr, *hw = nullptr, *he = nullptr;   // HOST
+    int32_t* hst = nullptr;
+    double *dx = nullptr, *du = nullptr, *dw = nullptr, *de = nullptr;   // DEVICE
+    int* dst = nullptr;
+    double* x(int k) const { return dx ? dx + (size_t)k * B * 12 : nullptr; }   // x(0): before the first tick
+    double* u(int k) const { return du ? du + (size_t)k * B * 4 : nullptr; }
+    double* w(int k) const { return dw ? dw + (size_t)k * B * 6 : nullptr; }
+    double* est(int k) const { return de ? de + (size_t)k * B * 6 : nullptr; }
+    int* status(int k) const { return dst ? dst + (size_t)k * B : nullptr; }
+    int begin(const brov_solver* s, int ticks_, double* u_log, double* x_log, int32_t* st_log, double* w_log, double* est_log, hipStream_t st,
+              const char* who) {
+        B = s->B; ticks = ticks_; hx = x_log; hu = u_log; hst = st_log; hw = w_log; he = est_log;
+        hipError_t e = hipSuccess;
+        if (hx && e == hipSuccess) e = hipMalloc((void**)&dx, (ticks + 1) * B * 12 * sizeof(double));
+        if (hu && e == hipSuccess) e = hipMalloc((void**)&du, ticks * B * 4 * sizeof(double));
+        if (hst && e == hipSuccess) e = hipMalloc((void**)&dst, ticks * B * sizeof(int));
+        if (hw && e == hipSuccess) e = hipMalloc((void**)&dw, ticks * B * 6 * sizeof(double));
+        if (he && e == hipSuccess) e = hipMalloc((void**)&de, ticks * B * 6 * sizeof(double));
+        if (e != hipSuccess) { g_err = std::string(who) + ": hipMalloc: " + hipGetErrorString(e); return BROV_ERR_ALLOC; }
+        if (dw) e = hipMemsetAsync(dw, 0, ticks * B * 6 * sizeof(double), st);   // (mode OFF: no wrench, nothing writes it)
+        if (dx && e == hipSuccess) e = hipMemcpyAsync(dx, s->x0, B * 12 * sizeof(double), hipMemcpyDeviceToDevice, st);
+        if (e != hipSuccess) { g_err = std::string(who) + ": log initialisation failed"; return BROV_ERR_HIP; }
+        return BROV_OK;
+    }
+    // after the host wait: copies back when the loop succeeded, frees in any case; returns rc
+    int end(int rc) {
+        if (rc == BROV_OK) {
+            if (dx) hipMemcpy(hx, dx, (ticks + 1) * B * 12 * sizeof(double), hipMemcpyDeviceToHost);
+            if (du) hipMemcpy(hu, du, ticks * B * 4 * sizeof(double), hipMemcpyDeviceToHost);
+            if (dst) hipMemcpy(hst, dst, ticks * B * sizeof(int), hipMemcpyDeviceToHost);
+            if (dw) hipMemcpy(hw, dw, ticks * B * 6 * sizeof(double), hipMemcpyDeviceToHost);
+            if (de) hipMemcpy(he, de, ticks * B * 6 * sizeof(double), hipMemcpyDeviceToHost);
+        }
+        for (void* q : {(void*)dx, (void*)du, (void*)dst, (void*)dw, (void*)de})
+            if (q) hipFree(q);
+        return rc;
+    }
+};
 extern "C" int brov_closed_loop(brov_solver* s, int ticks, int line0, int ncols, double dt, int substeps, double* u_log, double* x_log,
                                 int32_t* st_log) {
+    return brov_closed_loop_ex(s, ticks, line0, ncols, dt, substeps, u_log, x_log, st_log, nullptr);
+}
+extern "C" int brov_closed_loop_ex(brov_solver* s, int ticks, int line0, int ncols, double dt, int substeps, double* u_log, double* x_log,
+                                   int32_t* st_log, double* w_log) {
     if (!s || ticks < 1 || !s->traj || (ncols != 12 && ncols != 16) || !(dt > 0.0) || substeps < 1) {
         g_err = "brov_closed_loop: bad argument (needs a trajectory table, see brov_traj_set_host)";
         return BROV_ERR_ARG;
     }
+    if (int wrc = wrench_tick_ok(s, s->wr_tick + ticks - 1, "brov_closed_loop")) return wrc;
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = s->last_stream;
     const size_t B = s->B;
-    double *dx = nullptr, *du = nullptr;
-    int* dst = nullptr;
-    int rc = BROV_OK;
-    auto alloc = [&](void** p, size_t bytes) {
-        if (rc != BROV_OK) return;
-        const hipError_t e = hipMalloc(p, bytes);
-        if (e != hipSuccess) { g_err = std::string("brov_closed_loop: hipMalloc: ") + hipGetErrorString(e); rc = BROV_ERR_ALLOC; }
-    };
-    if (x_log) alloc((void**)&dx, (size_t)(ticks + 1) * B * 12 * sizeof(double));
-    if (u_log) alloc((void**)&du, (size_t)ticks * B * 4 * sizeof(double));
-    if (st_log) alloc((void**)&dst, (size_t)ticks * B * sizeof(int));
-    if (rc == BROV_OK) ensure_plant_params(s, st);
-    if (rc == BROV_OK && dx && hipMemcpyAsync(dx, s->x0, B * 12 * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess) {
-        g_err = "brov_closed_loop: log copy failed";
-        rc = BROV_ERR_HIP;
-    }
+    ensure_plant_params(s, st);
+    LoopLogs L;
+    int rc = L.begin(s, ticks, u_log, x_log, st_log, w_log, nullptr, st, "brov_closed_loop");
     // One launch for the whole loop where the fused kernels serve the solver and every window is rows of the table in place (round 5,
     // rti_fused_kernel_ticks with the plant update behind every step): every instance runs its own closed loop at its own pace -- no launch
     // boundaries, three launches per tick saved, and a tick on which one instance grinds through the QP loop holds nobody else.
     const int which = ticks_kernel(s);
-    const bool one_launch = rc == BROV_OK && s->k.closed_loop_fused && ncols == 16 && line0 >= 0 && line0 + (ticks - 1) + s->N <= s->traj_rows - 1 && which != 0;
+    // (The fused and windowed *_ticks kernels integrate the plant themselves and know no wrench: with a wrench mode in force the loop takes
+    // a launch per step.)
+    const bool one_launch = rc == BROV_OK && s->k.closed_loop_fused && ncols == 16 && line0 >= 0 && line0 + (ticks - 1) + s->N <= s->traj_rows - 1 && which != 0 &&
+                            s->wr.mode == BROV_WRENCH_OFF;
     if (one_launch) {
         rc = brov_set_yref_from_traj(s, line0, 16, st);
         if (rc == BROV_OK) rc = order_behind_last(s, st);
         if (rc == BROV_OK) {
             DevParams P = make_params(s);
             P.sched = nullptr;
-            P.ticks = ticks; P.tick_yref = 16; P.tick_status = dst;
+            P.ticks = ticks; P.tick_yref = 16; P.tick_status = L.status(0);
             P.plant_pp = s->pplant; P.plant_rp = plant_rp(s); P.plant_rp_stride = plant_rp_stride(s); P.plant_substeps = substeps; P.plant_dt = dt;
-            P.x0_rw = s->x0; P.plant_xlog = dx ? dx + B * 12 : nullptr; P.plant_ulog = du;
+            P.x0_rw = s->x0; P.plant_xlog = L.x(1); P.plant_ulog = L.u(0);
             if (s->timing) { hipEventRecord(s->ev[0], st); hipEventRecord(s->ev[1], st); }   // (as brov_solve_ticks: brov_last_solve_seconds then reports THIS launch)
             launch_ticks(s, P, st, which);
             if (s->timing) { hipEventRecord(s->ev[2], st); s->ev_valid = true; }
             s->traj_line = line0 + ticks - 1; s->yref_view = s->traj + (size_t)s->traj_line * 16;
+            s->wr_tick += ticks;
         }
     }
     for (int k = 0; k < ticks && rc == BROV_OK && !one_launch; k++) {
@@ -811,19 +935,50 @@ extern "C" int brov_closed_loop(brov_solver* s, int ticks, int line0, int ncols,
         launch_window(s->traj, s->traj_rows, nullptr, line0 + k, 1, s->N, ncols, s->yref_sh, st);
         s->yref_shared = true;
         rc = brov_solve_phase(s, st, 0);
-        if (dst) hipLaunchKernelGGL(gather_status_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, s->res, dst + (size_t)k * B, (int)B);
-        launch_plant(s->x0, s->res, s->pplant, plant_rp(s), plant_rp_stride(s), s->B, dt, substeps, dx ? dx + (size_t)(k + 1) * B * 12 : nullptr,
-                     du ? du + (size_t)k * B * 4 : nullptr, st);
+        if (L.status(k)) hipLaunchKernelGGL(gather_status_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, s->res, L.status(k), (int)B);
+        plant_step_on(s, dt, substeps, L.x(k + 1), L.u(k), L.w(k), st);
     }
     hipError_t e = hipStreamSynchronize(st);
     if (rc == BROV_OK && e != hipSuccess) { g_err = hipGetErrorString(e); rc = BROV_ERR_HIP; }
-    if (rc == BROV_OK && dx) hipMemcpy(x_log, dx, (size_t)(ticks + 1) * B * 12 * sizeof(double), hipMemcpyDeviceToHost);
-    if (rc == BROV_OK && du) hipMemcpy(u_log, du, (size_t)ticks * B * 4 * sizeof(double), hipMemcpyDeviceToHost);
-    if (rc == BROV_OK && dst) hipMemcpy(st_log, dst, (size_t)ticks * B * sizeof(int), hipMemcpyDeviceToHost);
-    if (dx) hipFree(dx);
-    if (du) hipFree(du);
-    if (dst) hipFree(dst);
-    return rc;
+    return L.end(rc);
+}
+
+// The DOB / AMPC loop on the device: per tick the five public calls of the header, on one stream, one host wait at the end.
+extern "C" int brov_closed_loop_dob(brov_solver* s, brov_ekf* e, brov_rls* r, int rls_mode, int ticks, int line0, int ncols, double dt, int substeps,
+                                    double* u_log, double* x_log, int32_t* st_log, double* w_log, double* est_log) {
+    if (!s || !e || ticks < 1 || !s->traj || (ncols != 12 && ncols != 16) || !(dt > 0.0) || substeps < 1) {
+        g_err = "brov_closed_loop_dob: bad argument (needs an observer and a trajectory table, see brov_traj_set_host)";
+        return BROV_ERR_ARG;
+    }
+    if (brov_ekf_batch(e) != s->B || (r && brov_rls_batch(r) != s->B)) { g_err = "brov_closed_loop_dob: batch sizes differ"; return BROV_ERR_ARG; }
+    if (r && rls_mode != BROV_RLS_APPLY_DISTURBANCE && rls_mode != BROV_RLS_APPLY_MODEL) { g_err = "brov_closed_loop_dob: unknown rls_mode"; return BROV_ERR_ARG; }
+    if (int wrc = wrench_tick_ok(s, s->wr_tick + ticks - 1, "brov_closed_loop_dob")) return wrc;
+    HIPCHK(hipSetDevice(s->device));
+    hipStream_t st = s->last_stream;
+    const size_t B = s->B;
+    LoopLogs L;
+    int rc = L.begin(s, ticks, u_log, x_log, st_log, w_log, est_log, st, "brov_closed_loop_dob");
+    // the observer's and the estimator's calls report through their own error strings: their code is handed on, their text copied
+    auto sub = [&](int code, const char* text) {
+        if (code != BROV_OK) { g_err = std::string("brov_closed_loop_dob: ") + text; rc = code; }
+        return code == BROV_OK;
+    };
+    for (int k = 0; k < ticks && rc == BROV_OK; k++) {
+        rc = brov_set_yref_from_traj(s, line0 + k, ncols, st);
+        if (rc == BROV_OK) rc = brov_solve_phase(s, st, 0);
+        if (rc != BROV_OK) break;
+        if (L.status(k)) hipLaunchKernelGGL(gather_status_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, s->res, L.status(k), (int)B);
+        ensure_plant_params(s, st);   // (the hand-off below rewrites the controller's stage 0, which a plant without parameters of its own follows)
+        plant_step_on(s, dt, substeps, L.x(k + 1), L.u(k), L.w(k), st);
+        if (!sub(brov_ekf_update_from_solver(e, s, st), brov_ekf_last_error())) break;
+        if (L.est(k)) launch_gather_cols(brov_ekf_x_device(e), (int)B, 18, 12, 6, L.est(k), st);
+        if (!r) sub(brov_ekf_apply_to_solver(e, s, st), brov_ekf_last_error());
+        else if (sub(brov_rls_update_from_ekf(r, e, s, st), brov_rls_last_error())) sub(brov_rls_apply_to_solver(r, s, rls_mode, st), brov_rls_last_error());
+    }
+    hipError_t err = hipStreamSynchronize(st);
+    if (rc == BROV_OK && err == hipSuccess) err = hipGetLastError();
+    if (rc == BROV_OK && err != hipSuccess) { g_err = hipGetErrorString(err); rc = BROV_ERR_HIP; }
+    return L.end(rc);
 }
 
 extern "C" int brov_set_iterate_host(brov_solver* s, const double* x, const double* u, const double* pi, const double* lam) {

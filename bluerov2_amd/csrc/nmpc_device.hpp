@@ -127,4 +127,20 @@ void launch_plant(double* x0, const brov_result* res, const double* pplant, cons
 void launch_candidates(int kind, const double* p0, const double* p1, const double* phase, double t0, double dt, int B, int N,
                        double* out, hipStream_t st);
 
+// time-varying world-frame wrench of the plant (plant_wrench.hip; include/bluerov2_nmpc.h, brov_plant_wrench_*): the generator's data.
+// A pure function of (this record, instance, tick): nothing of it lives on the device between two launches.
+struct WrenchGen {
+    int mode = 0;                    // BROV_WRENCH_*
+    int rows = 0;                    // table mode
+    const double* w = nullptr;       // constant mode: [B][6]
+    const double* tab = nullptr;     // table mode: [rows][6], shared by the batch
+    const double* gain = nullptr;    // table mode: [B] or nullptr
+    unsigned long long seed = 0;     // periodic mode
+    double scale = 6.0, phase0 = 0.0, dphi = 0.125, tz_div = 3.0;
+};
+void launch_plant_wrench(double* x0, const brov_result* res, const double* pplant, const double* prp, int rp_stride, int B, double dt, int substeps,
+                         double* xlog, double* ulog, const WrenchGen& g, long long tick, double* wlog /*[B][6] or nullptr*/, hipStream_t st);
+void launch_wrench_eval(const WrenchGen& g, int B, long long tick, double* out /*[B][6]*/, hipStream_t st);
+void launch_gather_cols(const double* src, int B, int src_stride, int col0, int ncols, double* dst /*[B][ncols]*/, hipStream_t st);
+
 }  // namespace brov

@@ -1,0 +1,141 @@
+// plant_wrench.hip -- the device plant under a time-varying WORLD-frame wrench: the disturbance scenarios of the reference's
+// applyBodyWrench() (bluerov2_dobmpc/src/bluerov2_dob.cpp:754-892; bluerov2_ampc.cpp:1050-1150 is the same code with a
+// slower phase rate), which the constant body-frame parameters p[0..3] of plant_kernel (traj_kernel.hip) cannot pose:
+//   constant   (10, 10, 10, 0) N / Nm in the world frame (:813-816)
+//   periodic   sin(t) times amplitudes redrawn every half period (:776-795), the yaw torque from the Y amplitude (:787)
+//   table      recorded force / torque rows, one per tick (:869-873)
+// The wrench of instance b at tick k is a pure function of (generator data, b, k): no generator state lives on the device, any tick can be
+// evaluated again (brov_plant_wrench_eval_host).  The arithmetic of the generator is written with explicitly rounded operations under
+// `fp contract(off)` (hipcc otherwise contracts a product and a sum into an FMA, also across inlined calls): the evaluation kernel, the plant kernel and the numpy restatement of tests/wrench_restatement.py then agree bit for bit
+// except through sin().
+// plant_wrench_kernel: one lane per instance, FP64, no scratch; the ERK4 of plant_kernel with the world wrench projected into the body
+// frame at EVERY stage with that stage's attitude (bluerov2_model.hpp, the model_f overload).  ~660 FP64 ops, 240 B + 48 B in, 96 B (+ logs)
+// out per instance.
+#include <hip/hip_runtime.h>
+
+#include "nmpc_device.hpp"
+#include "bluerov2_model.hpp"
+
+namespace brov {
+
+// the output function of SplitMix64 (Steele, Lea, Flood 2014; public domain reference implementation by S. Vigna)
+__device__ __forceinline__ unsigned long long splitmix64_finalise(unsigned long long z) {
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    return z ^ (z >> 31);
+}
+
+// amplitude of channel c (X = 0, Y = 1, Z = 2, N = 3) of instance b in half period j: scale * uniform[0.5, 1), counter-based
+__device__ __forceinline__ double wrench_amplitude(const WrenchGen& g, int b, long long j, int c) {
+#pragma clang fp contract(off)
+    const unsigned long long n = ((unsigned long long)b << 24) | ((unsigned long long)(j & 0x3FFFFF) << 2) | (unsigned long long)c;
+    const unsigned long long z = splitmix64_finalise(g.seed + (n + 1ULL) * 0x9E3779B97F4A7C15ULL);
+    const double U = (double)(z >> 11) * 0x1.0p-53;   // exact: 53 bits
+    return __dmul_rn(g.scale, __dadd_rn(0.5, __dmul_rn(0.5, U)));
+}
+
+__device__ __forceinline__ void wrench_at(const WrenchGen& g, int b, long long k, double (&w)[6]) {
+#pragma clang fp contract(off)
+    if (g.mode == BROV_WRENCH_CONSTANT) {
+#pragma unroll
+        for (int c = 0; c < 6; c++) w[c] = g.w[(size_t)b * 6 + c];
+    } else if (g.mode == BROV_WRENCH_TABLE) {
+        long long r = k < 0 ? 0 : k;
+        if (r > g.rows - 1) r = g.rows - 1;   // past the end: the last row, repeated (the reference indexes past the end)
+        const double gn = g.gain ? g.gain[b] : 1.0;
+#pragma unroll
+        for (int c = 0; c < 6; c++) w[c] = __dmul_rn(g.tab[(size_t)r * 6 + c], gn);
+    } else if (g.mode == BROV_WRENCH_PERIODIC) {
+        const double t = __dadd_rn(g.phase0, __dmul_rn((double)k, g.dphi));   // a product, not the reference's running sum
+        const long long j = (long long)floor(__ddiv_rn(t, 3.14159265358979323846));
+        const double ax = wrench_amplitude(g, b, j, 0), ay = wrench_amplitude(g, b, j, 1), az = wrench_amplitude(g, b, j, 2);
+        // (channel 3, the N amplitude, is drawn by the reference and never used: its counter value stays reserved)
+        const double sn = sin(t);
+        w[0] = __dmul_rn(sn, ax); w[1] = __dmul_rn(sn, ay); w[2] = __dmul_rn(sn, az);
+        w[3] = 0.0; w[4] = 0.0;
+        w[5] = __ddiv_rn(w[1], g.tz_div);   // the yaw torque follows the Y amplitude (:787)
+    } else {
+#pragma unroll
+        for (int c = 0; c < 6; c++) w[c] = 0.0;
+    }
+}
+
+__global__ __launch_bounds__(128) void wrench_eval_kernel(WrenchGen g, int B, long long tick, double* __restrict__ out) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double w[6];
+    wrench_at(g, b, tick, w);
+#pragma unroll
+    for (int c = 0; c < 6; c++) out[(size_t)b * 6 + c] = w[c];
+}
+
+__global__ __launch_bounds__(128) void plant_wrench_kernel(double* __restrict__ x0, const brov_result* __restrict__ res,
+                                                           const double* __restrict__ pplant, const double* __restrict__ prp, int rp_stride, int B,
+                                                           double dt, int substeps, double* __restrict__ xlog, double* __restrict__ ulog,
+                                                           WrenchGen g, long long tick, double* __restrict__ wlog) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double x[NX], u[NU], k[NX], xs[NX], acc[NX], wv[6];
+#pragma unroll
+    for (int j = 0; j < NX; j++) x[j] = x0[(size_t)b * NX + j];
+#pragma unroll
+    for (int j = 0; j < NU; j++) u[j] = res[b].u0[j];
+    const ModelPar m = make_par(pplant + (size_t)b * NP);
+    Wrench w = make_wrench(u);
+    if (prp) { w.k3 = prp[(size_t)b * rp_stride]; w.k4 = prp[(size_t)b * rp_stride + 1]; }   // 6-disturbance variant
+    wrench_at(g, b, tick, wv);
+    const WorldWrench ww = {wv[0], wv[1], wv[2], wv[3], wv[4], wv[5]};   // held over the tick, like the reference's service call
+    const double h = dt / substeps;
+    StagePoint sp;
+    for (int s = 0; s < substeps; s++) {
+        model_f(x, w, m, ww, k, sp);
+#pragma unroll
+        for (int j = 0; j < NX; j++) { acc[j] = x[j] + (h / 6.0) * k[j]; xs[j] = x[j] + 0.5 * h * k[j]; }
+        model_f(xs, w, m, ww, k, sp);
+#pragma unroll
+        for (int j = 0; j < NX; j++) { acc[j] += (h / 3.0) * k[j]; xs[j] = x[j] + 0.5 * h * k[j]; }
+        model_f(xs, w, m, ww, k, sp);
+#pragma unroll
+        for (int j = 0; j < NX; j++) { acc[j] += (h / 3.0) * k[j]; xs[j] = x[j] + h * k[j]; }
+        model_f(xs, w, m, ww, k, sp);
+#pragma unroll
+        for (int j = 0; j < NX; j++) x[j] = acc[j] + (h / 6.0) * k[j];
+    }
+#pragma unroll
+    for (int j = 0; j < NX; j++) x0[(size_t)b * NX + j] = x[j];
+    if (xlog) {
+#pragma unroll
+        for (int j = 0; j < NX; j++) xlog[(size_t)b * NX + j] = x[j];
+    }
+    if (ulog) {
+#pragma unroll
+        for (int j = 0; j < NU; j++) ulog[(size_t)b * NU + j] = u[j];
+    }
+    if (wlog) {
+#pragma unroll
+        for (int c = 0; c < 6; c++) wlog[(size_t)b * 6 + c] = wv[c];
+    }
+}
+
+// dst[b][c] = src[b * src_stride + col0 + c]: the disturbance estimate out of the observer's state for brov_closed_loop_dob's log
+__global__ void gather_cols_kernel(const double* __restrict__ src, int B, int src_stride, int col0, int ncols, double* __restrict__ dst) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= B * ncols) return;
+    const int b = t / ncols, c = t - b * ncols;
+    dst[t] = src[(size_t)b * src_stride + col0 + c];
+}
+
+void launch_plant_wrench(double* x0, const brov_result* res, const double* pplant, const double* prp, int rp_stride, int B, double dt, int substeps,
+                         double* xlog, double* ulog, const WrenchGen& g, long long tick, double* wlog, hipStream_t st) {
+    hipLaunchKernelGGL(plant_wrench_kernel, dim3((B + 127) / 128), dim3(128), 0, st, x0, res, pplant, prp, rp_stride, B, dt, substeps, xlog, ulog,
+                       g, tick, wlog);
+}
+void launch_wrench_eval(const WrenchGen& g, int B, long long tick, double* out, hipStream_t st) {
+    hipLaunchKernelGGL(wrench_eval_kernel, dim3((B + 127) / 128), dim3(128), 0, st, g, B, tick, out);
+}
+void launch_gather_cols(const double* src, int B, int src_stride, int col0, int ncols, double* dst, hipStream_t st) {
+    const int tot = B * ncols;
+    hipLaunchKernelGGL(gather_cols_kernel, dim3((tot + 255) / 256), dim3(256), 0, st, src, B, src_stride, col0, ncols, dst);
+}
+
+}  // namespace brov

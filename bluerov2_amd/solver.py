@@ -20,6 +20,7 @@ NX, NU, NP, NY = 12, 4, 16, 16
 MAX_N = 256      # BROV_MAX_N (streaming pair)
 MAX_N_LDS = 128  # BROV_MAX_N_LDS (LDS-resident kernels)
 PATH_AUTO, PATH_STREAMING, PATH_FUSED, PATH_WINDOWED = 0, 1, 2, 3
+WRENCH_OFF, WRENCH_CONSTANT, WRENCH_PERIODIC, WRENCH_TABLE = 0, 1, 2, 3   # BROV_WRENCH_*
 
 # nominal hydrodynamic parameters the nodes pass every tick (bluerov2_dob.cpp:340-353); p[0:4] = disturbance
 P_NOMINAL = np.array([0, 0, 0, 0, 1.7182, 0, 5.468, 0.4006, -11.7391, -20, -31.8678, -5, -18.18, -21.66, -36.99, -1.55])
@@ -106,10 +107,17 @@ def _load():
         "brov_set_time_steps": [vp, dp], "brov_set_stage0_weight": [vp, dp], "brov_general_grid": [vp],
         "brov_enable_dist6": [vp, C.c_int], "brov_dist6_enabled": [vp], "brov_set_rp_disturbance_host": [vp, dp, C.c_int],
         "brov_set_params18_host": [vp, dp, C.c_int], "brov_plant_set_rp_disturbance_host": [vp, dp], "brov_get_rp_disturbance_host": [vp, dp],
+        "brov_plant_wrench_constant_host": [vp, dp], "brov_plant_wrench_periodic": [vp, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_double],
+        "brov_plant_wrench_table_host": [vp, dp, C.c_int, dp], "brov_plant_wrench_off": [vp], "brov_plant_wrench_mode": [vp],
+        "brov_plant_wrench_seek": [vp, C.c_int64], "brov_plant_wrench_eval_host": [vp, C.c_int64, dp],
+        "brov_closed_loop_ex": [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, dp, dp, C.POINTER(C.c_int32), dp],
+        "brov_closed_loop_dob": [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, dp, dp, C.POINTER(C.c_int32), dp, dp],
     }.items():
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = C.c_int
+    L.brov_plant_wrench_tick.argtypes = [vp]
+    L.brov_plant_wrench_tick.restype = C.c_int64
     for name in ("brov_results_device", "brov_x0_device", "brov_yref_device", "brov_params_device", "brov_x_device",
                  "brov_u_device"):
         fn = getattr(L, name)
@@ -381,17 +389,88 @@ class BatchSolver:
         self._chk(self._L.brov_get_x0_host(self._h, _dp(x0)), "get_x0")
         return x0
 
-    def closed_loop(self, ticks, line0=0, ncols=16, dt=0.05, substeps=1, log=True):
-        """ticks x (window -> RTI step -> plant step) on the device; returns (u_log, x_log, status_log) or None"""
-        if not log:
+    def closed_loop(self, ticks, line0=0, ncols=16, dt=0.05, substeps=1, log=True, log_wrench=False):
+        """ticks x (window -> RTI step -> plant step) on the device; returns (u_log, x_log, status_log) or None; with log_wrench also the
+        applied world-frame wrench of every tick, (u_log, x_log, status_log, w_log [ticks, B, 6])"""
+        if not log and not log_wrench:
             self._chk(self._L.brov_closed_loop(self._h, int(ticks), int(line0), int(ncols), float(dt), int(substeps), None, None, None),
                       "closed_loop")
             return None
         ul, xl = np.empty((ticks, self.B, NU)), np.empty((ticks + 1, self.B, NX))
         sl = np.empty((ticks, self.B), dtype=np.int32)
-        self._chk(self._L.brov_closed_loop(self._h, int(ticks), int(line0), int(ncols), float(dt), int(substeps), _dp(ul), _dp(xl),
-                                           sl.ctypes.data_as(C.POINTER(C.c_int32))), "closed_loop")
-        return ul, xl, sl
+        if not log_wrench:
+            self._chk(self._L.brov_closed_loop(self._h, int(ticks), int(line0), int(ncols), float(dt), int(substeps), _dp(ul), _dp(xl),
+                                               sl.ctypes.data_as(C.POINTER(C.c_int32))), "closed_loop")
+            return ul, xl, sl
+        wl = np.empty((ticks, self.B, 6))
+        self._chk(self._L.brov_closed_loop_ex(self._h, int(ticks), int(line0), int(ncols), float(dt), int(substeps), _dp(ul), _dp(xl),
+                                              sl.ctypes.data_as(C.POINTER(C.c_int32)), _dp(wl)), "closed_loop_ex")
+        return ul, xl, sl, wl
+
+    def closed_loop_dob(self, ekf, rls=None, rls_mode=0, ticks=1, line0=0, ncols=16, dt=0.05, substeps=1, log=True):
+        """the DOB (rls None) / AMPC control loop on the device (brov_closed_loop_dob): ticks x (window -> RTI step -> plant step under
+        the wrench in force -> EKF from the solver -> parameter hand-off), one host wait.  Returns dict(u, x, status, wrench, est) --
+        est [ticks, B, 6]: the observer's disturbance estimate after each tick -- or None"""
+        hr = rls._h if rls is not None else None
+        args = (self._h, ekf._h, hr, int(rls_mode), int(ticks), int(line0), int(ncols), float(dt), int(substeps))
+        if not log:
+            self._chk(self._L.brov_closed_loop_dob(*args, None, None, None, None, None), "closed_loop_dob")
+            return None
+        ul, xl = np.empty((ticks, self.B, NU)), np.empty((ticks + 1, self.B, NX))
+        sl = np.empty((ticks, self.B), dtype=np.int32)
+        wl, el = np.empty((ticks, self.B, 6)), np.empty((ticks, self.B, 6))
+        self._chk(self._L.brov_closed_loop_dob(*args, _dp(ul), _dp(xl), sl.ctypes.data_as(C.POINTER(C.c_int32)), _dp(wl), _dp(el)),
+                  "closed_loop_dob")
+        return dict(u=ul, x=xl, status=sl, wrench=wl, est=el)
+
+    # ---- time-varying world-frame wrench on the plant (bluerov2_dob.cpp:754-892, applyBodyWrench) ------------------------------
+    def set_plant_wrench(self, constant=None, periodic=None, table=None, gain=None):
+        """exactly one of
+            constant=w         [6] or [B, 6], world frame [fx fy fz tx ty tz]; the reference's mode 1 is (10, 10, 10, 0, 0, 0)
+            periodic=dict(seed=0, scale=6.0, phase0=0.0, dphi=0.125, tz_div=3.0)   (any subset; dphi = 0.025 is the AMPC node's)
+            table=tab          [rows, 6], row min(tick, rows - 1); gain=[B] scales it per instance"""
+        if (constant is not None) + (periodic is not None) + (table is not None) != 1:
+            raise ValueError("set_plant_wrench takes exactly one of constant=, periodic=, table=")
+        if gain is not None and table is None:
+            raise ValueError("gain= goes with table=")
+        if constant is not None:
+            w = np.ascontiguousarray(constant, dtype=np.float64)
+            if w.shape == (6,):
+                w = np.ascontiguousarray(np.broadcast_to(w, (self.B, 6)))
+            self._chk(self._L.brov_plant_wrench_constant_host(self._h, _dp(_arr(w, (self.B, 6)))), "plant_wrench_constant")
+        elif periodic is not None:
+            kw = dict(seed=0, scale=6.0, phase0=0.0, dphi=0.125, tz_div=3.0)
+            unknown = set(periodic) - set(kw)
+            if unknown:
+                raise ValueError(f"unknown periodic wrench parameters {sorted(unknown)}")
+            kw.update(periodic)
+            self._chk(self._L.brov_plant_wrench_periodic(self._h, int(kw["seed"]) & 0xFFFFFFFFFFFFFFFF, float(kw["scale"]), float(kw["phase0"]),
+                                                         float(kw["dphi"]), float(kw["tz_div"])), "plant_wrench_periodic")
+        else:
+            tab = np.ascontiguousarray(table, dtype=np.float64)
+            if tab.ndim != 2 or tab.shape[1] != 6 or tab.shape[0] < 1:
+                raise ValueError("wrench table must be [rows][6]")
+            g = None if gain is None else _arr(gain, (self.B,))
+            self._chk(self._L.brov_plant_wrench_table_host(self._h, _dp(tab), tab.shape[0], None if g is None else _dp(g)), "plant_wrench_table")
+
+    def plant_wrench_off(self):
+        self._chk(self._L.brov_plant_wrench_off(self._h), "plant_wrench_off")
+
+    def plant_wrench_mode(self):
+        return int(self._L.brov_plant_wrench_mode(self._h))
+
+    def plant_wrench(self, tick):
+        """[B, 6]: the wrench of every instance at `tick`, evaluated by the device generator (moves nothing)"""
+        w = np.empty((self.B, 6))
+        self._chk(self._L.brov_plant_wrench_eval_host(self._h, int(tick), _dp(w)), "plant_wrench_eval")
+        return w
+
+    def plant_wrench_seek(self, tick):
+        self._chk(self._L.brov_plant_wrench_seek(self._h, int(tick)), "plant_wrench_seek")
+
+    def plant_wrench_tick(self):
+        """the tick counter: plant steps so far (plant_step and every closed-loop tick add one)"""
+        return int(self._L.brov_plant_wrench_tick(self._h))
 
     # ---- iterate ----------------------------------------------------------------------------------------------
     def set_iterate(self, x=None, u=None, pi=None, lam=None):

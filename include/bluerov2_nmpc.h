@@ -173,6 +173,48 @@ int brov_closed_loop(brov_solver* s, int ticks, int line0, int ncols, double dt,
                      int32_t* st_log);
 int brov_get_x0_host(brov_solver* s, double* x0 /*[B][12]*/);
 
+/* ---- time-varying WORLD-frame wrench on the plant: the disturbance scenarios of the reference's applyBodyWrench()
+ * (bluerov2_dobmpc/src/bluerov2_dob.cpp:754-892; bluerov2_ampc.cpp:1050-1150 is the same code with a slower phase rate).  The plant
+ * parameters above pose a disturbance that is constant in the BODY frame; the reference applies its wrench in the world frame (:879), so
+ * that its body-frame image turns with the vehicle -- the case the disturbance observer exists for.  Per instance, [fx fy fz tx ty tz],
+ * a pure function of (mode data, instance b, tick k): no generator state lives on the device, any tick can be evaluated again.
+ *   BROV_WRENCH_OFF       (default) brov_plant_step launches the plant kernel it always launched: bit-identical to a solver that never
+ *                         touched this API
+ *   BROV_WRENCH_CONSTANT  w[B][6]; the reference's mode 1 is (10, 10, 10, 0, 0, 0) (:813-816)
+ *   BROV_WRENCH_PERIODIC  (:776-795)  t_k = phase0 + k * dphi -- a PRODUCT, evaluated afresh for every tick; the reference accumulates
+ *                         dis_time += dt * 2.5, a running sum whose rounding depends on its history --, dphi = 0.125 in the DOB node (dt * 2.5),
+ *                         0.025 in the AMPC node;  j = floor(t_k / pi), which must stay below 2^22;  amplitude of channel c in {X = 0, Y = 1,
+ *                         Z = 2, N = 3}: A_c = scale * (0.5 + 0.5 U), U = (z >> 11) * 2^-53, z = splitmix64_finalise(seed + (n + 1) *
+ *                         0x9E3779B97F4A7C15), n = (b << 24) | (j << 2) | c -- redrawn every half period, in [scale / 2, scale) like the
+ *                         reference's uniform(0.5, 1) * 6;  wrench = sin(t_k) * (A_X, A_Y, A_Z, 0, 0, A_Y / tz_div): the yaw torque uses the Y
+ *                         amplitude as the reference does (:787; its N draw is made and never used).  Batches up to 2^24 instances draw
+ *                         independent amplitudes.
+ *   BROV_WRENCH_TABLE     (:869-873) a table [rows][6] resident in HBM and shared by the batch, row min(k, rows - 1) (the reference indexes
+ *                         past the end; this clamps, like the trajectory table), times an optional per-instance gain[B]
+ * With a mode in force the plant is plant_wrench_kernel: the same ERK4, the wrench held over the tick and projected into the body frame at
+ * EVERY stage with that stage's attitude (f_b = R^T f_w, t_b = R^T t_w), added to dx, dy, dz, the roll / pitch moments and dn ahead of the
+ * mass scaling.  The tick counter k counts plant steps: +1 in brov_plant_step and in every tick of brov_closed_loop / _ex / _dob, whatever
+ * the mode; brov_plant_wrench_seek sets it.  The one-launch closed loop and the *_ticks kernels know no wrench: brov_closed_loop with a mode
+ * in force takes its launch-per-tick branch. */
+#define BROV_WRENCH_OFF 0
+#define BROV_WRENCH_CONSTANT 1
+#define BROV_WRENCH_PERIODIC 2
+#define BROV_WRENCH_TABLE 3
+int brov_plant_wrench_constant_host(brov_solver* s, const double* w /*[B][6]*/);
+int brov_plant_wrench_periodic(brov_solver* s, uint64_t seed, double scale, double phase0, double dphi, double tz_div);
+int brov_plant_wrench_table_host(brov_solver* s, const double* tab /*[rows][6]*/, int rows, const double* gain /*[B] or NULL*/);
+int brov_plant_wrench_off(brov_solver* s);
+int brov_plant_wrench_mode(const brov_solver* s);
+int brov_plant_wrench_seek(brov_solver* s, int64_t tick);   /* tick >= 0 */
+int64_t brov_plant_wrench_tick(const brov_solver* s);
+/* the wrench of every instance at `tick`, from the device generator; moves neither the plant nor the tick counter (zeros while OFF) */
+int brov_plant_wrench_eval_host(brov_solver* s, int64_t tick, double* w /*[B][6]*/);
+/* brov_closed_loop with the applied wrench of every tick logged: w_log HOST [ticks][B][6] or NULL (zeros while OFF).  Like brov_closed_loop
+ * it delivers its logs only when the whole loop succeeded: a call that returns an error leaves the caller's log arrays untouched, also for
+ * the ticks that ran. */
+int brov_closed_loop_ex(brov_solver* s, int ticks, int line0, int ncols, double dt, int substeps, double* u_log, double* x_log,
+                        int32_t* st_log, double* w_log);
+
 /* iterate (warm start) access; any pointer may be NULL to skip that block */
 int brov_set_iterate_host(brov_solver* s, const double* x, const double* u, const double* pi, const double* lam);
 int brov_get_iterate_host(brov_solver* s, double* x, double* u, double* pi, double* lam);
@@ -488,6 +530,22 @@ int brov_rls_get_outputs_host(brov_rls* r, double* mpc_p /*[B][4]*/, double* wf_
 const double* brov_rls_theta_device(const brov_rls* r);   /* DEVICE theta, [4 components][B][4 axes] */
 /* seconds of the last update kernel (HIP events on its stream) */
 int brov_rls_last_update_seconds(brov_rls* r, double* seconds);
+
+/* ---- the DOB / AMPC control loop on the device: the counterpart of brov_closed_loop with the observer in the loop.  Per tick k it
+ * enqueues, on one stream (the solver's last one), exactly
+ *     brov_set_yref_from_traj(s, line0 + k, ncols)
+ *     brov_solve(s)
+ *     brov_plant_step(s, dt, substeps)                  under the wrench mode in force (brov_plant_wrench_*)
+ *     brov_ekf_update_from_solver(e, s)
+ *     r == NULL (the DOB node):   brov_ekf_apply_to_solver(e, s)
+ *     else (the AMPC node):       brov_rls_update_from_ekf(r, e, s);  brov_rls_apply_to_solver(r, s, rls_mode)      (bluerov2_ampc.cpp:346-349)
+ * and waits on the host ONCE, at the end.  The results are bit-identical to that call sequence.  Optional HOST logs: u_log [ticks][B][4],
+ * x_log [ticks+1][B][12], st_log [ticks][B], w_log [ticks][B][6] as brov_closed_loop_ex; est_log [ticks][B][6]: the observer's disturbance
+ * estimate x[12..17] after each tick.  The three objects must hold the same batch (BROV_ERR_ARG otherwise).  An error of one of the calls
+ * inside ends the loop and is returned with that call's own code (its text through brov_last_error); the logs are delivered only when the
+ * whole loop succeeded, and the tick counter and the objects' states then stand where the failing tick left them. */
+int brov_closed_loop_dob(brov_solver* s, brov_ekf* e, brov_rls* r /*NULL: DOB; else AMPC*/, int rls_mode, int ticks, int line0, int ncols,
+                         double dt, int substeps, double* u_log, double* x_log, int32_t* st_log, double* w_log, double* est_log);
 
 #ifdef __cplusplus
 }
