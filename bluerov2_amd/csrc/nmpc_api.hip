@@ -71,7 +71,8 @@ struct brov_solver {
     bool timing = false;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     bool ev_valid = false;
-    bool last_fused = false, last_windowed = false;
+    int last_family = 0;             // kernel family of the last solve (FAM_*)
+    int cus = 256;                   // compute units of the device, queried once in brov_create
     double* ws = nullptr;        // windowed kernel: per-block parking images
     int32_t* counter = nullptr;
     unsigned win_tick = 0;           // windowed launches so far: which of the two hand-out counters the next one uses
@@ -79,7 +80,6 @@ struct brov_solver {
     double* ws_split = nullptr;      // fused-kernel horizons, at most one instance per CU: per-instance workspace of the resident kernel's split launches (rti_phase 1 / 2)
     int alt_blocks = 0, alt_L = 0;   // parallel-in-time rounds (pit_rounds_stages): the resident configuration a solve may use instead
     int prep_path = 0;               // the last rti_phase-1 call: 1 streaming pair (linearisation in HBM), 2 resident split (factorised LDS image parked), 3 the latter, invalidated by a setter
-    bool force_windowed = false;
     unsigned long long* dbg = nullptr;
     // general grid (streaming kernels): per-stage time steps and / or a separate stage-0 weight
     std::vector<double> ts_host;     // N time steps, empty = uniform
@@ -89,7 +89,6 @@ struct brov_solver {
     double* wst = nullptr;           // device [N+1][16] scaled weights per stage
     int32_t* sched = nullptr;        // work ordering: 3 rotating buffers of 64 class counters | lists | pos[B] (qp_kernel.hip, sched_map)
     unsigned sched_tick = 0;
-    bool sched_on = true;
     hipStream_t tick_stream = nullptr;   // brov_tick_host: the solver's own stream and pinned staging buffer
     double* pin = nullptr;
     size_t pin_doubles = 0;
@@ -141,14 +140,19 @@ static DevKnobs read_knobs() {
     k.lds_pad = env_int("BROV_DEV_LDS_PAD", 0);
     k.closed_loop_fused = env_int("BROV_CLOSED_LOOP_FUSED", 1) != 0;   // 0: brov_closed_loop as three launches per tick (A/B, tests)
     k.tick_breakdown = env_int("BROV_TICK_BREAKDOWN", 0) != 0;
+    k.no_resident = env_int("BROV_DEV_NO_RESIDENT", 0) != 0;     // windows of <= 20 stages at every batch size (A/B, tests)
+    k.win_blocks = env_int("BROV_DEV_WIN_BLOCKS", 0);             // >= 1: at most this many persistent blocks of the windowed kernel (tests)
+    k.pit_rounds = env_int("BROV_PIT_ROUNDS", 1) != 0;            // 0: batches of one to two instances per CU stay on the windowed kernel
+    k.win_long = env_int("BROV_DEV_WIN_LONG", 0) != 0;            // the long-horizon windowed instantiations at every horizon (A/B)
     return k;
 }
 extern "C" int brov_dev_reload_knobs(brov_solver* s) {
     if (!s) return BROV_ERR_ARG;
-    const bool fw = s->force_windowed;
+    const DevKnobs at_create = s->k;
     s->k = read_knobs();
-    s->k.force_windowed = fw;        // (the workspaces were allocated for the create-time choice)
-    s->sched_on = s->k.sched != 0;
+    // the workspaces were allocated for the create-time values of the knobs that size them (plan_workspaces): those stay in force
+    s->k.force_windowed = at_create.force_windowed; s->k.no_resident = at_create.no_resident;
+    s->k.win_blocks = at_create.win_blocks; s->k.pit_rounds = at_create.pit_rounds;
     return BROV_OK;
 }
 
@@ -203,6 +207,15 @@ static int dalloc(brov_solver* s, T** p, size_t n) {
     return BROV_OK;
 }
 
+// a parked preparation (rti_phase 1 on the resident kernel's split launch) does not survive a call that changes what it factorised
+static void invalidate_preparation(brov_solver* s) { if (s && s->prep_path == 2) s->prep_path = 3; }
+// the shared window in force no longer names rows of the resident trajectory table
+static void forget_traj_window(brov_solver* s) { s->yref_view = nullptr; s->traj_line = -1; }
+// which LDS-resident kernels serve the solver's one-call step: the fused ones (whole horizon in an LDS slice, N <= 23) or the windowed ones
+static bool serves_fused(const brov_solver* s) { return fused_supported(s->N) && !s->k.force_windowed; }
+// ... and whether the windowed kernel runs in its large-batch configuration alone, the one that has a steps-per-launch variant
+static bool serves_windowed_ticks(const brov_solver* s) { return s->ws != nullptr && !windowed_is_resident(s->win_L) && s->alt_L == 0; }
+
 static bool general_grid(const brov_solver* s) { return !s->ts_host.empty() || s->has_W0; }
 // per-stage time steps and scaled weights of the general grid: wst[i] = ts_i * (i == 0 ? W_0 : W) for i < N, wst[N] = [We | 0]
 static int upload_grid(brov_solver* s) {
@@ -234,7 +247,7 @@ static int upload_cst(brov_solver* s) {
 }
 
 extern "C" int brov_init_iterate_default(brov_solver* s) {
-    if (s && s->prep_path == 2) s->prep_path = 3;   // a parked preparation (rti_phase 1, resident kernel) does not survive this call
+    invalidate_preparation(s);
     if (!s) return BROV_ERR_ARG;
     HIPCHK(hipSetDevice(s->device));
     const int B = s->B, N = s->N;
@@ -245,6 +258,42 @@ extern "C" int brov_init_iterate_default(brov_solver* s) {
     HIPCHK(hipMemset(s->pi, 0, (size_t)B * N * 12 * sizeof(double)));
     HIPCHK(hipMemset(s->lam, 0, (size_t)B * N * 8 * sizeof(double)));
     return BROV_OK;
+}
+
+// The workspaces of the LDS-resident kernels, decided at create from horizon, batch, CU count, path and the knobs that size them.
+//   N <= 23 (fused kernels; BROV_DEV_FORCE_WINDOWED=1: none): no workspace for the one-call step.  rti_phase 1 / 2 run on the resident kernel's
+//     split launches where its four waves all get a stage and the batch is at most one instance per CU: a workspace per instance (split).
+//   N >= 24: the windowed kernel at every batch size.  Its RESIDENT mode -- one window = the whole horizon, one block per CU -- where that window's
+//     LDS slice fits a CU's 160 KB, which is N <= 81, and the batch is at most one instance per CU; windows of <= 20 stages otherwise.  (Rounds 3-4
+//     sent up to eight instances at N > 81 to the streaming pair, then as fast; since round 5 the windowed kernel is ahead there too -- one instance
+//     at N = 82 / 128 / 160 / 256: 0.196 / 0.278 / 0.342 / 0.535 ms per step against 0.207 / 0.301 / 0.366 / 0.558, eight instances 0.198 / 0.281 /
+//     0.344 / 0.539 against 0.241 / 0.343 / 0.421 / 0.686: scripts/dev/long_horizon_small_batches.py.)
+//     The parallel-in-time kernel needs 244 doubles of the slice for itself and so serves the resident configuration up to N = 80.  Between one and
+//     two instances per CU at 48 <= N <= 80 (alt: pit_rounds_stages) a solve it can serve runs it with one block and one workspace per instance, the
+//     resident kernel behind it, instead of the windowed kernel: the workspace serves either.
+//   BROV_PATH_STREAMING: none of them.
+struct WorkspacePlan {
+    int win_L = 0, win_blocks = 0;   // windowed kernel: stages per window, persistent blocks
+    int alt_L = 0, alt_blocks = 0;   // ... the resident configuration a solve may take instead (0: none)
+    size_t ws_doubles = 0;           // ... the workspace that serves both
+    size_t split_doubles = 0;        // fused-kernel horizons: workspace of the resident split launches
+};
+static WorkspacePlan plan_workspaces(int N, int B, int cus, int kernel_path, const DevKnobs& k) {
+    WorkspacePlan w;
+    if (kernel_path == BROV_PATH_STREAMING) return w;
+    if (fused_supported(N) && !k.force_windowed) {
+        if (split_resident_horizon(N) && k.split_resident && B <= cus) w.split_doubles = (size_t)B * windowed_ws_doubles(N, N);
+        return w;
+    }
+    w.win_L = windowed_stage_count(N, B, cus, k);
+    w.win_blocks = windowed_blocks(B, w.win_L, cus, k);
+    w.ws_doubles = (size_t)w.win_blocks * windowed_ws_doubles(N, w.win_L);
+    if (!windowed_is_resident(w.win_L) && (w.alt_L = pit_rounds_stages(N, B, cus, k)) != 0) {   // one workspace per instance for rti_pit_kernel's blocks
+        w.alt_blocks = windowed_blocks(B, w.alt_L, cus, k);
+        const size_t alt = (size_t)B * windowed_ws_doubles(N, w.alt_L);
+        w.ws_doubles = alt > w.ws_doubles ? alt : w.ws_doubles;
+    }
+    return w;
 }
 
 extern "C" int brov_create(brov_solver** out, int device, int B, const brov_opts* opts) {
@@ -304,35 +353,13 @@ extern "C" int brov_create(brov_solver** out, int device, int B, const brov_opts
     AL(counter, 64);   // two hand-out counters of the windowed kernel, 128 bytes apart, used alternately
     AL(pit_done, Bz);   // rti_pit_kernel's per-instance verdict
     AL(sched, 3 * (size_t)sched_buffer_ints_host(B));
-    // development knob: BROV_DEV_FORCE_WINDOWED=1 runs the windowed kernel for every horizon (one window when N <= 20)
     s->k = read_knobs();
-    s->force_windowed = s->k.force_windowed != 0;
-    // BROV_PATH_AUTO beyond the horizons the fused kernels serve: the windowed kernel at every batch size -- its resident mode where the whole horizon
-    // fits one window (N <= 81, at most one instance per CU), windows of <= 20 stages otherwise.  (Rounds 3-4 sent up to eight instances at N > 81 to
-    // the streaming pair, then as fast; since round 5 the windowed kernel is ahead there too -- one instance at N = 82 / 128 / 160 / 256: 0.196 / 0.278 /
-    // 0.342 / 0.535 ms per step against 0.207 / 0.301 / 0.366 / 0.558, eight instances 0.198 / 0.281 / 0.344 / 0.539 against 0.241 / 0.343 / 0.421 /
-    // 0.686: scripts/dev/long_horizon_small_batches.py.)
-    if ((!fused_supported(opts->N) || s->force_windowed) && opts->kernel_path != BROV_PATH_STREAMING) {
-        s->win_L = windowed_stage_count(opts->N, B);
-        s->win_blocks = windowed_blocks(opts->N, B, s->win_L);
-        size_t ws_doubles = (size_t)s->win_blocks * windowed_ws_doubles(opts->N, s->win_L);
-        if (!windowed_is_resident(s->win_L) && (s->alt_L = pit_rounds_stages(opts->N, B)) != 0) {   // one workspace per instance for rti_pit_kernel's blocks
-            s->alt_blocks = windowed_blocks(opts->N, B, s->alt_L);
-            const size_t alt = (size_t)B * windowed_ws_doubles(opts->N, s->alt_L);
-            ws_doubles = alt > ws_doubles ? alt : ws_doubles;
-        }
-        AL(ws, ws_doubles);
-    }
-    // rti_phase 1 / 2 at a horizon the fused kernels serve: the resident kernel's split launches need a workspace per instance
-    if (fused_supported(opts->N) && !s->force_windowed && opts->kernel_path != BROV_PATH_STREAMING && split_resident_horizon(opts->N) &&
-        s->k.split_resident) {
-        int dev_ = 0, cus_ = 256;
-        (void)hipGetDevice(&dev_);
-        (void)hipDeviceGetAttribute(&cus_, hipDeviceAttributeMultiprocessorCount, dev_);
-        if (B <= cus_) {
-            AL(ws_split, (size_t)B * windowed_ws_doubles(opts->N, opts->N));
-        }
-    }
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) s->cus = cus;
+    const WorkspacePlan w = plan_workspaces(opts->N, B, s->cus, opts->kernel_path, s->k);
+    s->win_L = w.win_L; s->win_blocks = w.win_blocks; s->alt_L = w.alt_L; s->alt_blocks = w.alt_blocks;
+    if (w.ws_doubles) { AL(ws, w.ws_doubles); }
+    if (w.split_doubles) { AL(ws_split, w.split_doubles); }
 #undef AL
     if (rc != BROV_OK) { brov_destroy(s); return rc; }
     // create defaults: yref = 0, p = 0, x0 = [0,0,-20,0..] (acados_solver_bluerov2.c:355-364, 405-420, 520-527)
@@ -342,8 +369,6 @@ extern "C" int brov_create(brov_solver** out, int device, int B, const brov_opts
     hipMemset(s->res, 0, Bz * sizeof(brov_result));
     hipMemset(s->sched, 0, 3 * (size_t)sched_buffer_ints_host(B) * sizeof(int32_t));
     hipMemset(s->counter, 0, 64 * sizeof(int32_t));
-    // development knob: BROV_SCHED=0 hands the instances out in index order (A/B of the work ordering)
-    s->sched_on = s->k.sched != 0;
     {
         std::vector<double> h0(Bz * 12, 0.0);
         for (size_t k = 0; k < Bz; k++) h0[k * 12 + 2] = -20.0;
@@ -429,7 +454,7 @@ static const double* shared_window(const brov_solver* s) { return s->yref_view ?
 
 static int set_yref(brov_solver* s, const double* y, int shared, bool host, void* st) {
     if (!s) return BROV_ERR_ARG;
-    s->yref_view = nullptr; s->traj_line = -1;
+    forget_traj_window(s);
     s->yref_shared = shared != 0;
     const size_t n = (size_t)(s->N + 1) * 16;
     return shared ? copy_in(s, s->yref_sh, y, n, host, st) : copy_in(s, s->yref, y, n * s->B, host, st);
@@ -437,38 +462,36 @@ static int set_yref(brov_solver* s, const double* y, int shared, bool host, void
 extern "C" int brov_set_yref_host(brov_solver* s, const double* y, int shared) { return set_yref(s, y, shared, true, nullptr); }
 extern "C" int brov_set_yref_device(brov_solver* s, const double* y, int shared, void* st) { return set_yref(s, y, shared, false, st); }
 
-__global__ void bcast_par_kernel(const double* __restrict__ p16, double* __restrict__ par, int B, int N1) {
+// one row of `w` doubles per instance, copied to every stage of the instance: dst [B][N1][w] <- src [B][w]
+__global__ void bcast_rows_kernel(const double* __restrict__ src, double* __restrict__ dst, int B, int N1, int w) {
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t tot = (size_t)B * N1 * 16;
-    if (t >= tot) return;
-    const size_t b = t / ((size_t)N1 * 16);
-    par[t] = p16[b * 16 + (t & 15)];
+    if (t >= (size_t)B * N1 * w) return;
+    dst[t] = src[(t / ((size_t)N1 * w)) * w + t % w];
 }
-
-static int set_par(brov_solver* s, const double* p, int per_stage, bool host, void* st) {
-    if (!s || !p) return BROV_ERR_ARG;
-    s->pplant_stale = true;
-    const size_t N1 = s->N + 1;
-    if (per_stage) return copy_in(s, s->par, p, (size_t)s->B * N1 * 16, host, st);
+// per-stage rows [B][N+1][w] of the solver from the caller's [B][N+1][w] (per_stage) or [B][w] (one row for every stage of an instance)
+static int set_stage_rows(brov_solver* s, double* dst, const double* p, int w, int per_stage, bool host, void* st) {
+    const size_t N1 = s->N + 1, tot = (size_t)s->B * N1 * w;
+    if (per_stage) return copy_in(s, dst, p, tot, host, st);
     HIPCHK(hipSetDevice(s->device));
     const double* src = p;
     double* tmp = nullptr;
     if (!host) { if (int rc = order_behind_last(s, (hipStream_t)st)) return rc; }
     if (host) {
         HIPCHK(sync_last(s));
-        HIPCHK(hipMalloc((void**)&tmp, (size_t)s->B * 16 * sizeof(double)));
-        hipError_t e = hipMemcpy(tmp, p, (size_t)s->B * 16 * sizeof(double), hipMemcpyHostToDevice);
+        HIPCHK(hipMalloc((void**)&tmp, (size_t)s->B * w * sizeof(double)));
+        hipError_t e = hipMemcpy(tmp, p, (size_t)s->B * w * sizeof(double), hipMemcpyHostToDevice);
         if (e != hipSuccess) { hipFree(tmp); g_err = hipGetErrorString(e); return BROV_ERR_HIP; }
         src = tmp;
     }
-    const size_t tot = (size_t)s->B * N1 * 16;
-    hipLaunchKernelGGL(bcast_par_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)st, src, s->par, s->B, (int)N1);
-    if (host) {
-        hipStreamSynchronize((hipStream_t)st);
-        hipFree(tmp);
-    }
+    hipLaunchKernelGGL(bcast_rows_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)st, src, dst, s->B, (int)N1, w);
+    if (host) { hipStreamSynchronize((hipStream_t)st); hipFree(tmp); }
     HIPCHK(hipGetLastError());
     return BROV_OK;
+}
+static int set_par(brov_solver* s, const double* p, int per_stage, bool host, void* st) {
+    if (!s || !p) return BROV_ERR_ARG;
+    s->pplant_stale = true;
+    return set_stage_rows(s, s->par, p, 16, per_stage, host, st);
 }
 extern "C" int brov_set_params_host(brov_solver* s, const double* p, int per_stage) { return set_par(s, p, per_stage, true, nullptr); }
 extern "C" int brov_set_params_device(brov_solver* s, const double* p, int per_stage, void* st) { return set_par(s, p, per_stage, false, st); }
@@ -483,7 +506,7 @@ extern "C" int brov_set_param_stage_host(brov_solver* s, int inst, int stage, co
 }
 // ---- boundary corners of the reference API: non-uniform grids and a separate stage-0 weight ------------------------------------
 extern "C" int brov_set_time_steps(brov_solver* s, const double* ts) {
-    if (s && s->prep_path == 2) s->prep_path = 3;   // a parked preparation (rti_phase 1, resident kernel) does not survive this call
+    invalidate_preparation(s);
     if (!s) return BROV_ERR_ARG;
     HIPCHK(hipSetDevice(s->device));
     HIPCHK(sync_last(s));
@@ -499,7 +522,7 @@ extern "C" int brov_set_time_steps(brov_solver* s, const double* ts) {
     return upload_cst(s);
 }
 extern "C" int brov_set_stage0_weight(brov_solver* s, const double* W0) {
-    if (s && s->prep_path == 2) s->prep_path = 3;   // a parked preparation (rti_phase 1, resident kernel) does not survive this call
+    invalidate_preparation(s);
     if (!s) return BROV_ERR_ARG;
     HIPCHK(hipSetDevice(s->device));
     HIPCHK(sync_last(s));
@@ -517,11 +540,6 @@ extern "C" int brov_set_stage0_weight(brov_solver* s, const double* W0) {
 extern "C" int brov_general_grid(const brov_solver* s) { return s ? (general_grid(s) ? 1 : 0) : BROV_ERR_ARG; }
 
 // ---- 6-disturbance model variant ----------------------------------------------------------------
-__global__ void bcast_rp_kernel(const double* __restrict__ d2, double* __restrict__ rp, int B, int N1) {
-    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (size_t)B * N1 * 2) return;
-    rp[t] = d2[(t / ((size_t)N1 * 2)) * 2 + (t & 1)];
-}
 __global__ void split_p18_kernel(const double* __restrict__ p18, double* __restrict__ par, double* __restrict__ rp, size_t rows, int N1, int per_stage) {
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;   // one thread per (instance, stage)
     if (t >= rows) return;
@@ -556,24 +574,7 @@ static int need_dist6(brov_solver* s, const char* who) {
 static int set_rp(brov_solver* s, const double* d, int per_stage, bool host, void* st) {
     if (int rc = need_dist6(s, "brov_set_rp_disturbance")) return rc;
     if (!d) return BROV_ERR_ARG;
-    const size_t N1 = s->N + 1;
-    if (per_stage) return copy_in(s, s->par_rp, d, (size_t)s->B * N1 * 2, host, st);
-    HIPCHK(hipSetDevice(s->device));
-    const double* src = d;
-    double* tmp = nullptr;
-    if (!host) { if (int rc = order_behind_last(s, (hipStream_t)st)) return rc; }
-    if (host) {
-        HIPCHK(sync_last(s));
-        HIPCHK(hipMalloc((void**)&tmp, (size_t)s->B * 2 * sizeof(double)));
-        hipError_t e = hipMemcpy(tmp, d, (size_t)s->B * 2 * sizeof(double), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { hipFree(tmp); g_err = hipGetErrorString(e); return BROV_ERR_HIP; }
-        src = tmp;
-    }
-    const size_t tot = (size_t)s->B * N1 * 2;
-    hipLaunchKernelGGL(bcast_rp_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)st, src, s->par_rp, s->B, (int)N1);
-    if (host) { hipStreamSynchronize((hipStream_t)st); hipFree(tmp); }
-    HIPCHK(hipGetLastError());
-    return BROV_OK;
+    return set_stage_rows(s, s->par_rp, d, 2, per_stage, host, st);
 }
 extern "C" int brov_set_rp_disturbance_host(brov_solver* s, const double* d, int per_stage) { return set_rp(s, d, per_stage, true, nullptr); }
 extern "C" int brov_set_rp_disturbance_device(brov_solver* s, const double* d, int per_stage, void* st) { return set_rp(s, d, per_stage, false, st); }
@@ -622,7 +623,7 @@ extern "C" int brov_set_yref_stage_host(brov_solver* s, int inst, int stage, con
         for (int b = 0; b < s->B; b++)
             HIPCHK(hipMemcpy(s->yref + (size_t)b * (s->N + 1) * 16, shared_window(s), (size_t)(s->N + 1) * 16 * sizeof(double), hipMemcpyDeviceToDevice));
         s->yref_shared = false;
-        s->yref_view = nullptr; s->traj_line = -1;
+        forget_traj_window(s);
     }
     HIPCHK(hipMemcpy(s->yref + ((size_t)inst * (s->N + 1) + stage) * 16, y, (size_t)ny * sizeof(double), hipMemcpyHostToDevice));
     return BROV_OK;
@@ -636,7 +637,7 @@ extern "C" int brov_traj_set_host(brov_solver* s, const double* traj, int rows) 
         HIPCHK(hipMemcpy(s->yref_sh, s->yref_view, (size_t)(s->N + 1) * 16 * sizeof(double), hipMemcpyDeviceToDevice));
     // whatever window is in force -- a view, or one launch_window built from the OLD table (12 columns, end padding) -- no longer names a
     // line of the table that is coming: brov_solve_ticks(row_stride > 0) must not walk the new table from the old one's line
-    s->yref_view = nullptr; s->traj_line = -1;
+    forget_traj_window(s);
     if (s->traj) { hipFree(s->traj); s->traj = nullptr; }
     HIPCHK(hipMalloc((void**)&s->traj, (size_t)rows * 16 * sizeof(double)));
     HIPCHK(hipMemcpy(s->traj, traj, (size_t)rows * 16 * sizeof(double), hipMemcpyHostToDevice));
@@ -667,7 +668,7 @@ extern "C" int brov_set_yref_from_traj_lines_host(brov_solver* s, const int32_t*
     HIPCHK(hipMemcpy(s->lines, lines, (size_t)s->B * sizeof(int), hipMemcpyHostToDevice));
     launch_window(s->traj, s->traj_rows, s->lines, 0, s->B, s->N, ncols, s->yref, nullptr);
     s->yref_shared = false;
-    s->yref_view = nullptr; s->traj_line = -1;
+    forget_traj_window(s);
     HIPCHK(hipGetLastError());
     return BROV_OK;
 }
@@ -690,7 +691,7 @@ extern "C" int brov_set_yref_candidates(brov_solver* s, double t0, double dt, vo
     launch_candidates(s->cand_kind, s->scratch3, s->scratch3 + s->B, s->scratch3 + 2 * (size_t)s->B, t0, dt, s->B, s->N, s->yref,
                       (hipStream_t)stream);
     s->yref_shared = false;
-    s->yref_view = nullptr; s->traj_line = -1;
+    forget_traj_window(s);
     HIPCHK(hipGetLastError());
     return BROV_OK;
 }
@@ -843,9 +844,107 @@ extern "C" int brov_get_x0_host(brov_solver* s, double* x0) {
     HIPCHK(hipMemcpy(x0, s->x0, (size_t)s->B * 12 * sizeof(double), hipMemcpyDeviceToHost));
     return BROV_OK;
 }
-static DevParams make_params(const brov_solver* s);
+// ---- which kernels a call launches, and from which workspace: decided here, once per call ------------------------------------------------
+// LDS-resident kernels serve the one-call step (rti_phase 0) on the uniform and the general grid: the fused ones the whole horizon for
+// N <= 23, the windowed ones above.  rti_phase 1 / 2 (preparation and feedback as separate calls) need something to carry the preparation
+// over: the streaming pair keeps the linearisation in HBM; the windowed kernel's RESIDENT configuration -- at most one instance per CU, a
+// workspace per instance -- has split launches (rti_window_kernel_res_split): the preparation parks the factorised LDS image per instance,
+// the feedback runs from the forward sweep on.  Fused-kernel horizons take that configuration from a workspace of its own (ws_split, see
+// plan_workspaces).  A feedback call follows the path its preparation took (prep_path); BROV_SPLIT_RESIDENT=0: the streaming pair.
+enum { FAM_STREAMING = 0, FAM_FUSED, FAM_WINDOWED };
+struct SolvePlan {
+    int family = FAM_STREAMING;
+    bool split_ok = false;           // the solver's settings allow the resident split launches for rti_phase 1 / 2
+    int rti_split = 0;               // windowed family: 0 one launch, 1 / 2 the resident split launch of that rti_phase
+    double* ws = nullptr;            // windowed family: workspace (the solver's ws, or ws_split at a fused-kernel horizon), doubles per block,
+    int64_t ws_stride = 0;           // ... stages per window and persistent blocks of THIS launch
+    int win_L = 0, win_blocks = 0;
+    int pit = 0, pit_blocks = 0;     // parallel-in-time kernel ahead of the resident one: DevParams::pit (0: not launched), its blocks
+    int prep_path = 1;               // what brov_solver::prep_path becomes when this call is a preparation
+};
+static SolvePlan plan_solve(const brov_solver* s, int rti_phase) {
+    SolvePlan p;
+    const bool lds = s->opts.kernel_path != BROV_PATH_STREAMING, fused_h = serves_fused(s);
+    const bool may_split = lds && !s->dump_lin && s->k.split_resident;
+    const bool split_fused = may_split && fused_h && s->ws_split != nullptr;
+    p.split_ok = split_fused || (may_split && !fused_h && s->ws != nullptr && windowed_is_resident(s->win_L) && s->win_blocks == s->B);
+    const bool split = p.split_ok && (rti_phase == 1 || (rti_phase == 2 && s->prep_path == 2));
+    p.prep_path = split ? 2 : 1;
+    p.ws = s->ws; p.win_L = s->win_L; p.win_blocks = s->win_blocks;
+    if (split && split_fused) { p.ws = s->ws_split; p.win_L = s->N; p.win_blocks = s->B; }   // one window = the horizon, one block per instance
+    p.ws_stride = p.win_L ? (int64_t)windowed_ws_doubles(s->N, p.win_L) : 0;
+    if (!lds || (rti_phase != 0 && !split)) return p;
+    if (fused_h && !split) { p.family = FAM_FUSED; return p; }
+    if (!p.ws) return p;             // (a solver created with BROV_PATH_STREAMING has no workspace: the streaming pair whatever the path says now)
+    p.family = FAM_WINDOWED;
+    p.rti_split = rti_phase;
+    p.pit_blocks = p.win_blocks;
+    // The parallel-in-time kernel (BROV_PIT=0 off, 2: every instance is tried, not only those whose previous step was an early exit) runs whenever
+    // it can serve the solve -- a constant rule since round 5: it runs the whole QP loop itself (qp/pit.hpp), so what it leaves to the resident
+    // kernel behind it are the instances it gives up on (a NaN, a pivot block that fails or is ill-conditioned: verdicts of its first pass), and
+    // those cost it next to nothing.
+    bool pit = false;
+    if (s->k.pit && rti_phase == 2) {
+        // feedback of a split tick: its feedback instantiation rolls out the four quarters at once from what the preparation parked
+        pit = s->k.split_parallel && pit_supported(s->N, p.win_L);
+    } else if (s->k.pit && rti_phase == 0 && !s->dump_lin) {
+        if (s->alt_L) {              // between one and two instances per CU: the resident configuration, one rti_pit_kernel block per instance
+            p.win_L = s->alt_L; p.win_blocks = s->alt_blocks; p.ws_stride = (int64_t)windowed_ws_doubles(s->N, s->alt_L);
+            p.pit_blocks = s->B;
+        }
+        pit = pit_supported(s->N, p.win_L);
+    }
+    p.pit = pit ? s->k.pit : 0;
+    return p;
+}
+
+static DevParams make_params(const brov_solver* s, const SolvePlan& plan) {
+    DevParams P;
+    std::memset(&P, 0, sizeof P);
+    P.B = s->B; P.N = s->N;
+    P.qp_iter_max = s->opts.qp_iter_max; P.early_exit = s->opts.qp_early_exit;
+    P.on_failure = s->opts.on_failure; P.dump_lin = s->dump_lin ? 1 : 0;
+    P.robust_kkt_max = s->k.robust_kkt_max;
+    P.robust_pivot = s->k.robust_pivot;            // development knob: 0 off, 1 on demand (default), 2 every instance
+    P.partial_refactor = s->k.partial_refactor;    // development knob (A/B, tests)
+    P.Ts = s->opts.Ts; P.tol_mu = s->opts.qp_tol_mu; P.tol_stat = s->opts.qp_tol_stat;
+    for (int j = 0; j < 16; j++) P.W[j] = s->opts.W[j];
+    for (int j = 0; j < 12; j++) P.We[j] = s->opts.We[j];
+    for (int j = 0; j < 4; j++) { P.lbu[j] = s->opts.lbu[j]; P.ubu[j] = s->opts.ubu[j]; }
+    P.x0 = s->tick_x0 ? s->tick_x0 : s->x0;
+    P.yref = s->tick_yref ? s->tick_yref : (s->yref_shared ? shared_window(s) : s->yref);
+    P.yref_stride = s->yref_shared ? 0 : (int64_t)(s->N + 1) * 16;
+    P.par = s->tick_par ? s->tick_par : s->par;
+    P.par_rp = s->dist6 ? s->par_rp : nullptr;
+    P.tsv = general_grid(s) ? s->tsv : nullptr;
+    P.sched = s->k.sched ? s->sched : nullptr;   // development knob: BROV_SCHED=0 hands the instances out in index order (A/B of the work ordering)
+    P.sched_stride = sched_buffer_ints_host(s->B);
+    P.sched_r = (int)(s->sched_tick % 3); P.sched_w = (int)((s->sched_tick + 1) % 3); P.sched_z = (int)((s->sched_tick + 2) % 3);
+    P.wst = general_grid(s) ? s->wst : nullptr;
+    P.x = s->x; P.u = s->u; P.pi = s->pi; P.lam = s->lam;
+    P.BA = s->BA; P.bvec = s->bvec; P.kktp = s->kktp;
+    P.Ks = s->Ks; P.Kt = s->Kt; P.Mt = s->Mt; P.Pb = s->Pb; P.kff = s->kff; P.vhat = s->vhat; P.ipm = s->ipm;
+    P.dxb = s->dxb; P.cst = s->cst; P.res = s->res;
+    P.mail = s->mail; P.mail_flag = s->mail_flag; P.mail_seq = s->mail_seq;
+    P.mail_early = s->k.mail_early;   // development knob (A/B)
+    P.counter = s->counter + 32 * (s->win_tick & 1u);
+    P.counter_next = s->counter + 32 * ((s->win_tick + 1u) & 1u);
+    P.ws = plan.ws; P.ws_stride = plan.ws_stride; P.win_L = plan.win_L; P.win_blocks = plan.win_blocks;
+    P.rti_split = plan.rti_split; P.pit_blocks = plan.pit_blocks;
+    if (plan.pit) { P.pit = plan.pit; P.pit_done = s->pit_done; P.pit_try = s->k.pit_try; P.pit_light = s->k.pit_light; }
+    P.dbg = s->dbg;
+    return P;
+}
+// the launch(es) of an LDS-resident family and what the solver remembers of them
+static void launch_lds(brov_solver* s, const DevParams& P, int family, hipStream_t st) {
+    if (family == FAM_FUSED) launch_fused(P, st, s->k);
+    else { launch_windowed(P, st, s->k); s->win_tick++; }   // persistent blocks; the two hand-out counters alternate
+    s->pit_ran = P.pit != 0;
+    s->last_family = family;
+    s->last_stream = st;
+}
+
 static int ticks_kernel(const brov_solver* s);
-static void launch_ticks(brov_solver* s, DevParams& P, hipStream_t st, int which);
 // Device-side logs of the closed loops (brov_closed_loop_ex, brov_closed_loop_dob): a buffer per HOST log the caller asked for, the start
 // state and the zeroed wrench log enqueued on the loop's stream, everything copied back after the loop's one host wait.  Logs come back
 // only from a loop that completed: a failing call leaves the caller's arrays as they were.
@@ -918,20 +1017,20 @@ extern "C" int brov_closed_loop_ex(brov_solver* s, int ticks, int line0, int nco
         rc = brov_set_yref_from_traj(s, line0, 16, st);
         if (rc == BROV_OK) rc = order_behind_last(s, st);
         if (rc == BROV_OK) {
-            DevParams P = make_params(s);
+            DevParams P = make_params(s, plan_solve(s, 0));
             P.sched = nullptr;
             P.ticks = ticks; P.tick_yref = 16; P.tick_status = L.status(0);
             P.plant_pp = s->pplant; P.plant_rp = plant_rp(s); P.plant_rp_stride = plant_rp_stride(s); P.plant_substeps = substeps; P.plant_dt = dt;
             P.x0_rw = s->x0; P.plant_xlog = L.x(1); P.plant_ulog = L.u(0);
             if (s->timing) { hipEventRecord(s->ev[0], st); hipEventRecord(s->ev[1], st); }   // (as brov_solve_ticks: brov_last_solve_seconds then reports THIS launch)
-            launch_ticks(s, P, st, which);
+            launch_lds(s, P, which, st); s->prep_path = 0;
             if (s->timing) { hipEventRecord(s->ev[2], st); s->ev_valid = true; }
             s->traj_line = line0 + ticks - 1; s->yref_view = s->traj + (size_t)s->traj_line * 16;
             s->wr_tick += ticks;
         }
     }
     for (int k = 0; k < ticks && rc == BROV_OK && !one_launch; k++) {
-        s->yref_view = nullptr; s->traj_line = -1;
+        forget_traj_window(s);
         launch_window(s->traj, s->traj_rows, nullptr, line0 + k, 1, s->N, ncols, s->yref_sh, st);
         s->yref_shared = true;
         rc = brov_solve_phase(s, st, 0);
@@ -982,7 +1081,7 @@ extern "C" int brov_closed_loop_dob(brov_solver* s, brov_ekf* e, brov_rls* r, in
 }
 
 extern "C" int brov_set_iterate_host(brov_solver* s, const double* x, const double* u, const double* pi, const double* lam) {
-    if (s && s->prep_path == 2) s->prep_path = 3;   // a parked preparation (rti_phase 1, resident kernel) does not survive this call
+    invalidate_preparation(s);
     if (!s) return BROV_ERR_ARG;
     HIPCHK(hipSetDevice(s->device));
     HIPCHK(sync_last(s));   // a solve on a non-blocking stream may still be writing the iterate
@@ -1005,7 +1104,7 @@ extern "C" int brov_get_iterate_host(brov_solver* s, double* x, double* u, doubl
     return BROV_OK;
 }
 extern "C" int brov_reset(brov_solver* s) {  // acados_solver_bluerov2.c:797-830: everything to zero
-    if (s && s->prep_path == 2) s->prep_path = 3;   // a parked preparation (rti_phase 1, resident kernel) does not survive this call
+    invalidate_preparation(s);
     if (!s) return BROV_ERR_ARG;
     HIPCHK(hipSetDevice(s->device));
     HIPCHK(sync_last(s));
@@ -1019,142 +1118,46 @@ extern "C" int brov_reset(brov_solver* s) {  // acados_solver_bluerov2.c:797-830
     return BROV_OK;
 }
 
-static DevParams make_params(const brov_solver* s) {
-    DevParams P;
-    std::memset(&P, 0, sizeof P);
-    P.B = s->B; P.N = s->N;
-    P.qp_iter_max = s->opts.qp_iter_max; P.early_exit = s->opts.qp_early_exit;
-    P.on_failure = s->opts.on_failure; P.dump_lin = s->dump_lin ? 1 : 0;
-    P.robust_kkt_max = s->k.robust_kkt_max;
-    P.robust_pivot = s->k.robust_pivot;            // development knob: 0 off, 1 on demand (default), 2 every instance
-    P.partial_refactor = s->k.partial_refactor;    // development knob (A/B, tests)
-    P.Ts = s->opts.Ts; P.tol_mu = s->opts.qp_tol_mu; P.tol_stat = s->opts.qp_tol_stat;
-    for (int j = 0; j < 16; j++) P.W[j] = s->opts.W[j];
-    for (int j = 0; j < 12; j++) P.We[j] = s->opts.We[j];
-    for (int j = 0; j < 4; j++) { P.lbu[j] = s->opts.lbu[j]; P.ubu[j] = s->opts.ubu[j]; }
-    P.x0 = s->tick_x0 ? s->tick_x0 : s->x0;
-    P.yref = s->tick_yref ? s->tick_yref : (s->yref_shared ? shared_window(s) : s->yref);
-    P.yref_stride = s->yref_shared ? 0 : (int64_t)(s->N + 1) * 16;
-    P.par = s->tick_par ? s->tick_par : s->par;
-    P.par_rp = s->dist6 ? s->par_rp : nullptr;
-    P.tsv = general_grid(s) ? s->tsv : nullptr;
-    P.sched = s->sched_on ? s->sched : nullptr;
-    P.sched_stride = sched_buffer_ints_host(s->B);
-    P.sched_r = (int)(s->sched_tick % 3); P.sched_w = (int)((s->sched_tick + 1) % 3); P.sched_z = (int)((s->sched_tick + 2) % 3);
-    P.wst = general_grid(s) ? s->wst : nullptr;
-    P.x = s->x; P.u = s->u; P.pi = s->pi; P.lam = s->lam;
-    P.BA = s->BA; P.bvec = s->bvec; P.kktp = s->kktp;
-    P.Ks = s->Ks; P.Kt = s->Kt; P.Mt = s->Mt; P.Pb = s->Pb; P.kff = s->kff; P.vhat = s->vhat; P.ipm = s->ipm;
-    P.dxb = s->dxb; P.cst = s->cst; P.res = s->res;
-    P.mail = s->mail; P.mail_flag = s->mail_flag; P.mail_seq = s->mail_seq;
-    P.mail_early = s->k.mail_early;   // development knob (A/B)
-    P.ws = s->ws; P.ws_stride = s->win_L ? (int64_t)windowed_ws_doubles(s->N, s->win_L) : 0; P.counter = s->counter + 32 * (s->win_tick & 1u);
-    P.counter_next = s->counter + 32 * ((s->win_tick + 1u) & 1u);
-    P.win_L = s->win_L; P.win_blocks = s->win_blocks;
-    P.dbg = s->dbg;
-    return P;
-}
-
 extern "C" int brov_solve_phase(brov_solver* s, void* stream, int rti_phase) {
     if (!s || rti_phase < 0 || rti_phase > 2) return BROV_ERR_ARG;
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
     if (int rc = order_behind_last(s, st)) return rc;   // e.g. a brov_tick_host whose kernel is still finishing on the solver's own stream
-    DevParams P = make_params(s);
-    const int path = s->opts.kernel_path;
-    // LDS-resident kernels (one launch): whole horizon for N <= 23, windowed above.  rti_phase 1 / 2 (preparation and feedback as
-    // separate calls) need the linearisation in HBM between the calls: streaming kernels.
-    // a general grid (per-stage time steps / separate stage-0 weight) runs on the LDS-resident kernels too (round 4: rti_fused_kernel_grid,
-    // rti_window_kernel_grid, rti_window_kernel_res_grid, rti_pit_kernel_grid)
-    // rti_phase 1 / 2 in the windowed kernel's resident mode (at most one instance per CU at 24 <= N <= 81): the split
-    // launches of rti_window_kernel_res_split -- preparation parks the factorised LDS image per instance, feedback runs from the forward
-    // sweep on.  A feedback call follows the path its preparation took (prep_path); BROV_SPLIT_RESIDENT=0: the streaming pair as before.
-    const bool fused_h = fused_supported(s->N) && !s->force_windowed;
-    const bool split_env = s->k.split_resident != 0;
-    const bool split_fused_h = fused_h && s->ws_split != nullptr && path != BROV_PATH_STREAMING && !s->dump_lin && split_env;   // (N <= 23: see brov_create)
-    const bool split_res_ok = split_fused_h || (path != BROV_PATH_STREAMING && !fused_h && s->ws != nullptr &&
-                              windowed_is_resident(s->win_L) && s->win_blocks == (int)s->B && !s->dump_lin && split_env);
-    const bool split_res = (rti_phase == 1 && split_res_ok) || (rti_phase == 2 && split_res_ok && s->prep_path == 2);
+    const SolvePlan plan = plan_solve(s, rti_phase);
     if (rti_phase == 2 && s->prep_path == 0) {   // no preparation, or one that a later step (rti_phase 0, an earlier feedback) has used up: the iterate it linearised is gone
         g_err = "brov_solve: rti_phase 2 needs a preparation (rti_phase 1) of the CURRENT iterate: none since the last step";
         return BROV_ERR_ARG;
     }
-    if (rti_phase == 2 && (s->prep_path == 3 || (s->prep_path == 2 && !split_res_ok))) {   // (a grid / option / iterate / path change between the two calls)
+    if (rti_phase == 2 && (s->prep_path == 3 || (s->prep_path == 2 && !plan.split_ok))) {   // (a grid / option / iterate / path change between the two calls)
         g_err = "brov_solve: rti_phase 2 after a preparation on the resident kernel, which the solver's settings no longer allow: repeat rti_phase 1";
         return BROV_ERR_ARG;
     }
-    if (rti_phase == 1) s->prep_path = split_res ? 2 : 1;
-    // (128 < N <= 256: rti_window_kernel_long / _long_grid)
-    const bool lds_path = (rti_phase == 0 || split_res) && path != BROV_PATH_STREAMING;
-    const bool fused = lds_path && fused_supported(s->N) && !s->force_windowed && !(split_res && split_fused_h);
-    const bool windowed = lds_path && !fused && (s->ws != nullptr || (split_res && split_fused_h));
-    if (split_res && split_fused_h) {   // the resident configuration of a fused-kernel horizon: one window = the horizon, one block per instance
-        P.ws = s->ws_split; P.ws_stride = (int64_t)windowed_ws_doubles(s->N, s->N); P.win_L = s->N; P.win_blocks = (int32_t)s->B;
-    }
-    s->pit_ran = false;
+    if (rti_phase == 1) s->prep_path = plan.prep_path;
+    const DevParams P = make_params(s, plan);
     if (s->timing) hipEventRecord(s->ev[0], st);
-    if (fused || windowed) {
+    if (plan.family != FAM_STREAMING) {
         if (s->timing) hipEventRecord(s->ev[1], st);
-        if (fused) launch_fused(P, st, s->k);
-        else {
-            // batches the resident mode serves: the parallel-in-time step-0 solve goes first (rti_pit_kernel; BROV_PIT=0 off, 2: every
-            // instance is tried, not only those whose previous step was an early exit)
-            const int pit = s->k.pit;
-            const bool pit_can = pit && s->pit_done && !s->dump_lin && rti_phase == 0;
-            P.rti_split = rti_phase;
-            // the feedback half of a split tick: the parallel-in-time kernel's feedback instantiation first, rolling out the
-            // four quarters at once from what the preparation parked; the resident feedback launch behind it for what it leaves
-            if (rti_phase == 2 && pit && s->pit_done && pit_supported(s->N, P.win_L) && s->k.split_parallel) {
-                P.pit = pit; P.pit_done = s->pit_done; P.pit_blocks = P.win_blocks;
-                P.pit_try = s->k.pit_try; P.pit_light = s->k.pit_light;
-            }
-            P.pit_blocks = P.win_blocks;
-            // Round 5: a constant rule.  The parallel kernel runs the whole QP loop itself (qp/pit.hpp), so what it leaves to the resident kernel
-            // behind it are the instances it gives up on -- a NaN, a pivot block that fails or is ill-conditioned: verdicts of its first pass --, and
-            // those cost it next to nothing.  Round 4's kernel left every instance that needed a fourth try or an interior-point iteration, which then
-            // STARTED only when it was over; the host followed a pinned report word, paused the kernel for eight solves and probed (forty lines here).
-            // All of that is gone: the kernel runs whenever it can serve the solve.
-            const bool pit_now = pit_can && (s->alt_L != 0 || pit_supported(s->N, P.win_L));
-            if (pit_now && s->alt_L) {   // between one and two instances per CU: the resident configuration, one rti_pit_kernel block per instance
-                P.win_L = s->alt_L; P.win_blocks = s->alt_blocks; P.ws_stride = (int64_t)windowed_ws_doubles(s->N, s->alt_L);
-                P.pit_blocks = (int32_t)s->B;
-            }
-            if (pit_now && pit_supported(s->N, P.win_L)) {
-                P.pit = pit; P.pit_done = s->pit_done;
-                P.pit_try = s->k.pit_try; P.pit_light = s->k.pit_light;
-            }
-            s->pit_ran = P.pit != 0;
-            launch_windowed(P, st); s->win_tick++;   // persistent blocks; the two hand-out counters alternate
-        }
+        launch_lds(s, P, plan.family, st);
     } else {
         if (rti_phase != 2) launch_linearise(P, st);
         if (s->timing) hipEventRecord(s->ev[1], st);
         if (rti_phase != 1) launch_qp(P, st);
+        s->pit_ran = false; s->last_family = FAM_STREAMING; s->last_stream = st;
     }
     if (s->timing) { hipEventRecord(s->ev[2], st); s->ev_valid = true; }
     if (rti_phase != 1) s->sched_tick++;   // a QP kernel ran: it wrote the next ordering
     if (rti_phase != 1) s->prep_path = 0;  // ... and the iterate moved (and the per-block workspace was rewritten): whatever preparation there was is used up
-    s->last_fused = fused;
-    s->last_windowed = windowed;
-    s->last_stream = st;
     HIPCHK(hipGetLastError());
     return BROV_OK;
 }
 extern "C" int brov_solve(brov_solver* s, void* stream) { return brov_solve_phase(s, stream, 0); }
 
-// steps in one launch: 1 = rti_fused_kernel_ticks (N <= 23), 2 = rti_window_kernel_ticks (longer horizons, large batches: the windowed kernel's
+// steps in one launch, by family: FAM_FUSED = rti_fused_kernel_ticks (N <= 23), FAM_WINDOWED = rti_window_kernel_ticks (longer horizons, large batches: the windowed kernel's
 // persistent blocks), 0 = neither (general grid, streaming pair, a dumped linearisation, the resident / parallel-in-time configurations of small
 // batches -- those are latency paths: a launch per step)
 static int ticks_kernel(const brov_solver* s) {
     if (s->opts.kernel_path == BROV_PATH_STREAMING || general_grid(s) || s->dump_lin) return 0;
-    if (fused_supported(s->N) && !s->force_windowed) return 1;
-    if (s->ws != nullptr && !windowed_is_resident(s->win_L) && s->alt_L == 0) return 2;
-    return 0;
-}
-static void launch_ticks(brov_solver* s, DevParams& P, hipStream_t st, int which) {
-    if (which == 1) { launch_fused_ticks(P, st, s->k); s->last_fused = true; s->last_windowed = false; }
-    else { launch_windowed(P, st); s->win_tick++; s->last_fused = false; s->last_windowed = true; }
-    s->pit_ran = false; s->prep_path = 0; s->last_stream = st;
+    return serves_fused(s) ? FAM_FUSED : serves_windowed_ticks(s) ? FAM_WINDOWED : 0;
 }
 
 // `ticks` RTI steps of every instance with ONE launch where the fused kernels serve the solver (N <= 23, uniform grid): rti_fused_kernel_ticks,
@@ -1182,11 +1185,11 @@ extern "C" int brov_solve_ticks(brov_solver* s, void* stream, int ticks, int row
         return BROV_OK;
     }
     if (int rc = order_behind_last(s, st)) return rc;
-    DevParams P = make_params(s);
+    DevParams P = make_params(s, plan_solve(s, 0));
     P.sched = nullptr;                 // a launch of many steps neither reads nor writes the work ordering: every instance follows its own history
     P.ticks = ticks; P.tick_yref = (int64_t)row_stride * 16; P.tick_status = status_log;
     if (s->timing) { hipEventRecord(s->ev[0], st); hipEventRecord(s->ev[1], st); }
-    launch_ticks(s, P, st, which);
+    launch_lds(s, P, which, st); s->prep_path = 0;
     if (s->timing) { hipEventRecord(s->ev[2], st); s->ev_valid = true; }
     if (row_stride > 0) {              // the window in force is the last step's
         s->traj_line = line0 + (ticks - 1) * row_stride;
@@ -1268,7 +1271,7 @@ extern "C" int brov_tick_host(brov_solver* s, const double* x0, const double* yr
     if (x0 && x0 != px) std::memcpy(px, x0, n_x0 * sizeof(double));   // (equal: the caller wrote into the staging buffer, brov_tick_buffers)
     if (yref_shared) {
         if (yref_shared != py) std::memcpy(py, yref_shared, n_y * sizeof(double));
-        s->yref_view = nullptr; s->traj_line = -1;
+        forget_traj_window(s);
         s->yref_shared = true;
     }
     if (par_stage) { if (par_stage != pp) std::memcpy(pp, par_stage, n_p * sizeof(double)); s->pplant_stale = true; }
@@ -1392,10 +1395,10 @@ extern "C" int brov_tick_host(brov_solver* s, const double* x0, const double* yr
 }
 
 extern "C" int brov_set_opts(brov_solver* s, const brov_opts* o) {
-    if (s && s->prep_path == 2) s->prep_path = 3;   // a parked preparation (rti_phase 1, resident kernel) does not survive this call
+    invalidate_preparation(s);
     if (!s || !o || o->N != s->N) { g_err = "brov_set_opts: bad argument (N is fixed at create)"; return BROV_ERR_ARG; }
     if (const char* why = opts_problem(o)) { g_err = std::string("brov_set_opts: ") + why; return BROV_ERR_ARG; }
-    if (o->kernel_path == BROV_PATH_FUSED && !fused_supported(o->N) && !s->ws) {
+    if (o->kernel_path == BROV_PATH_FUSED && !serves_fused(s) && !s->ws) {
         // the windowed kernel's workspace is allocated at create, from the path and batch asked for then
         g_err = "brov_set_opts: BROV_PATH_FUSED at this horizon needs the windowed kernel's workspace, which this solver was created without "
                 "(created with BROV_PATH_STREAMING): create it with BROV_PATH_AUTO or BROV_PATH_FUSED";
@@ -1418,7 +1421,7 @@ extern "C" int brov_synchronize(brov_solver* s, void* stream) {
     return BROV_OK;
 }
 extern "C" int brov_last_kernel_path(const brov_solver* s) {
-    return s ? (s->last_fused ? BROV_PATH_FUSED : (s->last_windowed ? BROV_PATH_WINDOWED : BROV_PATH_STREAMING)) : BROV_ERR_ARG;
+    return s ? (s->last_family == FAM_FUSED ? BROV_PATH_FUSED : (s->last_family == FAM_WINDOWED ? BROV_PATH_WINDOWED : BROV_PATH_STREAMING)) : BROV_ERR_ARG;
 }
 // which instances of the LAST solve were completed by the parallel-in-time kernel (rti_pit_kernel, batches the resident windowed mode
 // serves): done[b] = 1, else 0 -- all zero when that kernel did not run.  Test / bench instrumentation.
@@ -1441,7 +1444,7 @@ extern "C" int brov_pit_last(brov_solver* s, int32_t* done) {
 extern "C" int brov_lds_kernel_info(const brov_solver* s, int32_t info[4]) {
     if (!s || !info) return BROV_ERR_ARG;
     HIPCHK(hipSetDevice(s->device));
-    const bool fused = fused_supported(s->N) && !s->force_windowed;
+    const bool fused = serves_fused(s);
     // streaming kernels (asked for, or forced by a general grid, or no windowed workspace): stage blocks in HBM, nothing to report
     if (s->opts.kernel_path == BROV_PATH_STREAMING || (!fused && !s->ws)) { info[0] = info[1] = info[2] = info[3] = 0; return BROV_OK; }
     lds_kernel_info(s->N, s->win_L, !fused, info, s->k);
@@ -1492,7 +1495,7 @@ extern "C" int brov_get_u0_host(brov_solver* s, double* u0) {
 }
 extern "C" const brov_result* brov_results_device(const brov_solver* s) { return s ? s->res : nullptr; }
 extern "C" double* brov_x0_device(brov_solver* s) { return s ? s->x0 : nullptr; }
-extern "C" double* brov_yref_device(brov_solver* s) { if (!s) return nullptr; s->yref_shared = false; s->yref_view = nullptr; s->traj_line = -1; return s->yref; }
+extern "C" double* brov_yref_device(brov_solver* s) { if (!s) return nullptr; s->yref_shared = false; forget_traj_window(s); return s->yref; }
 extern "C" double* brov_params_device(brov_solver* s) { if (!s) return nullptr; s->pplant_stale = true; return s->par; }
 extern "C" double* brov_x_device(brov_solver* s) { return s ? s->x : nullptr; }
 extern "C" double* brov_u_device(brov_solver* s) { return s ? s->u : nullptr; }

@@ -100,27 +100,30 @@ struct DevKnobs {
     double robust_kkt_max = 1e6;
     int robust_pivot = 1, partial_refactor = 1, mail_early = 1, split_resident = 1, pit = 1, split_parallel = 1, pit_try = 1, pit_light = 1;
     int tick_mailbox = 1, tick_bulk = 1, tick_zerocopy = 1, sched = 1, force_windowed = 0, fused_waves = 0, lds_pad = 0, tick_breakdown = 0, closed_loop_fused = 1;
+    int no_resident = 0, win_blocks = 0, pit_rounds = 1;   // size the workspaces: in force as read at create (win_blocks 0: as many as fit)
+    int win_long = 0;                                      // the long-horizon windowed instantiations at every horizon (A/B)
 };
 
 enum { IPM_V = 0, IPM_TL, IPM_TU, IPM_LL, IPM_LU, IPM_GAM, IPM_RT, IPM_DVA, IPM_ACT, IPM_NARR };
 
+// qp_kernel.hip: the kernel table, the choice of a kernel from a call's properties, and the launches.  The launchers read the variant
+// from what the host's plan left in P (tsv, ticks, rti_split, win_L, pit && pit_done, mail && mail_early).
 int sched_buffer_ints_host(int B);   // int32 per work-ordering buffer (three of them)
 int prepare_kernels_on_device(std::string* why);   // dynamic-LDS limits of every solver kernel on the CURRENT device, once per device, checked (brov_create)
-void launch_linearise(const DevParams& P, hipStream_t st);
-void launch_qp(const DevParams& P, hipStream_t st);
-void launch_fused(const DevParams& P, hipStream_t st, const DevKnobs& k);
-void launch_fused_ticks(const DevParams& P, hipStream_t st, const DevKnobs& k);   // P.ticks steps per instance in one launch (uniform grid, N <= 23)  // linearise + QP in one kernel, stage blocks in LDS
+void launch_linearise(const DevParams& P, hipStream_t st);   // streaming pair: linearisation into HBM ...
+void launch_qp(const DevParams& P, hipStream_t st);          // ... and the QP out of it
+void launch_fused(const DevParams& P, hipStream_t st, const DevKnobs& k);   // linearise + QP in one kernel, stage blocks in LDS; P.ticks steps per instance in one launch
 bool fused_supported(int N);      // whole horizon fits the LDS slice (N <= 23)
 // windowed LDS-resident kernel for longer horizons: persistent blocks (one wavefront each) that take instances from a counter
-void launch_windowed(const DevParams& P, hipStream_t st);
+void launch_windowed(const DevParams& P, hipStream_t st, const DevKnobs& k);
 void lds_kernel_info(int N, int win_L, bool windowed, int32_t info[4], const DevKnobs& k);   // LDS bytes per block, blocks per CU, threads, kernel kind
 bool pit_supported(int N, int win_L);       // rti_pit_kernel ahead of the resident kernel
 bool windowed_is_resident(int win_L);      // one window = the whole horizon (small batches)
-int windowed_stage_count(int N, int B);   // stages per window (= N for batches of at most one instance per CU: resident mode)
-int windowed_blocks(int N, int B, int L); // persistent blocks that will be launched on the current device
+int windowed_stage_count(int N, int B, int cus, const DevKnobs& k);   // stages per window (= N for batches of at most one instance per CU: resident mode)
+int windowed_blocks(int B, int L, int cus, const DevKnobs& k);        // persistent blocks of a launch on the current device
 size_t windowed_ws_doubles(int N, int L); // per-block workspace
 bool split_resident_horizon(int N);           // rti_phase 1 / 2 on the resident kernel's split launches at a fused-kernel horizon
-int pit_rounds_stages(int N, int B);          // batches of up to two instances per CU: resident stage count for parallel-in-time rounds, or 0
+int pit_rounds_stages(int N, int B, int cus, const DevKnobs& k);      // batches of up to two instances per CU: resident stage count for parallel-in-time rounds, or 0
 void launch_window(const double* traj, int rows, const int* lines, int line0, int B, int N, int ncols, double* out, hipStream_t st);
 void launch_plant(double* x0, const brov_result* res, const double* pplant, const double* prp, int rp_stride, int B, double dt, int substeps,
                   double* xlog, double* ulog, hipStream_t st);   // prp: roll / pitch disturbance moments, instance b at prp + b * rp_stride (or nullptr)

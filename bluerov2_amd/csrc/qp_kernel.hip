@@ -133,34 +133,48 @@ __global__ __launch_bounds__(64, 1) void rti_window_kernel_long(DevParams P) { r
 __global__ __launch_bounds__(64, 1) void rti_window_kernel_long_grid(DevParams P) { rti_window_body<false, true, false, false, true>(P); }
 __global__ __launch_bounds__(64, 1) void rti_window_kernel_long_ticks(DevParams P) { rti_window_body<false, false, false, true, true>(P); }
 
+// ---- the kernel table: every solver kernel ONCE -- function, name, threads per block, dynamic-LDS limit.  prepare_kernels_on_device sets the
+// limits from it, launch() takes function and block size from it, and the choosers below say which entry a call runs: a kernel that is in
+// the table cannot be launched ahead of its limit, and one that is not cannot be launched at all.
+enum KernelId {
+    K_NONE = -1,
+    K_QP, K_LIN, K_LIN_GRID,
+    K_FUSED, K_FUSED_W2, K_FUSED_GRID, K_FUSED_MAIL, K_FUSED_TICKS, K_FUSED_TICKS_W2,
+    K_WIN, K_WIN_GRID, K_WIN_TICKS, K_WIN_LONG, K_WIN_LONG_GRID, K_WIN_LONG_TICKS,
+    K_RES, K_RES_GRID, K_RES_SPLIT, K_RES_SPLIT_GRID,
+    K_PIT, K_PIT_GRID, K_PIT_FB, K_PIT_FB_GRID,
+    K_COUNT
+};
+struct Kernel { void (*fn)(DevParams); const char* name; int threads, lds_limit; };   // lds_limit 0: static LDS only
+#define BROV_K(k, threads, kb) {k, #k, threads, kb * 1024}
+static const Kernel kKernels[K_COUNT] = {
+    BROV_K(qp_kernel, 256, 0), BROV_K(lin_wave_kernel, 64, 64), BROV_K(lin_wave_kernel_grid, 64, 64),
+    BROV_K(rti_fused_kernel, 64, 160), BROV_K(rti_fused_kernel_w2, 64, 160), BROV_K(rti_fused_kernel_grid, 64, 160),
+    BROV_K(rti_fused_kernel_mail, 64, 160), BROV_K(rti_fused_kernel_ticks, 64, 160), BROV_K(rti_fused_kernel_ticks_w2, 64, 160),
+    BROV_K(rti_window_kernel, 64, 160), BROV_K(rti_window_kernel_grid, 64, 160), BROV_K(rti_window_kernel_ticks, 64, 160),
+    BROV_K(rti_window_kernel_long, 64, 160), BROV_K(rti_window_kernel_long_grid, 64, 160), BROV_K(rti_window_kernel_long_ticks, 64, 160),
+    BROV_K(rti_window_kernel_res, 256, 160), BROV_K(rti_window_kernel_res_grid, 256, 160),
+    BROV_K(rti_window_kernel_res_split, 256, 160), BROV_K(rti_window_kernel_res_split_grid, 256, 160),
+    BROV_K(rti_pit_kernel, 256, 160), BROV_K(rti_pit_kernel_grid, 256, 160), BROV_K(rti_pit_kernel_fb, 256, 160), BROV_K(rti_pit_kernel_fb_grid, 256, 160),
+};
+#undef BROV_K
+
 // The dynamic-LDS limit of every solver kernel (anything above 64 KB has to be asked for, per function and PER DEVICE), set ONCE per device and
 // CHECKED: brov_create calls this with its device current, so a runtime that refuses a limit fails the create with its reason instead of the
 // first launch with "invalid argument" -- and no launcher carries a lazy "first launch" flag any more.  Round 5's flags were plain statics,
 // flipped BEFORE the attribute calls ran: a second host thread making its first launch on the same device (one rank object per thread,
 // tests/test_gpu_group_loopback.py) could launch with > 64 KB ahead of the attribute.  std::call_once blocks that thread until the calls are over.
 int prepare_kernels_on_device(std::string* why) {
-    struct KernelLimit { const void* fn; int bytes; const char* name; };
-#define BROV_KL(k, kb) {(const void*)k, kb * 1024, #k}
-    static const KernelLimit limits[] = {
-        BROV_KL(lin_wave_kernel, 64), BROV_KL(lin_wave_kernel_grid, 64),
-        BROV_KL(rti_fused_kernel, 160), BROV_KL(rti_fused_kernel_w2, 160), BROV_KL(rti_fused_kernel_grid, 160), BROV_KL(rti_fused_kernel_mail, 160),
-        BROV_KL(rti_fused_kernel_ticks, 160), BROV_KL(rti_fused_kernel_ticks_w2, 160),
-        BROV_KL(rti_window_kernel, 160), BROV_KL(rti_window_kernel_grid, 160), BROV_KL(rti_window_kernel_ticks, 160),
-        BROV_KL(rti_window_kernel_res, 160), BROV_KL(rti_window_kernel_res_grid, 160), BROV_KL(rti_window_kernel_res_split, 160),
-        BROV_KL(rti_window_kernel_res_split_grid, 160),
-        BROV_KL(rti_window_kernel_long, 160), BROV_KL(rti_window_kernel_long_grid, 160), BROV_KL(rti_window_kernel_long_ticks, 160),
-        BROV_KL(rti_pit_kernel, 160), BROV_KL(rti_pit_kernel_grid, 160), BROV_KL(rti_pit_kernel_fb, 160), BROV_KL(rti_pit_kernel_fb_grid, 160),
-    };
-#undef BROV_KL
     constexpr int kMaxDev = 64;
     static std::once_flag once[kMaxDev];
     static std::string failure[kMaxDev];   // written inside call_once, read after it: ordered by call_once itself
     auto set_all = [](std::string& err) {
-        for (const KernelLimit& k : limits) {
-            const hipError_t e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.bytes);
+        for (const Kernel& k : kKernels) {
+            if (!k.lds_limit) continue;
+            const hipError_t e = hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds_limit);
             if (e != hipSuccess) {
                 (void)hipGetLastError();
-                err = std::string("hipFuncSetAttribute(") + k.name + ", MaxDynamicSharedMemorySize, " + std::to_string(k.bytes) + "): " + hipGetErrorString(e);
+                err = std::string("hipFuncSetAttribute(") + k.name + ", MaxDynamicSharedMemorySize, " + std::to_string(k.lds_limit) + "): " + hipGetErrorString(e);
                 return;
             }
         }
@@ -180,50 +194,76 @@ int prepare_kernels_on_device(std::string* why) {
     return BROV_OK;
 }
 
+// every solver launch: function and block size from the table (a failure is left as the runtime's last error, which every caller collects)
+static void launch(int id, int blocks, size_t lds_bytes, const DevParams& P, hipStream_t st) {
+    void* args[] = {(void*)&P};
+    (void)hipLaunchKernel((const void*)kKernels[id].fn, dim3(blocks), dim3(kKernels[id].threads), args, lds_bytes, st);
+}
+// blocks of kernel `id` the occupancy query grants a CU at this dynamic-LDS size (-1: the query failed)
+static int blocks_per_cu(int id, size_t lds_bytes) {
+    int per_cu = 0;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kKernels[id].fn, kKernels[id].threads, lds_bytes) == hipSuccess ? per_cu : -1;
+}
+
+// ---- which kernel a call runs: pure functions of the call's properties ----
+// fused kernels (N <= 23).  Several steps per launch: the variant a single step of this solver runs (two waves' code for short horizons), so
+// that the steps are the same code on the same data.  The mailbox tick (<= 64 instances) has the variant that delivers first, for the
+// uniform grid on one wave only.
+static int fused_kernel(bool grid, bool two_wave, bool mail_early, bool ticks) {
+    if (ticks) return two_wave ? K_FUSED_TICKS_W2 : K_FUSED_TICKS;
+    if (mail_early && !grid && !two_wave) return K_FUSED_MAIL;
+    return grid ? K_FUSED_GRID : two_wave ? K_FUSED_W2 : K_FUSED;
+}
+// windowed kernels.  pit: the parallel-in-time kernel launched AHEAD of the window kernel (K_NONE: none) -- its step-0 solve, whose completed
+// instances the resident kernel skips, or (feedback of a split tick) the four quarters rolled out at once from what the preparation parked.
+// The split launches are the resident mode's at every horizon.  long_h: 128 < N <= 256, interior-point vectors without register copies.
+struct WindowedKernels { int pit, win; };
+static WindowedKernels windowed_kernels(bool resident, int rti_split, bool grid, bool ticks, bool long_h, bool pit) {
+    if (resident || rti_split)
+        return {!pit ? K_NONE : rti_split == 2 ? (grid ? K_PIT_FB_GRID : K_PIT_FB) : (grid ? K_PIT_GRID : K_PIT),
+                rti_split ? (grid ? K_RES_SPLIT_GRID : K_RES_SPLIT) : (grid ? K_RES_GRID : K_RES)};
+    if (ticks) return {K_NONE, long_h ? K_WIN_LONG_TICKS : K_WIN_TICKS};
+    if (grid) return {K_NONE, long_h ? K_WIN_LONG_GRID : K_WIN_GRID};
+    return {K_NONE, long_h ? K_WIN_LONG : K_WIN};
+}
+
 void launch_linearise(const DevParams& P, hipStream_t st) {
     const int C = lin_chunk_len(P.N);
     const size_t lds = ((size_t)C * (kBaStage + NX + kRecInterval + NU) + (size_t)(C + 1) * NX + 64) * sizeof(double);
-    if (P.tsv) hipLaunchKernelGGL(lin_wave_kernel_grid, dim3(P.B * lin_chunks(P.N)), dim3(64), lds, st, P);
-    else hipLaunchKernelGGL(lin_wave_kernel, dim3(P.B * lin_chunks(P.N)), dim3(64), lds, st, P);
+    launch(P.tsv ? K_LIN_GRID : K_LIN, P.B * lin_chunks(P.N), lds, P, st);
 }
-
 void launch_qp(const DevParams& P, hipStream_t st) {
-    const int waves_per_block = 4;
-    const int blocks = (P.B + waves_per_block - 1) / waves_per_block;
-    hipLaunchKernelGGL(qp_kernel, dim3(blocks), dim3(64 * waves_per_block), 0, st, P);
+    const int waves_per_block = kKernels[K_QP].threads / 64;
+    launch(K_QP, (P.B + waves_per_block - 1) / waves_per_block, 0, P, st);
 }
 
 bool fused_supported(int N) { return N <= kFusedMaxN; }
 int sched_buffer_ints_host(int B) { return (sched_buffer_ints(B) + 31) & ~31; }
 
 static size_t windowed_lds_bytes(int L) { return ((size_t)win_off_const(L) + 2 + 17) * sizeof(double); }
+static bool windowed_resident(int L) { return L > kWinMaxStages; }
+bool windowed_is_resident(int win_L) { return windowed_resident(win_L); }
+size_t windowed_ws_doubles(int N, int L) { return win_ws_doubles(N, L); }
+// the whole horizon as ONE window of the resident kernels: its LDS slice must fit a CU's 160 KB
+static bool resident_fits(int N) { return windowed_lds_bytes(N) <= 160 * 1024; }
 // stages per window.  Large batches: windows of <= 20 stages, four blocks per CU.  Batches of at most one instance per CU (the ROS
-// node's batch of one, small Monte-Carlo sets): RESIDENT mode -- one window = the whole horizon in a slice of up to 160 KB, one
-// block per CU: no parking, no window fetches (N <= 80 fits)
-int windowed_stage_count(int N, int B) {
-    int dev = 0, cus = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const bool no_resident = getenv("BROV_DEV_NO_RESIDENT") && atoi(getenv("BROV_DEV_NO_RESIDENT")) != 0;   // development knob (tests)
-    if (!no_resident && N > kWinMaxStages && B <= cus && windowed_lds_bytes(N) <= 160 * 1024) return N;
+// node's batch of one, small Monte-Carlo sets): RESIDENT mode -- one window = the whole horizon, one block per CU: no parking, no
+// window fetches
+int windowed_stage_count(int N, int B, int cus, const DevKnobs& k) {
+    if (!k.no_resident && N > kWinMaxStages && B <= cus && resident_fits(N)) return N;
     return win_len(N);
 }
-size_t windowed_ws_doubles(int N, int L) { return win_ws_doubles(N, L); }
-static bool windowed_resident(int L) { return L > kWinMaxStages; }
-int windowed_blocks(int N, int B, int L) {
-    int dev = 0, cus = 256, per_cu = 4;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)N;
-    const void* fn = windowed_resident(L) ? (const void*)rti_window_kernel_res : (const void*)rti_window_kernel;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, windowed_resident(L) ? 256 : 64, windowed_lds_bytes(L)) != hipSuccess || per_cu < 1)
-        per_cu = windowed_resident(L) ? 1 : 4;
+// persistent blocks of a windowed launch: what the device holds at once, at most one per instance
+int windowed_blocks(int B, int L, int cus, const DevKnobs& k) {
+    const bool res = windowed_resident(L);
+    int per_cu = blocks_per_cu(windowed_kernels(res, 0, false, false, false, false).win, windowed_lds_bytes(L));
+    if (per_cu < 1) per_cu = res ? 1 : 4;
     long long fit = (long long)cus * per_cu;
     // development knob (tests/test_gpu_windowed.py): fewer persistent blocks, so that small batches take several instances per block
-    if (const char* e = getenv("BROV_DEV_WIN_BLOCKS")) { const long long v = atoll(e); if (v >= 1 && v < fit) fit = v; }
+    if (k.win_blocks >= 1 && k.win_blocks < fit) fit = k.win_blocks;
     return (int)(B < fit ? B : fit);
 }
-// Batches between one and two instances per CU at 48 <= N <= 80: as long as the parallel-in-time kernel can serve a solve (no dumped linearisation,
+// Batches between one and two instances per CU at N >= 48: as long as the parallel-in-time kernel can serve a solve (no dumped linearisation,
 // BROV_PIT != 0) it runs ONE BLOCK PER INSTANCE -- a CU's second block follows its first -- with the resident kernel behind it for what
 // it leaves, instead of the windowed kernel: 512 instances at N = 80 take 0.154 ms against 0.192 ms (N = 60: 0.135 / ~0.153; N = 40:
 // 0.120 / 0.114 -- hence the lower limit; scripts/dev/mid_batch_rate.py).  What the parallel kernel leaves (instances with many active
@@ -232,48 +272,25 @@ int windowed_blocks(int N, int B, int L) {
 // (BROV_PIT_ROUNDS=0 keeps the windowed kernel altogether).  Decided per solve: the solver is created for the windowed kernel and with a
 // workspace that serves either.  Returns the resident stage count (= N) or 0.
 constexpr int kPitRounds = 2, kPitRoundsMinN = 48;
-int pit_rounds_stages(int N, int B) {
-    int dev = 0, cus = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const bool off = (getenv("BROV_PIT_ROUNDS") && atoi(getenv("BROV_PIT_ROUNDS")) == 0) || (getenv("BROV_DEV_NO_RESIDENT") && atoi(getenv("BROV_DEV_NO_RESIDENT")) != 0);
-    return (!off && B > cus && B <= kPitRounds * cus && N >= kPitRoundsMinN && pit_supported(N, N)) ? N : 0;
+int pit_rounds_stages(int N, int B, int cus, const DevKnobs& k) {
+    return (k.pit_rounds && !k.no_resident && B > cus && B <= kPitRounds * cus && N >= kPitRoundsMinN && pit_supported(N, N)) ? N : 0;
 }
+// the parallel-in-time kernel serves the resident configuration of a horizon whose LDS slice has room for its own 244 doubles as well
 bool pit_supported(int N, int win_L) {
-    return windowed_resident(win_L) && win_L == N && N >= 24 && N <= 80 && windowed_lds_bytes(win_L) + kPitExtraDoubles * sizeof(double) <= 160 * 1024;
+    return windowed_resident(win_L) && win_L == N && N >= 24 && windowed_lds_bytes(win_L) + kPitExtraDoubles * sizeof(double) <= 160 * 1024;
 }
-void launch_windowed(const DevParams& P, hipStream_t st) {
-    // development knob, read once per process: the long-horizon instantiations (interior-point vectors without register copies) at every horizon (A/B)
-    static const bool force_long = getenv("BROV_DEV_WIN_LONG") && atoi(getenv("BROV_DEV_WIN_LONG")) != 0;
-    const bool long_h = P.N > BROV_MAX_N_LDS || force_long;
-    if (windowed_resident(P.win_L) || P.rti_split) {   // (the split launches are the resident mode's at every horizon)
-        if (P.pit && P.pit_done && P.rti_split == 2) {   // feedback of a split tick: the quarters rolled out at once from what the preparation parked
-            if (P.tsv) hipLaunchKernelGGL(rti_pit_kernel_fb_grid, dim3(P.pit_blocks), dim3(256), windowed_lds_bytes(P.win_L) + kPitExtraDoubles * sizeof(double), st, P);
-            else hipLaunchKernelGGL(rti_pit_kernel_fb, dim3(P.pit_blocks), dim3(256), windowed_lds_bytes(P.win_L) + kPitExtraDoubles * sizeof(double), st, P);
-        } else if (P.pit && P.pit_done) {   // parallel-in-time step-0 solve first; the resident kernel skips what it completed
-            // (pit_blocks = B where every instance has a workspace of its own: beyond one instance per CU the blocks queue for the CUs)
-            if (P.tsv) hipLaunchKernelGGL(rti_pit_kernel_grid, dim3(P.pit_blocks), dim3(256), windowed_lds_bytes(P.win_L) + kPitExtraDoubles * sizeof(double), st, P);
-            else hipLaunchKernelGGL(rti_pit_kernel, dim3(P.pit_blocks), dim3(256), windowed_lds_bytes(P.win_L) + kPitExtraDoubles * sizeof(double), st, P);
-        }
-        if (P.rti_split && P.tsv) hipLaunchKernelGGL(rti_window_kernel_res_split_grid, dim3(P.win_blocks), dim3(256), windowed_lds_bytes(P.win_L), st, P);
-        else if (P.rti_split) hipLaunchKernelGGL(rti_window_kernel_res_split, dim3(P.win_blocks), dim3(256), windowed_lds_bytes(P.win_L), st, P);
-        else if (P.tsv) hipLaunchKernelGGL(rti_window_kernel_res_grid, dim3(P.win_blocks), dim3(256), windowed_lds_bytes(P.win_L), st, P);
-        else hipLaunchKernelGGL(rti_window_kernel_res, dim3(P.win_blocks), dim3(256), windowed_lds_bytes(P.win_L), st, P);
-    }
-    else if (P.ticks > 0) {
-        if (long_h) hipLaunchKernelGGL(rti_window_kernel_long_ticks, dim3(P.win_blocks), dim3(64), windowed_lds_bytes(P.win_L), st, P);
-        else hipLaunchKernelGGL(rti_window_kernel_ticks, dim3(P.win_blocks), dim3(64), windowed_lds_bytes(P.win_L), st, P);
-    }
-    else if (P.tsv && long_h) hipLaunchKernelGGL(rti_window_kernel_long_grid, dim3(P.win_blocks), dim3(64), windowed_lds_bytes(P.win_L), st, P);
-    else if (P.tsv) hipLaunchKernelGGL(rti_window_kernel_grid, dim3(P.win_blocks), dim3(64), windowed_lds_bytes(P.win_L), st, P);
-    else if (long_h) hipLaunchKernelGGL(rti_window_kernel_long, dim3(P.win_blocks), dim3(64), windowed_lds_bytes(P.win_L), st, P);
-    else hipLaunchKernelGGL(rti_window_kernel, dim3(P.win_blocks), dim3(64), windowed_lds_bytes(P.win_L), st, P);
+// the variant follows what the plan left in P: resident configuration (win_L), split half, grid, steps per launch, parallel-in-time kernel ahead
+void launch_windowed(const DevParams& P, hipStream_t st, const DevKnobs& k) {
+    const WindowedKernels w = windowed_kernels(windowed_resident(P.win_L), P.rti_split, P.tsv != nullptr, P.ticks > 0,
+                                               P.N > BROV_MAX_N_LDS || k.win_long, P.pit && P.pit_done);
+    const size_t lds = windowed_lds_bytes(P.win_L);
+    // (pit_blocks = B where every instance has a workspace of its own: beyond one instance per CU the blocks queue for the CUs)
+    if (w.pit != K_NONE) launch(w.pit, P.pit_blocks, lds + kPitExtraDoubles * sizeof(double), P, st);
+    launch(w.win, P.win_blocks, lds, P, st);
 }
-bool windowed_is_resident(int win_L) { return windowed_resident(win_L); }
 // the split launches (rti_phase 1 / 2) of the resident kernel at a horizon the FUSED kernels serve in one call (N <= 23): the four quarters the
 // block's waves linearise must all hold a stage
-bool split_resident_horizon(int N) { return N >= 4 && 3 * ((N + 3) >> 2) < N && windowed_lds_bytes(N) <= 160 * 1024; }
-
+bool split_resident_horizon(int N) { return N >= 4 && 3 * ((N + 3) >> 2) < N && resident_fits(N); }
 
 static size_t fused_lds_bytes(int N) { return ((size_t)N * (kBaStage + NX + kKtStage + 4 + 4 + 4) + 2 * (size_t)(N + 1) * NX + 2 + 17) * sizeof(double); }
 static bool fused_two_wave(size_t lds, int force) {   // force: DevKnobs::fused_waves (development knob)
@@ -283,43 +300,16 @@ static bool fused_two_wave(size_t lds, int force) {   // force: DevKnobs::fused_
 // per CU, threads per block, 1 fused / 2 fused two-wave / 3 windowed / 4 windowed resident}.  For bench.py's horizon sweep (the
 // "LDS-occupancy crossover" of BASELINE configs[4]): which horizon still fits four instances into a CU's 160 KB.
 void lds_kernel_info(int N, int win_L, bool windowed, int32_t info[4], const DevKnobs& k) {
-    const void* fn;
-    size_t lds;
-    int threads = 64, kind;
-    if (windowed) {
-        lds = windowed_lds_bytes(win_L);
-        const bool res = windowed_resident(win_L);
-        fn = res ? (const void*)rti_window_kernel_res : (const void*)rti_window_kernel;
-        threads = res ? 256 : 64;
-        kind = res ? 4 : 3;
-    } else {
-        lds = fused_lds_bytes(N);
-        const bool w2 = fused_two_wave(lds, k.fused_waves);
-        fn = w2 ? (const void*)rti_fused_kernel_w2 : (const void*)rti_fused_kernel;
-        kind = w2 ? 2 : 1;
-    }
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, lds) != hipSuccess) per_cu = -1;
-    info[0] = (int32_t)lds; info[1] = per_cu; info[2] = threads; info[3] = kind;
+    const bool res = windowed_resident(win_L);
+    const size_t lds = windowed ? windowed_lds_bytes(win_L) : fused_lds_bytes(N);
+    const bool w2 = !windowed && fused_two_wave(lds, k.fused_waves);
+    const int id = windowed ? windowed_kernels(res, 0, false, false, false, false).win : fused_kernel(false, w2, false, false);
+    info[0] = (int32_t)lds; info[1] = blocks_per_cu(id, lds); info[2] = kKernels[id].threads; info[3] = windowed ? (res ? 4 : 3) : (w2 ? 2 : 1);
 }
-void launch_fused_ticks(const DevParams& P, hipStream_t st, const DevKnobs& k) {
-    const size_t lds = fused_lds_bytes(P.N);
-    // the variant a single step of this solver runs (two waves per SIMD for short horizons): the steps are then the same code on the same data
-    if (fused_two_wave(lds, k.fused_waves)) hipLaunchKernelGGL(rti_fused_kernel_ticks_w2, dim3(P.B), dim3(64), lds + (size_t)k.lds_pad, st, P);
-    else hipLaunchKernelGGL(rti_fused_kernel_ticks, dim3(P.B), dim3(64), lds + (size_t)k.lds_pad, st, P);
-}
+// one block per instance; development knobs (scripts/dev/occupancy_probe.py): pad the LDS request / force a variant (1, 2; default by LDS size)
 void launch_fused(const DevParams& P, hipStream_t st, const DevKnobs& k) {
     const size_t lds = fused_lds_bytes(P.N);
-    // development knobs (scripts/dev/occupancy_probe.py): pad the LDS request / force a variant (1, 2; default by LDS size)
-    const size_t pad = (size_t)k.lds_pad;
-    const bool w2 = fused_two_wave(lds, k.fused_waves);
-    if (P.mail && P.mail_early && !P.tsv && !w2) {   // mailbox tick (<= 64 instances): the variant that delivers first
-        hipLaunchKernelGGL(rti_fused_kernel_mail, dim3(P.B), dim3(64), lds + pad, st, P);
-        return;
-    }
-    if (P.tsv) hipLaunchKernelGGL(rti_fused_kernel_grid, dim3(P.B), dim3(64), lds + pad, st, P);
-    else if (w2) hipLaunchKernelGGL(rti_fused_kernel_w2, dim3(P.B), dim3(64), lds + pad, st, P);
-    else hipLaunchKernelGGL(rti_fused_kernel, dim3(P.B), dim3(64), lds + pad, st, P);
+    launch(fused_kernel(P.tsv != nullptr, fused_two_wave(lds, k.fused_waves), P.mail && P.mail_early, P.ticks > 0), P.B, lds + (size_t)k.lds_pad, P, st);
 }
 
 }  // namespace brov
