@@ -1,15 +1,14 @@
 // ekf_kernel.hip -- batched EKF disturbance observer and its C ABI (include/bluerov2_nmpc.h,
 // brov_ekf_*).  B independent copies of the reference's 18-state filter BLUEROV2_DOB::EKF()
-// (/root/reference/bluerov2_dobmpc/src/bluerov2_dob.cpp:495-545): forward-difference Jacobians of the RK4 map (:730-744, RK4
+// (bluerov2_dobmpc/src/bluerov2_dob.cpp:495-545 of the reference): forward-difference Jacobians of the RK4 map (:730-744, RK4
 // with the k2/3 stage quirk :621-634, process model :637-702) and of the measurement model (:705-727, :747-762), Kalman gain
 // through the explicit inverse of the innovation covariance, Joseph-form covariance update, world-frame disturbance, and the
 // hand-over to the NMPC parameters p[0..3] (:334-337).
 //
 // One kernel, ekf_update_kernel_sp: one filter per 16-lane DPP row, right-hand rows of the products broadcast out of registers with
 // v_fmac_f64_dpp row_newbcast, only the non-zero pattern of the finite-difference Jacobians multiplied, 16 evaluations of the RK4 map
-// in one pass, two LDS buffers, two waves per SIMD -- see the comments in front of the DPP helpers and of the kernel.  DESIGN.md
-// section 4.4 has the history and the measurements of the two kernels it replaced (first an LDS-broadcast kernel, then a dense DPP
-// kernel); their code is in commit d7af66b.
+// in one pass, two LDS buffers, two waves per SIMD -- see the comments in front of the DPP helpers and of the kernel; DESIGN.md
+// section 4.4 has the history and the measurements.
 // 18 does not fit the 16-wide FP64 MFMA tile (a 32x32 padding would waste 3/4 of the issue slots, and FP64 MFMA has the same flop
 // rate as FP64 VALU on this part), so the filter runs on the VALU with one lane per matrix row; the lane that perturbs state r in
 // the finite differences ends up holding column r of the Jacobian, i.e. row r of its transpose, and the products are arranged so
@@ -144,23 +143,28 @@ __device__ __forceinline__ void pin_rows(const Rows& Rc) {
     asm volatile("s_nop 1");
 }
 
-// C += A B.  B in row layout (registers); ap(k) / as(k) deliver A[l][k] and A[16+l][k] of this lane (as(k) = 0 for l >= 2).
+// C += A B over the non-zero pattern NZ of B (NZ::at(row of B, column); NzAll: dense).  B in row layout (registers); ap(k) / as(k)
+// deliver A[l][k] and A[16+l][k] of this lane (as(k) = 0 for l >= 2).
 // The A elements of a block of k's are requested (LDS) before the fmacs of the previous block are issued.
 // CORNER: only columns 16, 17 of the secondary rows are accumulated -- for a symmetric result the rest of rows 16, 17 is
 // columns 16, 17 of the primary rows.
-template <int K0, int NK, bool SECB, bool CORNER>
+struct NzAll { static constexpr bool at(int, int) { return true; } };
+template <class NZ, int K0, int NK, bool SECB, bool CORNER>
 __device__ __forceinline__ void gemm_block(Rows& C, const Rows& B, const double (&a0)[NK], const double (&a1)[NK]) {
     for_k(std::make_integer_sequence<int, NK>{}, [&](auto kc) {
         constexpr int KK = decltype(kc)::value;
-        constexpr int K = K0 + KK;            // lane that owns the B row
-#pragma unroll
-        for (int j = 0; j < EN; j++) {
-            fmac_bc<K>(C.p[j], SECB ? B.s[j] : B.p[j], a0[KK]);
-            if (!CORNER || j >= 16) fmac_bc<K>(C.s[j], SECB ? B.s[j] : B.p[j], a1[KK]);
-        }
+        constexpr int K = K0 + KK;                 // lane that owns the B row
+        constexpr int ROW = SECB ? 16 + K : K;     // the row's index in B
+        for_k(std::make_integer_sequence<int, EN>{}, [&](auto jc) {
+            constexpr int J = decltype(jc)::value;
+            if constexpr (NZ::at(ROW, J)) {
+                fmac_bc<K>(C.p[J], SECB ? B.s[J] : B.p[J], a0[KK]);
+                if constexpr (!CORNER || J >= 16) fmac_bc<K>(C.s[J], SECB ? B.s[J] : B.p[J], a1[KK]);
+            }
+        });
     });
 }
-template <bool CORNER = false, class AP, class AS>
+template <class NZ, bool CORNER = false, class AP, class AS>
 __device__ __forceinline__ void gemm_dpp(Rows& C, const Rows& B, AP ap, AS as) {
     double p0[6], s0[6], p1[6], s1[6];
 #pragma unroll
@@ -168,56 +172,63 @@ __device__ __forceinline__ void gemm_dpp(Rows& C, const Rows& B, AP ap, AS as) {
 #pragma unroll
     for (int k = 0; k < 6; k++) { p1[k] = ap(6 + k); s1[k] = as(6 + k); }
     pin_rows(B);
-    gemm_block<0, 6, false, CORNER>(C, B, p0, s0);
+    gemm_block<NZ, 0, 6, false, CORNER>(C, B, p0, s0);
 #pragma unroll
     for (int k = 0; k < 4; k++) { p0[k] = ap(12 + k); s0[k] = as(12 + k); }
     p0[4] = ap(16); s0[4] = as(16); p0[5] = ap(17); s0[5] = as(17);
-    gemm_block<6, 6, false, CORNER>(C, B, p1, s1);
+    gemm_block<NZ, 6, 6, false, CORNER>(C, B, p1, s1);
     {
         const double q0[4] = {p0[0], p0[1], p0[2], p0[3]}, q1[4] = {s0[0], s0[1], s0[2], s0[3]};
-        gemm_block<12, 4, false, CORNER>(C, B, q0, q1);
+        gemm_block<NZ, 12, 4, false, CORNER>(C, B, q0, q1);
         const double r0[2] = {p0[4], p0[5]}, r1[2] = {s0[4], s0[5]};
-        gemm_block<0, 2, true, CORNER>(C, B, r0, r1);
+        gemm_block<NZ, 0, 2, true, CORNER>(C, B, r0, r1);
     }
 }
-// Symmetric result computed with CORNER = true: rows 16, 17 (secondary set of lanes 0, 1), columns 0..15, are columns 16, 17 of
-// the primary rows -- lane 0 / 1 gathers them with 2 x 16 row broadcasts instead of 2 x 16 x 18 fmacs issued for two lanes.
-// Lanes >= 2 receive lane 1's values (their secondary set is never read) -- one select per element.
-__device__ __forceinline__ void fill_secondary_from_symmetry(Rows& C, int l) {
-    for_k(std::make_integer_sequence<int, 16>{}, [&](auto jc) {
-        constexpr int J = decltype(jc)::value;
-        const double t16 = bcast<J>(C.p[16]), t17 = bcast<J>(C.p[17]);
-        C.s[J] = (l == 0) ? t16 : t17;
-    });
-}
-// C += A B for a SYMMETRIC right operand B, secondary rows of C done the cheap way: C[16+r][j] = sum_k A[16+r][k] B[k][j] and
-// B[k][j] = B[j][k] is element k of the row lane j owns, so lane j computes C[16][j] and C[17][j] with 2 x 18 fmacs on its own
-// registers (a16(k), a17(k): rows 16, 17 of A, identical for the 16 lanes of a filter), then lanes 0 / 1 gather their rows with
-// row broadcasts.  Columns 16, 17 of those rows use B's secondary rows (lanes 0, 1).  init16 / init17: C[16][j], C[17][j] to add to.
-template <class AP, class A16, class A17>
-__device__ __forceinline__ void gemm_dpp_symB(Rows& C, const Rows& B, AP ap, A16 a16, A17 a17, int l) {
-    gemm_dpp<true>(C, B, ap, [&](int) { return 0.0; });     // primary rows; the secondary set is rebuilt below
-    double c16 = 0.0, c17 = 0.0, d16[2] = {0.0, 0.0}, d17[2] = {0.0, 0.0};
-#pragma unroll
-    for (int k = 0; k < EN; k++) {
-        const double x16 = a16(k), x17 = a17(k);
-        c16 = fma(x16, B.p[k], c16);          // lane j < 16: column j of rows 16 / 17
-        c17 = fma(x17, B.p[k], c17);
-        // columns 16, 17: B[k][16 + m] = B[16 + m][k] = B.s[k] of lane m
-        d16[0] = fma(x16, B.s[k], d16[0]);    // valid in lanes 0 (column 16) and 1 (column 17)
-        d17[0] = fma(x17, B.s[k], d17[0]);
-    }
+// Rows 16, 17 of C (secondary set of lanes 0, 1) out of per-lane values: lane j < 16 holds c16 = C[16][j], c17 = C[17][j], lane 0 / 1
+// gathers its row with 2 x 16 row broadcasts.  Lanes >= 2 receive lane 1's values (their secondary set is never read) -- one
+// select per element.
+__device__ __forceinline__ void gather_secondary(Rows& C, double c16, double c17, int l) {
     for_k(std::make_integer_sequence<int, 16>{}, [&](auto jc) {
         constexpr int J = decltype(jc)::value;
         const double t16 = bcast<J>(c16), t17 = bcast<J>(c17);
         C.s[J] = (l == 0) ? t16 : t17;
     });
-    {   // corner: lane 0 needs C[16][16] (its own d16), C[16][17] (lane 1's d16); lane 1 needs C[17][16] (lane 0's d17), C[17][17]
-        const double e16_0 = bcast<0>(d16[0]), e16_1 = bcast<1>(d16[0]), e17_0 = bcast<0>(d17[0]), e17_1 = bcast<1>(d17[0]);
-        C.s[16] = (l == 0) ? e16_0 : e17_0;
-        C.s[17] = (l == 0) ? e16_1 : e17_1;
-    }
-    (void)d16[1]; (void)d17[1];
+}
+// ... and their 2x2 corner: lane m < 2 holds d16 = C[16][16 + m], d17 = C[17][16 + m]; lane 0 needs C[16][16] (its own d16) and
+// C[16][17] (lane 1's d16), lane 1 needs C[17][16] (lane 0's d17) and C[17][17]
+__device__ __forceinline__ void gather_corner(Rows& C, double d16, double d17, int l) {
+    const double e16_0 = bcast<0>(d16), e16_1 = bcast<1>(d16), e17_0 = bcast<0>(d17), e17_1 = bcast<1>(d17);
+    C.s[16] = (l == 0) ? e16_0 : e17_0;
+    C.s[17] = (l == 0) ? e16_1 : e17_1;
+}
+// Symmetric result computed with CORNER = true: rows 16, 17, columns 0..15, are columns 16, 17 of the primary rows -- gathered
+// instead of 2 x 16 x 18 fmacs issued for two lanes.
+__device__ __forceinline__ void fill_secondary_from_symmetry(Rows& C, int l) { gather_secondary(C, C.p[16], C.p[17], l); }
+// Rows 16, 17 of C = A B for a SYMMETRIC right operand B, done the cheap way: C[16+r][j] = sum_k A[16+r][k] B[k][j] and
+// B[k][j] = B[j][k] is element k of the row lane j owns, so lane j computes C[16][j] and C[17][j] with 2 x 18 fmacs on its own
+// registers (a16(k), a17(k): rows 16, 17 of A, identical for the 16 lanes of a filter; k arrives as an integral_constant), then
+// lanes 0 / 1 gather their rows with row broadcasts.  Columns 16, 17 of those rows use B's secondary rows (lanes 0, 1).
+// NZT: non-zero pattern of A's transpose -- A[16 + r][k] is multiplied where NZT::at(k, 16 + r).
+template <class NZT, class A16, class A17>
+__device__ __forceinline__ void sym_secondary(Rows& C, const Rows& B, A16 a16, A17 a17, int l) {
+    double c16 = 0.0, c17 = 0.0, d16 = 0.0, d17 = 0.0;
+    for_k(std::make_integer_sequence<int, EN>{}, [&](auto kc) {
+        constexpr int K = decltype(kc)::value;
+        if constexpr (NZT::at(K, 16)) c16 = fma(a16(kc), B.p[K], c16);   // lane j < 16: column j of rows 16 / 17
+        if constexpr (NZT::at(K, 17)) c17 = fma(a17(kc), B.p[K], c17);
+        // columns 16, 17: B[k][16 + m] = B[16 + m][k] = B.s[k] of lane m -- valid in lanes 0 (column 16) and 1 (column 17)
+        if constexpr (NZT::at(K, 16)) d16 = fma(a16(kc), B.s[K], d16);
+        if constexpr (NZT::at(K, 17)) d17 = fma(a17(kc), B.s[K], d17);
+    });
+    gather_secondary(C, c16, c17, l);
+    gather_corner(C, d16, d17, l);
+}
+// C += A B for a SYMMETRIC right operand B: primary rows by the product schedule; rows 16, 17 are REBUILT by sym_secondary (C's
+// secondary set on entry is taken as zero)
+template <class AP, class A16, class A17>
+__device__ __forceinline__ void gemm_dpp_symB(Rows& C, const Rows& B, AP ap, A16 a16, A17 a17, int l) {
+    gemm_dpp<NzAll, true>(C, B, ap, [&](int) { return 0.0; });
+    sym_secondary<NzAll>(C, B, a16, a17, l);
 }
 __device__ __forceinline__ void zero_rows(Rows& R) {
 #pragma unroll
@@ -303,43 +314,6 @@ __device__ __forceinline__ void ekf_rk4_fd(const EkfConst& c, const double (&x)[
     }
 }
 
-// C += A B over the non-zero pattern NZ of B (NZ::at(row of B, column)); otherwise gemm_block / gemm_dpp
-template <class NZ, int K0, int NK, bool SECB, bool CORNER>
-__device__ __forceinline__ void gemm_block_sp(Rows& C, const Rows& B, const double (&a0)[NK], const double (&a1)[NK]) {
-    for_k(std::make_integer_sequence<int, NK>{}, [&](auto kc) {
-        constexpr int KK = decltype(kc)::value;
-        constexpr int K = K0 + KK;                 // lane that owns the B row
-        constexpr int ROW = SECB ? 16 + K : K;     // the row's index in B
-        for_k(std::make_integer_sequence<int, EN>{}, [&](auto jc) {
-            constexpr int J = decltype(jc)::value;
-            if constexpr (NZ::at(ROW, J)) {
-                fmac_bc<K>(C.p[J], SECB ? B.s[J] : B.p[J], a0[KK]);
-                if constexpr (!CORNER || J >= 16) fmac_bc<K>(C.s[J], SECB ? B.s[J] : B.p[J], a1[KK]);
-            }
-        });
-    });
-}
-template <class NZ, bool CORNER = false, class AP, class AS>
-__device__ __forceinline__ void gemm_dpp_sp(Rows& C, const Rows& B, AP ap, AS as) {
-    double p0[6], s0[6], p1[6], s1[6];
-#pragma unroll
-    for (int k = 0; k < 6; k++) { p0[k] = ap(k); s0[k] = as(k); }
-#pragma unroll
-    for (int k = 0; k < 6; k++) { p1[k] = ap(6 + k); s1[k] = as(6 + k); }
-    pin_rows(B);
-    gemm_block_sp<NZ, 0, 6, false, CORNER>(C, B, p0, s0);
-#pragma unroll
-    for (int k = 0; k < 4; k++) { p0[k] = ap(12 + k); s0[k] = as(12 + k); }
-    p0[4] = ap(16); s0[4] = as(16); p0[5] = ap(17); s0[5] = as(17);
-    gemm_block_sp<NZ, 6, 6, false, CORNER>(C, B, p1, s1);
-    {
-        const double q0[4] = {p0[0], p0[1], p0[2], p0[3]}, q1[4] = {s0[0], s0[1], s0[2], s0[3]};
-        gemm_block_sp<NZ, 12, 4, false, CORNER>(C, B, q0, q1);
-        const double r0[2] = {p0[4], p0[5]}, r1[2] = {s0[4], s0[5]};
-        gemm_block_sp<NZ, 0, 2, true, CORNER>(C, B, r0, r1);
-    }
-}
-
 __global__ __launch_bounds__(64, 2) void ekf_update_kernel_sp(EkfArgs A) {
     extern __shared__ __attribute__((aligned(16))) double esm[];
     const EkfConst& c = A.c;
@@ -411,7 +385,7 @@ __global__ __launch_bounds__(64, 2) void ekf_update_kernel_sp(EkfArgs A) {
 #pragma unroll
         for (int j = 0; j < EN; j++) {
             const double v = (xb[j] - f0[j]) * idp;
-            Ft.p[j] = (j < 3 && l == j) ? fd[j < 3 ? j : 0] : v;
+            Ft.p[j] = (j < 3 && l == j) ? fd[j] : v;
             Ft.s[j] = (dpp32_f64<0x101>(xb[j]) - f0[j]) * ids;   // row_shl:1 -- lane 0 <- lane 1 (state 16), lane 1 <- lane 2 (state 17)
             x[j] = f0[j];                   // from here on x = x_pred
         }
@@ -421,7 +395,7 @@ __global__ __launch_bounds__(64, 2) void ekf_update_kernel_sp(EkfArgs A) {
     // G = P F^T
     Rows G;
     zero_rows(G);
-    gemm_dpp_sp<NzFt>(G, Ft, [&](int k) { return bufX[l * EN + k]; }, [&](int k) { return bufX[(16 + ls) * EN + k]; });
+    gemm_dpp<NzFt>(G, Ft, [&](int k) { return bufX[l * EN + k]; }, [&](int k) { return bufX[(16 + ls) * EN + k]; });
     store_rows(bufY, Ft, l);                // F^T row-major: F[l][k] = bufY[k][l]
     __syncthreads();                        // (also: the reads of P are done, bufX is free)
     // P_pred = F G + Q.  F[l][k] is zero for k < 3 except on the diagonal (own-lane multiply-add), rows 16 / 17 of F are e_16 / e_17
@@ -433,7 +407,7 @@ __global__ __launch_bounds__(64, 2) void ekf_update_kernel_sp(EkfArgs A) {
 #pragma unroll
         for (int k = 0; k < 15; k++) a[k] = bufY[(3 + k) * EN + l];
         const double fdl = bufY[l * EN + l], a16 = bufY[16 * EN + 16 + ls], a17 = bufY[17 * EN + 16 + ls];
-        const double fd3 = (l < 3) ? fdl : 0.0, s16 = a16, s17 = a17;
+        const double fd3 = (l < 3) ? fdl : 0.0;
 #pragma unroll
         for (int j = 0; j < EN; j++) Pq.p[j] = fma(fd3, G.p[j], Pq.p[j]);
         pin_rows(G);
@@ -444,10 +418,10 @@ __global__ __launch_bounds__(64, 2) void ekf_update_kernel_sp(EkfArgs A) {
         });
 #pragma unroll
         for (int j = 0; j < EN; j++) fmac_bc<0>(Pq.p[j], G.s[j], a[13]);
-        fmac_bc<0>(Pq.s[16], G.s[16], s16); fmac_bc<0>(Pq.s[17], G.s[17], s16);
+        fmac_bc<0>(Pq.s[16], G.s[16], a16); fmac_bc<0>(Pq.s[17], G.s[17], a16);
 #pragma unroll
         for (int j = 0; j < EN; j++) fmac_bc<1>(Pq.p[j], G.s[j], a[14]);
-        fmac_bc<1>(Pq.s[16], G.s[16], s17); fmac_bc<1>(Pq.s[17], G.s[17], s17);
+        fmac_bc<1>(Pq.s[16], G.s[16], a17); fmac_bc<1>(Pq.s[17], G.s[17], a17);
     }
     fill_secondary_from_symmetry(Pq, l);    // P_pred is symmetric: only the 2x2 corner of rows 16, 17 was accumulated
     store_rows(bufX, Pq, l);                // P_pred stays in bufX (right operand of V = J P_pred)
@@ -498,32 +472,15 @@ __global__ __launch_bounds__(64, 2) void ekf_update_kernel_sp(EkfArgs A) {
         });
 #pragma unroll
         for (int j = 0; j < EN; j++) W.p[j] = fma(hd, Pq.p[j], W.p[j]);
-        // rows 16, 17 through the symmetry of P_pred, as gemm_dpp_symB does it: lane j computes W[16][j], W[17][j] from its own row
-        double c16 = 0.0, c17 = 0.0, d16 = 0.0, d17 = 0.0;
-        for_k(std::make_integer_sequence<int, 12>{}, [&](auto kc) {
-            constexpr int K = decltype(kc)::value;
-            if constexpr (ekf_h21col(K)) {
-                constexpr int Q = ekf_h21idx(K);
-                c16 = fma(h16[Q], Pq.p[K], c16); c17 = fma(h17[Q], Pq.p[K], c17);
-                d16 = fma(h16[Q], Pq.s[K], d16); d17 = fma(h17[Q], Pq.s[K], d17);
-            }
-        });
-        c16 = fma(hd16, Pq.p[16], c16); d16 = fma(hd16, Pq.s[16], d16);
-        c17 = fma(hd17, Pq.p[17], c17); d17 = fma(hd17, Pq.s[17], d17);
-        for_k(std::make_integer_sequence<int, 16>{}, [&](auto jc) {
-            constexpr int J = decltype(jc)::value;
-            const double t16 = bcast<J>(c16), t17 = bcast<J>(c17);
-            W.s[J] = (l == 0) ? t16 : t17;
-        });
-        const double e16_0 = bcast<0>(d16), e16_1 = bcast<1>(d16), e17_0 = bcast<0>(d17), e17_1 = bcast<1>(d17);
-        W.s[16] = (l == 0) ? e16_0 : e17_0;
-        W.s[17] = (l == 0) ? e16_1 : e17_1;
+        // rows 16, 17 through the symmetry of P_pred
+        sym_secondary<NzHt>(W, Pq, [&](auto kc) { if constexpr (kc == 16) return hd16; else return h16[ekf_h21idx(kc)]; },
+                            [&](auto kc) { if constexpr (kc == 17) return hd17; else return h17[ekf_h21idx(kc)]; }, l);
     }
     // S = W H^T + R.  The left operand's elements W[l][k], W[16 + l][k] are this lane's own rows: W never goes through LDS
     Rows S;
 #pragma unroll
     for (int j = 0; j < EN; j++) { S.p[j] = (j == l) ? c.R : 0.0; S.s[j] = (sec && j == 16 + l) ? c.R : 0.0; }
-    gemm_dpp_sp<NzHt, true>(S, Ht, [&](int k) { return W.p[k]; }, [&](int k) { return W.s[k]; });
+    gemm_dpp<NzHt, true>(S, Ht, [&](int k) { return W.p[k]; }, [&](int k) { return W.s[k]; });
     fill_secondary_from_symmetry(S, l);     // S is symmetric
     // ---- K^T = S^-1 W by Gauss-Jordan on [S | W] without pivoting (S is SPD); the pivot row is broadcast with DPP.
     Rows& T = W;                            // Gauss-Jordan on [S | W] in place
@@ -561,7 +518,7 @@ __global__ __launch_bounds__(64, 2) void ekf_update_kernel_sp(EkfArgs A) {
         constexpr int JJ = decltype(jc)::value;
         if constexpr (ekf_h21col(JJ)) { hp[ekf_h21idx(JJ)] = bufY[JJ * EN + l]; hs[ekf_h21idx(JJ)] = bufY[JJ * EN + 16 + ls]; }
     });
-    const double hdJ = bufY[l * EN + l], hsdJ = bufY[(16 + ls) * EN + 16 + ls];
+    const double hd = bufY[l * EN + l], hsd = bufY[(16 + ls) * EN + 16 + ls];
     __syncthreads();                        // reads of bufY (H^T) are done
     store_rows(bufY, T, l);                 // K^T row-major: Kal[l][k] = bufY[k][l]
     __syncthreads();
@@ -583,7 +540,6 @@ __global__ __launch_bounds__(64, 2) void ekf_update_kernel_sp(EkfArgs A) {
     Rows J;
     zero_rows(J);
     {
-        const double hd = hdJ, hsd = hsdJ;
         double a0[EN], a1[EN];
 #pragma unroll
         for (int k = 0; k < EN; k++) { a0[k] = -bufY[k * EN + l]; a1[k] = -bufY[k * EN + 16 + ls]; }
@@ -633,10 +589,10 @@ __global__ __launch_bounds__(64, 2) void ekf_update_kernel_sp(EkfArgs A) {
     {
         Rows Jt;
         load_rows_t(bufX, Jt, l);
-        gemm_dpp<true>(Pn, Jt, [&](int k) { return V.p[k]; }, [&](int k) { return V.s[k]; });
+        gemm_dpp<NzAll, true>(Pn, Jt, [&](int k) { return V.p[k]; }, [&](int k) { return V.s[k]; });
         Rows Kt;
         load_rows(bufY, Kt, l);
-        gemm_dpp<true>(Pn, Kt, [&](int k) { return c.R * bufY[k * EN + l]; }, [&](int k) { return c.R * bufY[k * EN + 16 + ls]; });
+        gemm_dpp<NzAll, true>(Pn, Kt, [&](int k) { return c.R * bufY[k * EN + l]; }, [&](int k) { return c.R * bufY[k * EN + 16 + ls]; });
     }
     if (live) {   // P_new is symmetric: rows 16, 17 are columns 16, 17 of the primary rows (+ the 2x2 corner from lanes 0, 1)
         double* pg = A.P + (size_t)inst * kMat;
