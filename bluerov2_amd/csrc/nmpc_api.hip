@@ -3,6 +3,7 @@
 // usable HIP device every entry point fails with BROV_ERR_NO_DEVICE.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstddef>
 #include <cstdio>
 #include <cstdlib>
@@ -988,6 +989,89 @@ struct LoopLogs {
         return rc;
     }
 };
+// DEVICE logs of a run of consecutive ticks, entry j = tick j of the run (x: the plant state AFTER it); a null block is not logged.  The
+// whole-loop logs of brov_closed_loop_ex / _dob and the one-chunk logs of brov_closed_loop_track are both handed to the tick runners so.
+struct TickLogs {
+    size_t B = 0;
+    double *dx = nullptr, *du = nullptr, *dw = nullptr, *de = nullptr;
+    int* dst = nullptr;
+    double* x(int j) const { return dx ? dx + (size_t)j * B * 12 : nullptr; }
+    double* u(int j) const { return du ? du + (size_t)j * B * 4 : nullptr; }
+    double* w(int j) const { return dw ? dw + (size_t)j * B * 6 : nullptr; }
+    double* est(int j) const { return de ? de + (size_t)j * B * 6 : nullptr; }
+    int* status(int j) const { return dst ? dst + (size_t)j * B : nullptr; }
+};
+static TickLogs tick_logs(const LoopLogs& L) {
+    TickLogs T;
+    T.B = L.B; T.dx = L.x(1); T.du = L.du; T.dw = L.dw; T.de = L.de; T.dst = L.dst;
+    return T;
+}
+// whether brov_closed_loop_ex runs `ticks` ticks from `line0` as one launch, and with which kernel.
+// One launch for the whole loop where the fused kernels serve the solver and every window is rows of the table in place (round 5,
+// rti_fused_kernel_ticks with the plant update behind every step): every instance runs its own closed loop at its own pace -- no launch
+// boundaries, three launches per tick saved, and a tick on which one instance grinds through the QP loop holds nobody else.
+// (The fused and windowed *_ticks kernels integrate the plant themselves and know no wrench: with a wrench mode in force the loop takes
+// a launch per step.)
+static bool loop_in_one_launch(const brov_solver* s, int ticks, int line0, int ncols, int* which) {
+    *which = ticks_kernel(s);
+    return s->k.closed_loop_fused && ncols == 16 && line0 >= 0 && line0 + (ticks - 1) + s->N <= s->traj_rows - 1 && *which != 0 &&
+           s->wr.mode == BROV_WRENCH_OFF;
+}
+// `n` ticks of the plain loop (window -> RTI step -> plant step) from trajectory row `line` on `st`, logged into T
+static int run_loop_ticks(brov_solver* s, int n, int line, int ncols, double dt, int substeps, bool one_launch, int which, const TickLogs& T,
+                          hipStream_t st) {
+    const size_t B = s->B;
+    int rc = BROV_OK;
+    if (one_launch) {
+        rc = brov_set_yref_from_traj(s, line, 16, st);
+        if (rc == BROV_OK) rc = order_behind_last(s, st);
+        if (rc == BROV_OK) {
+            DevParams P = make_params(s, plan_solve(s, 0));
+            P.sched = nullptr;
+            P.ticks = n; P.tick_yref = 16; P.tick_status = T.status(0);
+            P.plant_pp = s->pplant; P.plant_rp = plant_rp(s); P.plant_rp_stride = plant_rp_stride(s); P.plant_substeps = substeps; P.plant_dt = dt;
+            P.x0_rw = s->x0; P.plant_xlog = T.x(0); P.plant_ulog = T.u(0);
+            if (s->timing) { hipEventRecord(s->ev[0], st); hipEventRecord(s->ev[1], st); }   // (as brov_solve_ticks: brov_last_solve_seconds then reports THIS launch)
+            launch_lds(s, P, which, st); s->prep_path = 0;
+            if (s->timing) { hipEventRecord(s->ev[2], st); s->ev_valid = true; }
+            s->traj_line = line + n - 1; s->yref_view = s->traj + (size_t)s->traj_line * 16;
+            s->wr_tick += n;
+        }
+    }
+    for (int k = 0; k < n && rc == BROV_OK && !one_launch; k++) {
+        forget_traj_window(s);
+        launch_window(s->traj, s->traj_rows, nullptr, line + k, 1, s->N, ncols, s->yref_sh, st);
+        s->yref_shared = true;
+        rc = brov_solve_phase(s, st, 0);
+        if (T.status(k)) hipLaunchKernelGGL(gather_status_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, s->res, T.status(k), (int)B);
+        plant_step_on(s, dt, substeps, T.x(k), T.u(k), T.w(k), st);
+    }
+    return rc;
+}
+// `n` ticks of the DOB / AMPC loop from trajectory row `line` on `st`: per tick the five public calls of the header.  The observer's and the
+// estimator's calls report through their own error strings: their code is handed on, their text copied behind `who`
+static int run_dob_ticks(brov_solver* s, brov_ekf* e, brov_rls* r, int rls_mode, int n, int line, int ncols, double dt, int substeps,
+                         const TickLogs& T, hipStream_t st, const char* who) {
+    const size_t B = s->B;
+    int rc = BROV_OK;
+    auto sub = [&](int code, const char* text) {
+        if (code != BROV_OK) { g_err = std::string(who) + ": " + text; rc = code; }
+        return code == BROV_OK;
+    };
+    for (int k = 0; k < n && rc == BROV_OK; k++) {
+        rc = brov_set_yref_from_traj(s, line + k, ncols, st);
+        if (rc == BROV_OK) rc = brov_solve_phase(s, st, 0);
+        if (rc != BROV_OK) break;
+        if (T.status(k)) hipLaunchKernelGGL(gather_status_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, s->res, T.status(k), (int)B);
+        ensure_plant_params(s, st);   // (the hand-off below rewrites the controller's stage 0, which a plant without parameters of its own follows)
+        plant_step_on(s, dt, substeps, T.x(k), T.u(k), T.w(k), st);
+        if (!sub(brov_ekf_update_from_solver(e, s, st), brov_ekf_last_error())) break;
+        if (T.est(k)) launch_gather_cols(brov_ekf_x_device(e), (int)B, 18, 12, 6, T.est(k), st);
+        if (!r) sub(brov_ekf_apply_to_solver(e, s, st), brov_ekf_last_error());
+        else if (sub(brov_rls_update_from_ekf(r, e, s, st), brov_rls_last_error())) sub(brov_rls_apply_to_solver(r, s, rls_mode, st), brov_rls_last_error());
+    }
+    return rc;
+}
 extern "C" int brov_closed_loop(brov_solver* s, int ticks, int line0, int ncols, double dt, int substeps, double* u_log, double* x_log,
                                 int32_t* st_log) {
     return brov_closed_loop_ex(s, ticks, line0, ncols, dt, substeps, u_log, x_log, st_log, nullptr);
@@ -1001,42 +1085,12 @@ extern "C" int brov_closed_loop_ex(brov_solver* s, int ticks, int line0, int nco
     if (int wrc = wrench_tick_ok(s, s->wr_tick + ticks - 1, "brov_closed_loop")) return wrc;
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = s->last_stream;
-    const size_t B = s->B;
     ensure_plant_params(s, st);
     LoopLogs L;
     int rc = L.begin(s, ticks, u_log, x_log, st_log, w_log, nullptr, st, "brov_closed_loop");
-    // One launch for the whole loop where the fused kernels serve the solver and every window is rows of the table in place (round 5,
-    // rti_fused_kernel_ticks with the plant update behind every step): every instance runs its own closed loop at its own pace -- no launch
-    // boundaries, three launches per tick saved, and a tick on which one instance grinds through the QP loop holds nobody else.
-    const int which = ticks_kernel(s);
-    // (The fused and windowed *_ticks kernels integrate the plant themselves and know no wrench: with a wrench mode in force the loop takes
-    // a launch per step.)
-    const bool one_launch = rc == BROV_OK && s->k.closed_loop_fused && ncols == 16 && line0 >= 0 && line0 + (ticks - 1) + s->N <= s->traj_rows - 1 && which != 0 &&
-                            s->wr.mode == BROV_WRENCH_OFF;
-    if (one_launch) {
-        rc = brov_set_yref_from_traj(s, line0, 16, st);
-        if (rc == BROV_OK) rc = order_behind_last(s, st);
-        if (rc == BROV_OK) {
-            DevParams P = make_params(s, plan_solve(s, 0));
-            P.sched = nullptr;
-            P.ticks = ticks; P.tick_yref = 16; P.tick_status = L.status(0);
-            P.plant_pp = s->pplant; P.plant_rp = plant_rp(s); P.plant_rp_stride = plant_rp_stride(s); P.plant_substeps = substeps; P.plant_dt = dt;
-            P.x0_rw = s->x0; P.plant_xlog = L.x(1); P.plant_ulog = L.u(0);
-            if (s->timing) { hipEventRecord(s->ev[0], st); hipEventRecord(s->ev[1], st); }   // (as brov_solve_ticks: brov_last_solve_seconds then reports THIS launch)
-            launch_lds(s, P, which, st); s->prep_path = 0;
-            if (s->timing) { hipEventRecord(s->ev[2], st); s->ev_valid = true; }
-            s->traj_line = line0 + ticks - 1; s->yref_view = s->traj + (size_t)s->traj_line * 16;
-            s->wr_tick += ticks;
-        }
-    }
-    for (int k = 0; k < ticks && rc == BROV_OK && !one_launch; k++) {
-        forget_traj_window(s);
-        launch_window(s->traj, s->traj_rows, nullptr, line0 + k, 1, s->N, ncols, s->yref_sh, st);
-        s->yref_shared = true;
-        rc = brov_solve_phase(s, st, 0);
-        if (L.status(k)) hipLaunchKernelGGL(gather_status_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, s->res, L.status(k), (int)B);
-        plant_step_on(s, dt, substeps, L.x(k + 1), L.u(k), L.w(k), st);
-    }
+    int which = 0;
+    const bool one_launch = loop_in_one_launch(s, ticks, line0, ncols, &which);
+    if (rc == BROV_OK) rc = run_loop_ticks(s, ticks, line0, ncols, dt, substeps, one_launch, which, tick_logs(L), st);
     hipError_t e = hipStreamSynchronize(st);
     if (rc == BROV_OK && e != hipSuccess) { g_err = hipGetErrorString(e); rc = BROV_ERR_HIP; }
     return L.end(rc);
@@ -1054,30 +1108,62 @@ extern "C" int brov_closed_loop_dob(brov_solver* s, brov_ekf* e, brov_rls* r, in
     if (int wrc = wrench_tick_ok(s, s->wr_tick + ticks - 1, "brov_closed_loop_dob")) return wrc;
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = s->last_stream;
-    const size_t B = s->B;
     LoopLogs L;
     int rc = L.begin(s, ticks, u_log, x_log, st_log, w_log, est_log, st, "brov_closed_loop_dob");
-    // the observer's and the estimator's calls report through their own error strings: their code is handed on, their text copied
-    auto sub = [&](int code, const char* text) {
-        if (code != BROV_OK) { g_err = std::string("brov_closed_loop_dob: ") + text; rc = code; }
-        return code == BROV_OK;
-    };
-    for (int k = 0; k < ticks && rc == BROV_OK; k++) {
-        rc = brov_set_yref_from_traj(s, line0 + k, ncols, st);
-        if (rc == BROV_OK) rc = brov_solve_phase(s, st, 0);
-        if (rc != BROV_OK) break;
-        if (L.status(k)) hipLaunchKernelGGL(gather_status_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, s->res, L.status(k), (int)B);
-        ensure_plant_params(s, st);   // (the hand-off below rewrites the controller's stage 0, which a plant without parameters of its own follows)
-        plant_step_on(s, dt, substeps, L.x(k + 1), L.u(k), L.w(k), st);
-        if (!sub(brov_ekf_update_from_solver(e, s, st), brov_ekf_last_error())) break;
-        if (L.est(k)) launch_gather_cols(brov_ekf_x_device(e), (int)B, 18, 12, 6, L.est(k), st);
-        if (!r) sub(brov_ekf_apply_to_solver(e, s, st), brov_ekf_last_error());
-        else if (sub(brov_rls_update_from_ekf(r, e, s, st), brov_rls_last_error())) sub(brov_rls_apply_to_solver(r, s, rls_mode, st), brov_rls_last_error());
-    }
+    if (rc == BROV_OK) rc = run_dob_ticks(s, e, r, rls_mode, ticks, line0, ncols, dt, substeps, tick_logs(L), st, "brov_closed_loop_dob");
     hipError_t err = hipStreamSynchronize(st);
     if (rc == BROV_OK && err == hipSuccess) err = hipGetLastError();
     if (rc == BROV_OK && err != hipSuccess) { g_err = hipGetErrorString(err); rc = BROV_ERR_HIP; }
     return L.end(rc);
+}
+
+namespace brov {
+// one accumulate of the tracking statistics over DEVICE logs on `st`, saturation judged by the given bounds (track_kernel.hip)
+int track_accumulate_on(brov_track* t, const double* x, const double* u, const int* status, int K, const double* ref, int rows, int line1,
+                        const double* lbu, const double* ubu, hipStream_t st);
+}
+// The same loops scored instead of logged (brov_track_*, track_kernel.hip): chunks of ticks into DEVICE logs of one chunk, one accumulate behind
+// every chunk on the same stream, one host wait at the end.
+extern "C" int brov_closed_loop_track(brov_solver* s, brov_ekf* e, brov_rls* r, int rls_mode, brov_track* t, int ticks, int line0, int ncols,
+                                      double dt, int substeps, int chunk) {
+    if (!s || !t || (r && !e) || ticks < 1 || chunk < 0 || !s->traj || (ncols != 12 && ncols != 16) || !(dt > 0.0) || substeps < 1) {
+        g_err = "brov_closed_loop_track: bad argument (needs a tracker, ticks >= 1, chunk >= 0 and a trajectory table, see brov_traj_set_host)";
+        return BROV_ERR_ARG;
+    }
+    if (brov_track_batch(t) != s->B || (e && brov_ekf_batch(e) != s->B) || (r && brov_rls_batch(r) != s->B)) {
+        g_err = "brov_closed_loop_track: batch sizes differ";
+        return BROV_ERR_ARG;
+    }
+    if (r && rls_mode != BROV_RLS_APPLY_DISTURBANCE && rls_mode != BROV_RLS_APPLY_MODEL) { g_err = "brov_closed_loop_track: unknown rls_mode"; return BROV_ERR_ARG; }
+    if (int wrc = wrench_tick_ok(s, s->wr_tick + ticks - 1, "brov_closed_loop_track")) return wrc;
+    HIPCHK(hipSetDevice(s->device));
+    hipStream_t st = s->last_stream;
+    if (!e) ensure_plant_params(s, st);
+    int which = 0;
+    const bool one_launch = !e && loop_in_one_launch(s, ticks, line0, ncols, &which);   // decided for the whole run, as brov_closed_loop_ex does
+    const size_t B = s->B, C = (size_t)std::min(chunk == 0 ? 64 : chunk, ticks);
+    TickLogs T;
+    T.B = B;
+    hipError_t he = hipMalloc((void**)&T.dx, C * B * 12 * sizeof(double));
+    if (he == hipSuccess) he = hipMalloc((void**)&T.du, C * B * 4 * sizeof(double));
+    if (he == hipSuccess) he = hipMalloc((void**)&T.dst, C * B * sizeof(int));
+    int rc = BROV_OK;
+    if (he != hipSuccess) { (void)hipGetLastError(); g_err = std::string("brov_closed_loop_track: hipMalloc: ") + hipGetErrorString(he); rc = BROV_ERR_ALLOC; }
+    for (int k0 = 0; k0 < ticks && rc == BROV_OK; k0 += (int)C) {
+        const int n = std::min((int)C, ticks - k0);
+        rc = e ? run_dob_ticks(s, e, r, rls_mode, n, line0 + k0, ncols, dt, substeps, T, st, "brov_closed_loop_track")
+               : run_loop_ticks(s, n, line0 + k0, ncols, dt, substeps, one_launch, which, T, st);
+        if (rc != BROV_OK) break;
+        // the state after tick k against row line0 + k + 1, by the solver's bounds of the moment
+        rc = track_accumulate_on(t, T.dx, T.du, T.dst, n, s->traj, s->traj_rows, line0 + k0 + 1, s->opts.lbu, s->opts.ubu, st);
+        if (rc != BROV_OK) g_err = std::string("brov_closed_loop_track: ") + brov_track_last_error();
+    }
+    hipError_t err = hipStreamSynchronize(st);
+    if (rc == BROV_OK && err == hipSuccess) err = hipGetLastError();
+    if (rc == BROV_OK && err != hipSuccess) { g_err = hipGetErrorString(err); rc = BROV_ERR_HIP; }
+    for (void* q : {(void*)T.dx, (void*)T.du, (void*)T.dst})
+        if (q) hipFree(q);
+    return rc;
 }
 
 extern "C" int brov_set_iterate_host(brov_solver* s, const double* x, const double* u, const double* pi, const double* lam) {

@@ -423,6 +423,15 @@ class BatchSolver:
                   "closed_loop_dob")
         return dict(u=ul, x=xl, status=sl, wrench=wl, est=el)
 
+    def closed_loop_track(self, track, ticks, line0=0, ncols=16, dt=0.05, substeps=1, ekf=None, rls=None, rls_mode=0, chunk=0):
+        """the closed loop scored instead of logged (brov_closed_loop_track): the ticks of closed_loop() -- with ekf= those of closed_loop_dob(),
+        rls= making it the AMPC loop -- in chunks of `chunk` ticks (0: 64), each chunk's device logs folded into `track` (a BatchTrack) against
+        the trajectory table; one host wait, no host log.  The statistics continue those of earlier calls (track.reset() starts afresh)."""
+        he = ekf._h if ekf is not None else None
+        hr = rls._h if rls is not None else None
+        self._chk(track._L.brov_closed_loop_track(self._h, he, hr, int(rls_mode), track._h, int(ticks), int(line0), int(ncols), float(dt),
+                                                  int(substeps), int(chunk)), "closed_loop_track")
+
     # ---- time-varying world-frame wrench on the plant (bluerov2_dob.cpp:754-892, applyBodyWrench) ------------------------------
     def set_plant_wrench(self, constant=None, periodic=None, table=None, gain=None):
         """exactly one of

@@ -1,0 +1,147 @@
+"""Host-side mirror of the batched tracking statistics (include/bluerov2_nmpc.h, brov_track_*): closed loops scored on the device
+instead of logged.  ctypes over the HIP library -- no CPU path."""
+import ctypes as C
+
+import numpy as np
+
+from .solver import _load, NoDeviceError
+
+# brov_track_stats, 96 bytes per instance
+TRACK_STATS_DTYPE = np.dtype([("sum_pos2", "f8"), ("sum_yaw2", "f8"), ("max_pos2", "f8"), ("max_yaw", "f8"), ("sum_u2", "f8", (4,)),
+                              ("ticks", "i4"), ("failed", "i4"), ("saturated", "i4"), ("nonfinite", "i4"), ("first_failed", "i4"),
+                              ("worst_tick", "i4"), ("pad_", "i4", (2,))])
+assert TRACK_STATS_DTYPE.itemsize == 96
+
+
+class TrackParams(C.Structure):
+    """brov_track_params: the input bounds `saturated` is judged by; TrackParams.default() = the bounds of brov_default_opts"""
+    _fields_ = [("lbu", C.c_double * 4), ("ubu", C.c_double * 4)]
+
+    @classmethod
+    def default(cls):
+        p = cls()
+        _track_lib().brov_track_default_params(C.byref(p))
+        return p
+
+
+class TrackSummary(C.Structure):
+    """brov_track_summary"""
+    _fields_ = [("rms_pos", C.c_double), ("rms_yaw", C.c_double), ("worst_max_pos2", C.c_double), ("ticks", C.c_int64),
+                ("failed", C.c_int64), ("saturated", C.c_int64), ("nonfinite", C.c_int64), ("worst_instance", C.c_int32),
+                ("failed_instances", C.c_int32)]
+
+
+_bound = False
+
+
+def _track_lib():
+    global _bound
+    L = _load()
+    if not _bound:
+        vp, dp, ip = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        L.brov_track_last_error.restype = C.c_char_p
+        L.brov_track_default_params.argtypes = [C.POINTER(TrackParams)]
+        L.brov_track_default_params.restype = None
+        L.brov_track_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.POINTER(TrackParams)]
+        L.brov_track_destroy.argtypes = [vp]
+        L.brov_track_destroy.restype = None
+        for name, args in {
+            "brov_track_batch": [vp], "brov_track_reset": [vp],
+            "brov_track_accumulate_host": [vp, dp, dp, ip, C.c_int, dp, C.c_int, C.c_int],
+            "brov_track_accumulate_device": [vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp],
+            "brov_track_get_stats_host": [vp, vp], "brov_track_get_summary_host": [vp, C.POINTER(TrackSummary)],
+            "brov_track_last_seconds": [vp, dp],
+            "brov_closed_loop_track": [vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int],
+        }.items():
+            fn = getattr(L, name)
+            fn.argtypes = args
+            fn.restype = C.c_int
+        _bound = True
+    return L
+
+
+def _dp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _c(a, shape, dtype=np.float64):
+    a = np.ascontiguousarray(a, dtype=dtype)
+    if a.shape != tuple(shape):
+        raise ValueError(f"expected shape {tuple(shape)}, got {a.shape}")
+    return a
+
+
+class BatchTrack:
+    """One tracking-statistics record per instance, resident on one GPU (brov_track).  Fed by accumulate() from logs or by
+    BatchSolver.closed_loop_track(); stats() = the records, summary() = the whole batch."""
+
+    def __init__(self, batch, params=None, device=0):
+        L = _track_lib()
+        self.B = int(batch)
+        self.params = params if params is not None else TrackParams.default()
+        h = C.c_void_p()
+        rc = L.brov_track_create(C.byref(h), int(device), self.B, C.byref(self.params))
+        if rc == -2:
+            raise NoDeviceError(L.brov_track_last_error().decode() or "no HIP device")
+        if rc != 0:
+            raise RuntimeError(f"brov_track_create failed ({rc}): {L.brov_track_last_error().decode()}")
+        self._h, self._L = h, L
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.brov_track_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def _chk(self, rc, what):
+        if rc != 0:
+            raise RuntimeError(f"{what} failed ({rc}): {self._L.brov_track_last_error().decode()}")
+
+    def reset(self):
+        self._chk(self._L.brov_track_reset(self._h), "reset")
+
+    def accumulate(self, x, u, status, ref, line1):
+        """K ticks of host logs x [K, B, 12], u [K, B, 4], status [K, B] (None: all zero) against the table ref [rows, 16]: tick j against
+        row min(line1 + j, rows - 1)"""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        K = x.shape[0] if x.ndim == 3 else 0
+        x = _c(x, (K, self.B, 12)); u = _c(u, (K, self.B, 4))
+        ref = np.ascontiguousarray(ref, dtype=np.float64)
+        if ref.ndim != 2 or ref.shape[1] != 16:
+            raise ValueError(f"expected a table [rows, 16], got {ref.shape}")
+        sp = None
+        if status is not None:
+            status = _c(status, (K, self.B), np.int32)
+            sp = status.ctypes.data_as(C.POINTER(C.c_int32))
+        self._chk(self._L.brov_track_accumulate_host(self._h, _dp(x), _dp(u), sp, K, _dp(ref), ref.shape[0], int(line1)), "accumulate")
+
+    def accumulate_device(self, x_ptr, u_ptr, status_ptr, K, ref_ptr, rows, line1, stream=0):
+        """the same through device pointers (status_ptr 0 / None: all zero); enqueued on `stream`, no host wait"""
+        self._chk(self._L.brov_track_accumulate_device(self._h, C.c_void_p(x_ptr), C.c_void_p(u_ptr), C.c_void_p(status_ptr or None), int(K),
+                                                       C.c_void_p(ref_ptr), int(rows), int(line1), C.c_void_p(stream)), "accumulate_device")
+
+    def stats(self):
+        """the records, a structured array [B] of TRACK_STATS_DTYPE"""
+        out = np.empty(self.B, dtype=TRACK_STATS_DTYPE)
+        self._chk(self._L.brov_track_get_stats_host(self._h, out.ctypes.data_as(C.c_void_p)), "stats")
+        return out
+
+    def summary(self):
+        """dict of the batch summary (brov_track_summary) plus worst_max_pos = sqrt(worst_max_pos2)"""
+        s = TrackSummary()
+        self._chk(self._L.brov_track_get_summary_host(self._h, C.byref(s)), "summary")
+        d = {k: getattr(s, k) for k, _ in TrackSummary._fields_}
+        d["worst_max_pos"] = float(np.sqrt(s.worst_max_pos2))
+        return d
+
+    def summary_bytes(self):
+        """the raw 64 bytes of brov_track_summary (two calls return the same bytes)"""
+        s = TrackSummary()
+        self._chk(self._L.brov_track_get_summary_host(self._h, C.byref(s)), "summary")
+        return bytes(s)
+
+    def last_seconds(self):
+        s = C.c_double()
+        self._chk(self._L.brov_track_last_seconds(self._h, C.byref(s)), "last_seconds")
+        return s.value

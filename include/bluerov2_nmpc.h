@@ -547,6 +547,78 @@ int brov_rls_last_update_seconds(brov_rls* r, double* seconds);
 int brov_closed_loop_dob(brov_solver* s, brov_ekf* e, brov_rls* r /*NULL: DOB; else AMPC*/, int rls_mode, int ticks, int line0, int ncols,
                          double dt, int substeps, double* u_log, double* x_log, int32_t* st_log, double* w_log, double* est_log);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Batched tracking statistics: closed loops scored on the device.  What users do with the logs of a closed loop is always the same
+ * reduction -- the RMS position error against the trajectory (the reference's bluerov2_states/scripts/error.py) --
+ * and at Monte-Carlo batch sizes the logs themselves are the bottleneck.  A brov_track holds one 96-byte record
+ * per instance, fed from logs [K][B][..] of K consecutive ticks; the record is updated in tick order, so it does not depend on how a
+ * run is cut into calls (bit for bit).  Ticks are numbered from the last brov_track_reset: tick number = ticks + nonfinite so far.
+ *   counted tick    x, y, z, psi of the state row (columns 0, 1, 2, 5: the only ones read) and the four inputs are all finite.
+ *                   e2 = ((x-xr)^2 + (y-yr)^2) + (z-zr)^2 and the other squares in plain IEEE arithmetic in this order (no fused
+ *                   multiply-add): sums and maxima equal a sequential restatement bit for bit (tests/track_restatement.py)
+ *   non-finite tick any of those eight values is NaN or +-Inf: counted in `nonfinite`, in `failed` / `first_failed` if its status says so,
+ *                   and in nothing else -- it reaches neither the sums nor the maxima
+ * The yaw error is the raw difference psi - psi_r, NOT wrapped to (-pi, pi]: the OCP's residual is the unwrapped difference too, and
+ * trajectory and plant state are both continuous in yaw (the circle's psi grows past pi without a jump), so wrapping would score a
+ * state that the controller sees as a full turn off as on target.
+ * ------------------------------------------------------------------------------------------------------------------- */
+typedef struct brov_track_stats {
+    double  sum_pos2;       /* sum over counted ticks of e2 */
+    double  sum_yaw2;       /* sum of (psi - psi_r)^2 */
+    double  max_pos2;       /* max of e2 (squared: the host takes the root) */
+    double  max_yaw;        /* max |psi - psi_r| */
+    double  sum_u2[BROV_NU];/* sum of u_c^2 */
+    int32_t ticks;          /* counted ticks */
+    int32_t failed;         /* ticks with status != 0 (counted or not) */
+    int32_t saturated;      /* counted ticks with any u_c <= lbu_c or u_c >= ubu_c */
+    int32_t nonfinite;      /* non-finite ticks */
+    int32_t first_failed;   /* number of the first tick with status != 0; -1: none */
+    int32_t worst_tick;     /* number of the tick that set max_pos2, the first such tick on ties; -1 while ticks == 0 */
+    int32_t pad_[2];        /* zero */
+} brov_track_stats;
+/* the whole batch.  Instances with ticks == 0 add nothing to the sums and cannot be the worst instance (their failed / nonfinite
+ * counts are totalled: an instance that was NaN from its first tick on shows there); no counted tick at all: rms = 0, worst_instance = -1 */
+typedef struct brov_track_summary {
+    double  rms_pos;        /* sqrt(sum of sum_pos2 / sum of ticks) */
+    double  rms_yaw;        /* sqrt(sum of sum_yaw2 / sum of ticks) */
+    double  worst_max_pos2; /* the largest max_pos2 of the batch */
+    int64_t ticks, failed, saturated, nonfinite;   /* totals */
+    int32_t worst_instance; /* where worst_max_pos2 sits, the lowest index on ties */
+    int32_t failed_instances;   /* instances with failed > 0 */
+} brov_track_summary;
+typedef struct brov_track brov_track;
+typedef struct brov_track_params {   /* input bounds that `saturated` is judged by */
+    double lbu[BROV_NU], ubu[BROV_NU];
+} brov_track_params;
+void brov_track_default_params(brov_track_params* p);   /* the bounds of brov_default_opts */
+const char* brov_track_last_error(void); /* message of the last failing brov_track_* call on this thread */
+int  brov_track_create(brov_track** out, int device, int batch, const brov_track_params* p /* NULL: defaults */);
+void brov_track_destroy(brov_track* t);
+int  brov_track_batch(const brov_track* t);
+int  brov_track_reset(brov_track* t);   /* every record: zeros, first_failed = worst_tick = -1 */
+/* K >= 1 ticks of logs x [K][B][12], u [K][B][4], status [K][B] (NULL: all zero) against the trajectory table ref [rows][16]: tick j of
+ * the call is compared with row min(line1 + j, rows - 1) (rows below 0: row 0).  HOST pointers: copied, then one kernel.  DEVICE
+ * pointers: one kernel enqueued on `stream`, no host wait; the logs must stay valid until it has run. */
+int brov_track_accumulate_host(brov_track* t, const double* x, const double* u, const int32_t* status, int K, const double* ref, int rows,
+                               int line1);
+int brov_track_accumulate_device(brov_track* t, const double* x, const double* u, const int32_t* status, int K, const double* ref, int rows,
+                                 int line1, void* stream);
+int brov_track_get_stats_host(brov_track* t, brov_track_stats* stats /*[B]*/);
+/* reduced on the device without floating-point atomics, in an order that depends on the batch size only: two calls return the same bytes */
+int brov_track_get_summary_host(brov_track* t, brov_track_summary* summary);
+/* seconds of the last accumulate kernel (HIP events on its stream) */
+int brov_track_last_seconds(brov_track* t, double* seconds);
+/* A closed loop that is scored instead of logged.  e == NULL: the ticks of brov_closed_loop_ex (the one-launch kernel where that call would
+ * take it for the whole run, a launch per tick otherwise, e.g. under a wrench mode); with an observer: the ticks of brov_closed_loop_dob
+ * (r == NULL: DOB, else AMPC with rls_mode).  The run is cut into chunks of `chunk` ticks (0: 64; < 0: BROV_ERR_ARG); each chunk writes
+ * DEVICE logs sized for ONE chunk -- the same buffers for every chunk -- and is followed on the same stream by one accumulate against the
+ * solver's own trajectory table: the state after tick k against row min(line0 + k + 1, rows - 1), saturation judged by the solver's bounds
+ * of the moment (brov_opts::lbu / ubu).  One host wait, at the end; no host log.  Solver, observer and estimator end bit for bit where
+ * the loop they mirror leaves them.  The record is NOT reset: successive calls continue the same statistics.  The objects must hold the
+ * same batch (BROV_ERR_ARG); otherwise arguments and errors are those of the mirrored loop (text through brov_last_error). */
+int brov_closed_loop_track(brov_solver* s, brov_ekf* e /*NULL: no observer*/, brov_rls* r /*NULL: DOB; else AMPC*/, int rls_mode, brov_track* t,
+                           int ticks, int line0, int ncols, double dt, int substeps, int chunk);
+
 #ifdef __cplusplus
 }
 #endif
