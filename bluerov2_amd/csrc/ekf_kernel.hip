@@ -675,20 +675,12 @@ __global__ void ekf_apply_kernel(int B, int stages, const double* __restrict__ m
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
+#include "host_common.hpp"   // (here, not at the top: the kernels above keep their line numbers in the compiler's resource report)
+
 using namespace brov;
 
 static thread_local std::string g_ekf_err;
-#define EKFCHK(call)                                                                                          \
-    do {                                                                                                      \
-        hipError_t e_ = (call);                                                                               \
-        if (e_ != hipSuccess) {                                                                               \
-            g_ekf_err = std::string(#call) + ": " + hipGetErrorString(e_);                                    \
-            (void)hipGetLastError();                                                                              \
-            return (e_ == hipErrorNoDevice || e_ == hipErrorInvalidDevice || e_ == hipErrorInsufficientDriver) \
-                       ? BROV_ERR_NO_DEVICE                                                                   \
-                       : BROV_ERR_HIP;                                                                        \
-        }                                                                                                     \
-    } while (0)
+#define HIPCHK(call) BROV_HIPCHK(g_ekf_err, call)
 
 struct brov_ekf {
     int device = 0, B = 0;
@@ -698,9 +690,8 @@ struct brov_ekf {
            *vprev = nullptr;
     int* status = nullptr;
     hipStream_t last_stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    bool ev_valid = false;
-    std::vector<void*> allocs;
+    KernelTimer timer;   // around the last update kernel
+    DeviceAllocs mem;
 };
 
 extern "C" const char* brov_ekf_last_error(void) { return g_ekf_err.c_str(); }
@@ -708,7 +699,7 @@ extern "C" const char* brov_ekf_last_error(void) { return g_ekf_err.c_str(); }
 // for the RLS-FF estimator (rls_kernel.hip): `st` waits on the device for the observer's last update kernel -- the estimate it reads
 namespace brov {
 int ekf_wait_last_update(const brov_ekf* e, hipStream_t st) {
-    if (e->ev_valid) EKFCHK(hipStreamWaitEvent(st, e->ev[1], 0));
+    if (e->timer.valid) HIPCHK(hipStreamWaitEvent(st, e->timer.stop_event(), 0));
     return BROV_OK;
 }
 }  // namespace brov
@@ -775,27 +766,17 @@ static void make_const(const brov_ekf_params& p, EkfConst& c) {
     derive_mass(p, c.Md, c.iMd);
 }
 
-template <typename T>
-static int ekf_alloc(brov_ekf* e, T** p, size_t n) {
-    void* q = nullptr;
-    if (hipMalloc(&q, n * sizeof(T)) != hipSuccess) { g_ekf_err = "hipMalloc failed"; return BROV_ERR_ALLOC; }
-    e->allocs.push_back(q);
-    *p = (T*)q;
-    return BROV_OK;
-}
-
 extern "C" void brov_ekf_destroy(brov_ekf* e) {
     if (!e) return;
     (void)hipSetDevice(e->device);
-    for (void* q : e->allocs) (void)hipFree(q);
-    for (auto& ev : e->ev)
-        if (ev) (void)hipEventDestroy(ev);
+    e->mem.free_all();
+    e->timer.destroy();
     delete e;
 }
 
 extern "C" int brov_ekf_reset(brov_ekf* e, const double* x0, const double* P0) {
     if (!e) return BROV_ERR_ARG;
-    EKFCHK(hipSetDevice(e->device));
+    HIPCHK(hipSetDevice(e->device));
     static const double xr[18] = {0, 0, -20, 0, 0, 0, 0, 0, 0, 0, 0, 0, 6, 6, 6, 0, 0, 0};  // bluerov2_dob.cpp:64
     std::vector<double> hx((size_t)e->B * 18), hp((size_t)e->B * 324, 0.0);
     for (int b = 0; b < e->B; b++) {
@@ -803,37 +784,35 @@ extern "C" int brov_ekf_reset(brov_ekf* e, const double* x0, const double* P0) {
         if (P0) std::memcpy(&hp[(size_t)b * 324], P0, 324 * sizeof(double));
         else for (int i = 0; i < 18; i++) hp[(size_t)b * 324 + i * 19] = 1.0;
     }
-    EKFCHK(hipMemcpy(e->x, hx.data(), hx.size() * sizeof(double), hipMemcpyHostToDevice));
-    EKFCHK(hipMemcpy(e->P, hp.data(), hp.size() * sizeof(double), hipMemcpyHostToDevice));
-    EKFCHK(hipMemset(e->vprev, 0, (size_t)e->B * 6 * sizeof(double)));
+    HIPCHK(hipMemcpy(e->x, hx.data(), hx.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(e->P, hp.data(), hp.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(e->vprev, 0, (size_t)e->B * 6 * sizeof(double)));
     return BROV_OK;
 }
 
 extern "C" int brov_ekf_create(brov_ekf** out, int device, int B, const brov_ekf_params* p) {
     if (!out || B <= 0) { g_ekf_err = "brov_ekf_create: bad arguments"; return BROV_ERR_ARG; }
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
+    if (!usable_device(device)) {
         g_ekf_err = "brov_ekf_create: no usable HIP device (the observer has no CPU path)";
         return BROV_ERR_NO_DEVICE;
     }
-    EKFCHK(hipSetDevice(device));
+    HIPCHK(hipSetDevice(device));
     brov_ekf* e = new brov_ekf();
     e->device = device; e->B = B;
     if (p) e->par = *p; else brov_ekf_default_params(&e->par);
     make_const(e->par, e->c);
     int rc = BROV_OK;
-    if ((rc = ekf_alloc(e, &e->x, (size_t)B * 18)) || (rc = ekf_alloc(e, &e->P, (size_t)B * 324)) ||
-        (rc = ekf_alloc(e, &e->thrust, (size_t)B * 6)) || (rc = ekf_alloc(e, &e->y12, (size_t)B * 12)) ||
-        (rc = ekf_alloc(e, &e->acc, (size_t)B * 6)) || (rc = ekf_alloc(e, &e->wf, (size_t)B * 6)) ||
-        (rc = ekf_alloc(e, &e->mp, (size_t)B * 4)) || (rc = ekf_alloc(e, &e->vprev, (size_t)B * 6)) ||
-        (rc = ekf_alloc(e, &e->status, (size_t)B))) {
+    auto al = [&](auto** p, size_t n) { return rc = e->mem.alloc(p, n, g_ekf_err); };
+    if (al(&e->x, (size_t)B * 18) || al(&e->P, (size_t)B * 324) || al(&e->thrust, (size_t)B * 6) || al(&e->y12, (size_t)B * 12) ||
+        al(&e->acc, (size_t)B * 6) || al(&e->wf, (size_t)B * 6) || al(&e->mp, (size_t)B * 4) || al(&e->vprev, (size_t)B * 6) ||
+        al(&e->status, (size_t)B)) {
+        g_ekf_err = "brov_ekf_create: " + g_ekf_err;
         brov_ekf_destroy(e);
         return rc;
     }
     if (hipMemset(e->wf, 0, (size_t)B * 6 * sizeof(double)) != hipSuccess || hipMemset(e->mp, 0, (size_t)B * 4 * sizeof(double)) != hipSuccess ||
-        hipMemset(e->status, 0, (size_t)B * sizeof(int)) != hipSuccess || hipEventCreate(&e->ev[0]) != hipSuccess ||
-        hipEventCreate(&e->ev[1]) != hipSuccess) {
+        hipMemset(e->status, 0, (size_t)B * sizeof(int)) != hipSuccess || e->timer.create() != hipSuccess) {
         g_ekf_err = "brov_ekf_create: device initialisation failed";
         brov_ekf_destroy(e);
         return BROV_ERR_HIP;
@@ -850,18 +829,18 @@ extern "C" int brov_ekf_batch(const brov_ekf* e) { return e ? e->B : 0; }
 
 extern "C" int brov_ekf_set_state_host(brov_ekf* e, const double* x, const double* P) {
     if (!e) return BROV_ERR_ARG;
-    EKFCHK(hipSetDevice(e->device));
-    if (x) EKFCHK(hipMemcpy(e->x, x, (size_t)e->B * 18 * sizeof(double), hipMemcpyHostToDevice));
-    if (P) EKFCHK(hipMemcpy(e->P, P, (size_t)e->B * 324 * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipSetDevice(e->device));
+    if (x) HIPCHK(hipMemcpy(e->x, x, (size_t)e->B * 18 * sizeof(double), hipMemcpyHostToDevice));
+    if (P) HIPCHK(hipMemcpy(e->P, P, (size_t)e->B * 324 * sizeof(double), hipMemcpyHostToDevice));
     return BROV_OK;
 }
 
 extern "C" int brov_ekf_get_state_host(brov_ekf* e, double* x, double* P) {
     if (!e) return BROV_ERR_ARG;
-    EKFCHK(hipSetDevice(e->device));
-    EKFCHK(hipStreamSynchronize(e->last_stream));
-    if (x) EKFCHK(hipMemcpy(x, e->x, (size_t)e->B * 18 * sizeof(double), hipMemcpyDeviceToHost));
-    if (P) EKFCHK(hipMemcpy(P, e->P, (size_t)e->B * 324 * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->last_stream));
+    if (x) HIPCHK(hipMemcpy(x, e->x, (size_t)e->B * 18 * sizeof(double), hipMemcpyDeviceToHost));
+    if (P) HIPCHK(hipMemcpy(P, e->P, (size_t)e->B * 324 * sizeof(double), hipMemcpyDeviceToHost));
     return BROV_OK;
 }
 
@@ -869,39 +848,38 @@ static int launch_update(brov_ekf* e, const double* thrust, const double* y12, c
     EkfArgs a;
     a.c = e->c; a.B = e->B; a.x = e->x; a.P = e->P; a.thrust = thrust; a.y12 = y12; a.acc = acc; a.wf = e->wf; a.mp = e->mp;
     a.status = e->status;
-    EKFCHK(hipEventRecord(e->ev[0], st));
+    HIPCHK(e->timer.start(st));
     const int blocks = (e->B + kDppFilters - 1) / kDppFilters;
     hipLaunchKernelGGL(ekf_update_kernel_sp, dim3(blocks), dim3(64), kDppFilters * kSpLds * sizeof(double), st, a);
-    EKFCHK(hipGetLastError());
-    EKFCHK(hipEventRecord(e->ev[1], st));
-    e->ev_valid = true;
+    HIPCHK(hipGetLastError());
+    HIPCHK(e->timer.stop(st));
     e->last_stream = st;
     return BROV_OK;
 }
 
 extern "C" int brov_ekf_update_device(brov_ekf* e, const double* thrust, const double* y12, const double* acc, void* stream) {
     if (!e || !thrust || !y12 || !acc) return BROV_ERR_ARG;
-    EKFCHK(hipSetDevice(e->device));
+    HIPCHK(hipSetDevice(e->device));
     return launch_update(e, thrust, y12, acc, (hipStream_t)stream);
 }
 
 extern "C" int brov_ekf_update_host(brov_ekf* e, const double* thrust, const double* y12, const double* acc, void* stream) {
     if (!e || !thrust || !y12 || !acc) return BROV_ERR_ARG;
-    EKFCHK(hipSetDevice(e->device));
+    HIPCHK(hipSetDevice(e->device));
     hipStream_t st = (hipStream_t)stream;
-    EKFCHK(hipMemcpyAsync(e->thrust, thrust, (size_t)e->B * 6 * sizeof(double), hipMemcpyHostToDevice, st));
-    EKFCHK(hipMemcpyAsync(e->y12, y12, (size_t)e->B * 12 * sizeof(double), hipMemcpyHostToDevice, st));
-    EKFCHK(hipMemcpyAsync(e->acc, acc, (size_t)e->B * 6 * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(e->thrust, thrust, (size_t)e->B * 6 * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(e->y12, y12, (size_t)e->B * 12 * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(e->acc, acc, (size_t)e->B * 6 * sizeof(double), hipMemcpyHostToDevice, st));
     return launch_update(e, e->thrust, e->y12, e->acc, st);
 }
 
 extern "C" int brov_ekf_get_outputs_host(brov_ekf* e, double* wf, double* mpc_p, int* status) {
     if (!e) return BROV_ERR_ARG;
-    EKFCHK(hipSetDevice(e->device));
-    EKFCHK(hipStreamSynchronize(e->last_stream));
-    if (wf) EKFCHK(hipMemcpy(wf, e->wf, (size_t)e->B * 6 * sizeof(double), hipMemcpyDeviceToHost));
-    if (mpc_p) EKFCHK(hipMemcpy(mpc_p, e->mp, (size_t)e->B * 4 * sizeof(double), hipMemcpyDeviceToHost));
-    if (status) EKFCHK(hipMemcpy(status, e->status, (size_t)e->B * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->last_stream));
+    if (wf) HIPCHK(hipMemcpy(wf, e->wf, (size_t)e->B * 6 * sizeof(double), hipMemcpyDeviceToHost));
+    if (mpc_p) HIPCHK(hipMemcpy(mpc_p, e->mp, (size_t)e->B * 4 * sizeof(double), hipMemcpyDeviceToHost));
+    if (status) HIPCHK(hipMemcpy(status, e->status, (size_t)e->B * sizeof(int), hipMemcpyDeviceToHost));
     return BROV_OK;
 }
 
@@ -911,18 +889,18 @@ extern "C" const double* brov_ekf_mpc_p_device(const brov_ekf* e) { return e ? e
 
 extern "C" int brov_ekf_update_from_solver(brov_ekf* e, brov_solver* s, void* stream) {
     if (!e || !s || brov_batch(s) != e->B) { g_ekf_err = "brov_ekf_update_from_solver: batch sizes differ"; return BROV_ERR_ARG; }
-    EKFCHK(hipSetDevice(e->device));
+    HIPCHK(hipSetDevice(e->device));
     hipStream_t st = (hipStream_t)stream;
     if (brov_order_stream(s, stream) != BROV_OK) { g_ekf_err = "brov_ekf_update_from_solver: could not order behind the solver's last stream"; return BROV_ERR_HIP; }
     hipLaunchKernelGGL(ekf_inputs_from_solver_kernel, dim3((e->B + 255) / 256), dim3(256), 0, st, e->B, e->c.dt, 1.0 / kRotor,
                        (const double*)brov_x0_device(s), brov_results_device(s), e->vprev, e->thrust, e->y12, e->acc);
-    EKFCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return launch_update(e, e->thrust, e->y12, e->acc, st);
 }
 
 extern "C" int brov_ekf_apply_to_solver(brov_ekf* e, brov_solver* s, void* stream) {
     if (!e || !s || brov_batch(s) != e->B) { g_ekf_err = "brov_ekf_apply_to_solver: batch sizes differ"; return BROV_ERR_ARG; }
-    EKFCHK(hipSetDevice(e->device));
+    HIPCHK(hipSetDevice(e->device));
     brov_opts o;
     if (brov_get_opts(s, &o) != BROV_OK) return BROV_ERR_ARG;
     const int stages = o.N + 1;
@@ -930,17 +908,13 @@ extern "C" int brov_ekf_apply_to_solver(brov_ekf* e, brov_solver* s, void* strea
     if (brov_order_stream(s, stream) != BROV_OK) { g_ekf_err = "brov_ekf_apply_to_solver: could not order behind the solver's last stream"; return BROV_ERR_HIP; }
     hipLaunchKernelGGL(ekf_apply_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, e->B, stages,
                        (const double*)e->mp, brov_params_device(s), (const double*)e->x, e->c.inv_rc, brov_rp_disturbance_device(s));
-    EKFCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     e->last_stream = (hipStream_t)stream;
     return BROV_OK;
 }
 
 extern "C" int brov_ekf_last_update_seconds(brov_ekf* e, double* seconds) {
-    if (!e || !seconds || !e->ev_valid) return BROV_ERR_ARG;
-    EKFCHK(hipSetDevice(e->device));
-    EKFCHK(hipEventSynchronize(e->ev[1]));
-    float ms = 0.f;
-    EKFCHK(hipEventElapsedTime(&ms, e->ev[0], e->ev[1]));
-    *seconds = ms * 1e-3;
-    return BROV_OK;
+    if (!e || !seconds || !e->timer.valid) return BROV_ERR_ARG;
+    HIPCHK(hipSetDevice(e->device));
+    return e->timer.seconds(seconds, g_ekf_err);
 }

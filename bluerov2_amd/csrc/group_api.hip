@@ -44,6 +44,7 @@ typedef enum { ncclSuccess = 0 } ncclResult_t;
 typedef enum { ncclUint8 = 1, ncclDouble = 8 } ncclDataType_t;
 
 #include "../../include/bluerov2_nmpc.h"
+#include "host_common.hpp"
 
 static thread_local std::string g_gerr;
 extern "C" const char* brov_group_last_error(void) { return g_gerr.c_str(); }
@@ -148,15 +149,7 @@ struct brov_group {
     bool ev_solve = false, ev_gather = false;   // ... the solve's pair, the gather's end
 };
 
-#define GHIP(call)                                                                          \
-    do {                                                                                    \
-        hipError_t e_ = (call);                                                             \
-        if (e_ != hipSuccess) {                                                             \
-            g_gerr = std::string(#call) + ": " + hipGetErrorString(e_);                     \
-            (void)hipGetLastError();   /* reported here: do not leave it behind as the thread's "last error" for an unrelated call */ \
-            return (e_ == hipErrorNoDevice || e_ == hipErrorInvalidDevice) ? BROV_ERR_NO_DEVICE : BROV_ERR_HIP; \
-        }                                                                                   \
-    } while (0)
+#define HIPCHK(call) BROV_HIPCHK(g_gerr, call)
 #define GNCCL(call)                                                                         \
     do {                                                                                    \
         ncclResult_t r_ = (call);                                                           \
@@ -329,10 +322,11 @@ static int group_build(brov_group** out, const int* devices, int n, int W, int r
     if (collective != BROV_COLLECTIVE_RCCL && collective != BROV_COLLECTIVE_COPY) { g_gerr = "brov_group_create: unknown collective"; return BROV_ERR_ARG; }
     const bool copy = collective == BROV_COLLECTIVE_COPY;
     DeviceKeeper keep;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_gerr = "brov_group_create: no usable HIP device (this library has no CPU fallback)"; return BROV_ERR_NO_DEVICE; }
     for (int d = 0; d < n; d++) {
-        if (devices[d] < 0 || devices[d] >= ndev) { g_gerr = "brov_group_create: device ordinal out of range"; return BROV_ERR_NO_DEVICE; }
+        if (!brov::usable_device(devices[d])) {
+            g_gerr = "brov_group_create: no usable HIP device at ordinal " + std::to_string(devices[d]) + " (this library has no CPU fallback)";
+            return BROV_ERR_NO_DEVICE;
+        }
         for (int e = 0; e < d && !copy; e++)
             if (devices[e] == devices[d]) { g_gerr = "brov_group_create: a device may appear once (one RCCL rank per GPU; BROV_COLLECTIVE_COPY lifts this)"; return BROV_ERR_ARG; }
     }
@@ -526,9 +520,9 @@ static int copy_fence(brov_group* g) {
         if (!ok) { g_gerr = "copy collective: rank " + std::to_string(missing) + " has not finished gather " + std::to_string(g->round); return BROV_ERR_HIP; }
     }
     for (int d = 0; d < g->n; d++) {
-        GHIP(hipSetDevice(g->dev[d]));
+        HIPCHK(hipSetDevice(g->dev[d]));
         for (int r = 0; r < g->W; r++)
-            if (r != g->r0 + d) GHIP(hipStreamWaitEvent(g->st[d], c.peer[r].pulled, 0));
+            if (r != g->r0 + d) HIPCHK(hipStreamWaitEvent(g->st[d], c.peer[r].pulled, 0));
     }
     return BROV_OK;
 }
@@ -539,8 +533,8 @@ static int copy_gather(brov_group* g, int mode) {
     const size_t rec = sizeof(brov_result);
     const long round = ++g->round;
     for (int d = 0; d < g->n; d++) {
-        GHIP(hipSetDevice(g->dev[d]));
-        GHIP(hipEventRecord(c.peer[g->r0 + d].ready, g->st[d]));
+        HIPCHK(hipSetDevice(g->dev[d]));
+        HIPCHK(hipEventRecord(c.peer[g->r0 + d].ready, g->st[d]));
     }
     {
         std::unique_lock<std::mutex> lk(c.m);
@@ -558,15 +552,15 @@ static int copy_gather(brov_group* g, int mode) {
             if (c.peer[r].entered == round && c.peer[r].mode != mode) { g_gerr = "copy collective: the ranks disagree about the gather mode"; return BROV_ERR_ARG; }
     }
     for (int d = 0; d < g->n; d++) {
-        GHIP(hipSetDevice(g->dev[d]));
+        HIPCHK(hipSetDevice(g->dev[d]));
         for (int r = 0; r < g->W; r++) {
-            if (r != g->r0 + d) GHIP(hipStreamWaitEvent(g->st[d], c.peer[r].ready, 0));
+            if (r != g->r0 + d) HIPCHK(hipStreamWaitEvent(g->st[d], c.peer[r].ready, 0));
             if (mode == BROV_GATHER_RECORDS)
-                GHIP(hipMemcpyAsync(g->gathered[d] + (size_t)r * g->Bmax, c.peer[r].src_rec, (size_t)g->Bmax * rec, hipMemcpyDefault, g->st[d]));
+                HIPCHK(hipMemcpyAsync(g->gathered[d] + (size_t)r * g->Bmax, c.peer[r].src_rec, (size_t)g->Bmax * rec, hipMemcpyDefault, g->st[d]));
             else
-                GHIP(hipMemcpyAsync(g->pairs[d] + 2 * r, c.peer[r].src_pair, 2 * sizeof(double), hipMemcpyDefault, g->st[d]));
+                HIPCHK(hipMemcpyAsync(g->pairs[d] + 2 * r, c.peer[r].src_pair, 2 * sizeof(double), hipMemcpyDefault, g->st[d]));
         }
-        GHIP(hipEventRecord(c.peer[g->r0 + d].pulled, g->st[d]));
+        HIPCHK(hipEventRecord(c.peer[g->r0 + d].pulled, g->st[d]));
     }
     {
         std::lock_guard<std::mutex> lk(c.m);
@@ -581,10 +575,10 @@ int brov_group_solve(brov_group* g) {
     DeviceKeeper keep;
     if (int rc = copy_fence(g)) return rc;
     for (int d = 0; d < g->n; d++) {
-        GHIP(hipSetDevice(g->dev[d]));
-        if (g->timing) GHIP(hipEventRecord(g->ev[4 * d + 0], g->st[d]));
+        HIPCHK(hipSetDevice(g->dev[d]));
+        if (g->timing) HIPCHK(hipEventRecord(g->ev[4 * d + 0], g->st[d]));
         if (int rc = brov_solve(g->sol[d], g->st[d])) { g_gerr = brov_last_error(); return rc; }
-        if (g->timing) GHIP(hipEventRecord(g->ev[4 * d + 1], g->st[d]));
+        if (g->timing) HIPCHK(hipEventRecord(g->ev[4 * d + 1], g->st[d]));
     }
     g->last_mode = -1;
     g->ev_sel = false; g->ev_gather = false; g->ev_solve = g->timing;
@@ -598,13 +592,13 @@ int brov_group_gather(brov_group* g, int mode) {
     if (int rc = copy_fence(g)) return rc;
     // what each device contributes, produced on its own stream behind the solve
     for (int d = 0; d < g->n; d++) {
-        GHIP(hipSetDevice(g->dev[d]));
+        HIPCHK(hipSetDevice(g->dev[d]));
         // (timing: the solve's end event doubles as the gather's start)
         if (mode == BROV_GATHER_RECORDS) {
-            if (!g->even) GHIP(hipMemcpyAsync(g->stage[d], brov_results_device(g->sol[d]), (size_t)g->cnt[g->r0 + d] * rec, hipMemcpyDeviceToDevice, g->st[d]));
+            if (!g->even) HIPCHK(hipMemcpyAsync(g->stage[d], brov_results_device(g->sol[d]), (size_t)g->cnt[g->r0 + d] * rec, hipMemcpyDeviceToDevice, g->st[d]));
         } else {
             hipLaunchKernelGGL(group_pack_kernel, dim3(1), dim3(256), 0, g->st[d], brov_results_device(g->sol[d]), g->cnt[g->r0 + d], g->lo[g->r0 + d], g->pair[d], g->pmail[d]);
-            GHIP(hipGetLastError());
+            HIPCHK(hipGetLastError());
         }
     }
     if (g->cc) {
@@ -625,7 +619,7 @@ int brov_group_gather(brov_group* g, int mode) {
         GNCCL(R.GroupEnd());
     }
     if (g->timing)
-        for (int d = 0; d < g->n; d++) { GHIP(hipSetDevice(g->dev[d])); GHIP(hipEventRecord(g->ev[4 * d + 2], g->st[d])); }
+        for (int d = 0; d < g->n; d++) { HIPCHK(hipSetDevice(g->dev[d])); HIPCHK(hipEventRecord(g->ev[4 * d + 2], g->st[d])); }
     g->ev_gather = g->timing && g->ev_solve;
     g->last_mode = mode;
     return BROV_OK;
@@ -634,7 +628,7 @@ int brov_group_gather(brov_group* g, int mode) {
 int brov_group_synchronize(brov_group* g) {
     if (!g) return BROV_ERR_ARG;
     DeviceKeeper keep;
-    for (int d = 0; d < g->n; d++) { GHIP(hipSetDevice(g->dev[d])); GHIP(hipStreamSynchronize(g->st[d])); }
+    for (int d = 0; d < g->n; d++) { HIPCHK(hipSetDevice(g->dev[d])); HIPCHK(hipStreamSynchronize(g->st[d])); }
     return BROV_OK;
 }
 
@@ -673,7 +667,7 @@ int brov_group_select_best(brov_group* g, int* best_index, brov_result* best) {
         // every device holds all records: device 0 selects (any would do).  The kernel delivers the winning slot and its record into
         // the pinned mailbox and the host polls the sequence word: no copy command, no stream synchronisation on the way back (the
         // other devices only finish their gather -- their streams order whatever is enqueued next behind it).
-        GHIP(hipSetDevice(g->dev[0]));
+        HIPCHK(hipSetDevice(g->dev[0]));
         const int slots = g->W * g->Bmax;
         int nb = (slots + 1023) / 1024;
         nb = nb < 1 ? 1 : (nb > kSelBlocks ? kSelBlocks : nb);
@@ -681,8 +675,8 @@ int brov_group_select_best(brov_group* g, int* best_index, brov_result* best) {
         const int32_t seq = g->mail_seq;
         hipLaunchKernelGGL(group_select_kernel, dim3(nb), dim3(256), 0, g->st[0], g->gathered[0], slots, g->best[0], g->sel_cost, g->sel_idx,
                            (unsigned*)(g->best[0] + 1), g->sel_rec, g->mail, seq);
-        GHIP(hipGetLastError());
-        if (g->timing) { GHIP(hipEventRecord(g->ev[3], g->st[0])); g->ev_sel = true; }
+        HIPCHK(hipGetLastError());
+        if (g->timing) { HIPCHK(hipEventRecord(g->ev[3], g->st[0])); g->ev_sel = true; }
         if (int rc = mail_wait(g, seq)) return rc;
         const int slot = g->mail->slot;
         *best_index = slot_to_global(g, slot);
@@ -690,12 +684,12 @@ int brov_group_select_best(brov_group* g, int* best_index, brov_result* best) {
     } else {
         // the gathered pairs are reduced on device 0 and the winner's (owner rank, global index, cost) comes back through the mailbox;
         // its whole record is already in the owner's own mailbox (group_pack_kernel) when the owner is a device of this process
-        GHIP(hipSetDevice(g->dev[0]));
+        HIPCHK(hipSetDevice(g->dev[0]));
         g->mail_seq = g->mail_seq == 0x7fffffff ? 1 : g->mail_seq + 1;
         const int32_t seq = g->mail_seq;
         hipLaunchKernelGGL(group_pairs_kernel, dim3(1), dim3(64), 0, g->st[0], g->pairs[0], g->W, g->mail, seq);
-        GHIP(hipGetLastError());
-        if (g->timing) { GHIP(hipEventRecord(g->ev[3], g->st[0])); g->ev_sel = true; }
+        HIPCHK(hipGetLastError());
+        if (g->timing) { HIPCHK(hipEventRecord(g->ev[3], g->st[0])); g->ev_sel = true; }
         if (int rc = mail_wait(g, seq)) return rc;
         const int owner = g->mail->owner;
         if (owner >= 0) {
@@ -719,9 +713,9 @@ int brov_group_get_results_host(brov_group* g, brov_result* res) {
     if (g->last_mode != BROV_GATHER_RECORDS) { g_gerr = "brov_group_get_results_host: needs a BROV_GATHER_RECORDS gather"; return BROV_ERR_ARG; }
     if (int rc = brov_group_synchronize(g)) return rc;
     DeviceKeeper keep;
-    GHIP(hipSetDevice(g->dev[0]));
+    HIPCHK(hipSetDevice(g->dev[0]));
     for (int r = 0; r < g->W; r++)   // strip the padding slots of uneven shards
-        GHIP(hipMemcpy(res + g->lo[r], g->gathered[0] + (size_t)r * g->Bmax, (size_t)g->cnt[r] * sizeof(brov_result), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(res + g->lo[r], g->gathered[0] + (size_t)r * g->Bmax, (size_t)g->cnt[r] * sizeof(brov_result), hipMemcpyDeviceToHost));
     return BROV_OK;
 }
 const brov_result* brov_group_gathered_device(const brov_group* g, int rank) { return (g && rank >= 0 && rank < g->n) ? g->gathered[rank] : nullptr; }
@@ -732,19 +726,19 @@ int brov_group_last_seconds(brov_group* g, double* solve, double* gather, double
     double ts = 0, tg = 0, tsel = 0;
     DeviceKeeper keep;
     for (int d = 0; d < g->n; d++) {
-        GHIP(hipSetDevice(g->dev[d]));
+        HIPCHK(hipSetDevice(g->dev[d]));
         float a = 0, b = 0;
-        GHIP(hipEventSynchronize(g->ev[4 * d + 1]));
-        GHIP(hipEventElapsedTime(&a, g->ev[4 * d + 0], g->ev[4 * d + 1]));
-        if (g->last_mode >= 0 && g->ev_gather) { GHIP(hipEventSynchronize(g->ev[4 * d + 2])); GHIP(hipEventElapsedTime(&b, g->ev[4 * d + 1], g->ev[4 * d + 2])); }
+        HIPCHK(hipEventSynchronize(g->ev[4 * d + 1]));
+        HIPCHK(hipEventElapsedTime(&a, g->ev[4 * d + 0], g->ev[4 * d + 1]));
+        if (g->last_mode >= 0 && g->ev_gather) { HIPCHK(hipEventSynchronize(g->ev[4 * d + 2])); HIPCHK(hipEventElapsedTime(&b, g->ev[4 * d + 1], g->ev[4 * d + 2])); }
         if (a * 1e-3 > ts) ts = a * 1e-3;
         if (b * 1e-3 > tg) tg = b * 1e-3;
     }
     if (g->last_mode >= 0 && g->ev_sel && g->ev_gather) {   // (an event that was never recorded makes hipEventElapsedTime fail, and the failure would stay
         float c = 0;                        // behind as the thread's "last error" for the next hipGetLastError of an unrelated call)
-        GHIP(hipSetDevice(g->dev[0]));
-        GHIP(hipEventSynchronize(g->ev[3]));
-        GHIP(hipEventElapsedTime(&c, g->ev[2], g->ev[3]));
+        HIPCHK(hipSetDevice(g->dev[0]));
+        HIPCHK(hipEventSynchronize(g->ev[3]));
+        HIPCHK(hipEventElapsedTime(&c, g->ev[2], g->ev[3]));
         tsel = c * 1e-3;
     }
     if (solve) *solve = ts;

@@ -14,6 +14,7 @@
 #include <chrono>
 #include <vector>
 
+#include "host_common.hpp"
 #include "nmpc_device.hpp"
 
 using namespace brov;
@@ -23,17 +24,7 @@ using namespace brov;
 static thread_local std::string g_err;
 extern "C" const char* brov_last_error(void) { return g_err.c_str(); }
 
-#define HIPCHK(call)                                                                                   \
-    do {                                                                                               \
-        hipError_t e_ = (call);                                                                        \
-        if (e_ != hipSuccess) {                                                                        \
-            g_err = std::string(#call) + ": " + hipGetErrorString(e_);                                 \
-            (void)hipGetLastError(); /* reported here: not left behind as the "last error" of a later call */ \
-            return (e_ == hipErrorNoDevice || e_ == hipErrorInvalidDevice || e_ == hipErrorInsufficientDriver) \
-                       ? BROV_ERR_NO_DEVICE                                                            \
-                       : BROV_ERR_HIP;                                                                 \
-        }                                                                                              \
-    } while (0)
+#define HIPCHK(call) BROV_HIPCHK(g_err, call)
 
 struct brov_solver {
     int device = 0, B = 0, N = 0;
@@ -66,8 +57,7 @@ struct brov_solver {
     int cand_kind = 0;
     bool dump_lin = false;
     int* lines = nullptr;        // [B]
-    size_t bytes = 0;
-    std::vector<void*> allocs;
+    DeviceAllocs mem;            // every buffer above that is not named in brov_destroy
     hipStream_t last_stream = nullptr;
     bool timing = false;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
@@ -194,20 +184,6 @@ static const char* opts_problem(const brov_opts* o) {
     return nullptr;
 }
 
-template <typename T>
-static int dalloc(brov_solver* s, T** p, size_t n) {
-    void* q = nullptr;
-    hipError_t e = hipMalloc(&q, n * sizeof(T));
-    if (e != hipSuccess) {
-        g_err = std::string("hipMalloc: ") + hipGetErrorString(e);
-        return BROV_ERR_ALLOC;
-    }
-    s->allocs.push_back(q);
-    s->bytes += n * sizeof(T);
-    *p = (T*)q;
-    return BROV_OK;
-}
-
 // a parked preparation (rti_phase 1 on the resident kernel's split launch) does not survive a call that changes what it factorised
 static void invalidate_preparation(brov_solver* s) { if (s && s->prep_path == 2) s->prep_path = 3; }
 // the shared window in force no longer names rows of the resident trajectory table
@@ -223,8 +199,8 @@ static int upload_grid(brov_solver* s) {
     if (!general_grid(s)) return BROV_OK;
     const int N = s->N;
     if (!s->tsv) {
-        if (int rc = dalloc(s, &s->tsv, (size_t)N)) return rc;
-        if (int rc = dalloc(s, &s->wst, (size_t)(N + 1) * 16)) return rc;
+        if (int rc = s->mem.alloc(&s->tsv, (size_t)N, g_err)) return rc;
+        if (int rc = s->mem.alloc(&s->wst, (size_t)(N + 1) * 16, g_err)) return rc;
     }
     std::vector<double> ts(N), w((size_t)(N + 1) * 16, 0.0);
     for (int i = 0; i < N; i++) {
@@ -306,9 +282,7 @@ extern "C" int brov_create(brov_solver** out, int device, int B, const brov_opts
         g_err = std::string("brov_create: ") + why;
         return BROV_ERR_ARG;
     }
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev < 1 || device < 0 || device >= ndev) {
+    if (!usable_device(device)) {
         g_err = "brov_create: no usable HIP device (this library has no CPU fallback)";
         return BROV_ERR_NO_DEVICE;
     }
@@ -324,7 +298,7 @@ extern "C" int brov_create(brov_solver** out, int device, int B, const brov_opts
     s->opts = *opts;
     const size_t N = opts->N, Bz = B;
     int rc = BROV_OK;
-#define AL(ptr, n) if (rc == BROV_OK) rc = dalloc(s, &s->ptr, (n))
+#define AL(ptr, n) if (rc == BROV_OK) rc = s->mem.alloc(&s->ptr, (n), g_err)
     // x0 | shared reference window | stage parameters in ONE allocation, in the order of brov_tick_host's staging buffer: a tick that
     // rewrites all three (the ROS node does) uploads them with one copy
     AL(x0, Bz * 12 + (size_t)(N + 1) * 16 + Bz * (N + 1) * 16);
@@ -390,7 +364,7 @@ extern "C" void brov_destroy(brov_solver* s) {
     if (s->tick_stream) hipStreamSynchronize(s->tick_stream);
     if (s->copy_stream) hipStreamSynchronize(s->copy_stream);
     // (a caller's own stream is the caller's to drain -- it may not exist any more; hipFree below waits for the device in any case)
-    for (void* p : s->allocs) hipFree(p);
+    s->mem.free_all();
     if (s->traj) hipFree(s->traj);
     if (s->wr_tab) hipFree(s->wr_tab);
     if (s->dbg) hipFree(s->dbg);
@@ -408,7 +382,7 @@ extern "C" void brov_destroy(brov_solver* s) {
 
 extern "C" int brov_batch(const brov_solver* s) { return s ? s->B : 0; }
 extern "C" int brov_horizon(const brov_solver* s) { return s ? s->N : 0; }
-extern "C" size_t brov_device_bytes(const brov_solver* s) { return s ? s->bytes : 0; }
+extern "C" size_t brov_device_bytes(const brov_solver* s) { return s ? s->mem.bytes : 0; }
 
 // Stream ordering.  Everything a solver enqueues runs on the stream its caller names, and brov_tick_host uses the solver's own
 // non-blocking stream and (mailbox path) returns while the tail of its kernel is still running.  A call that arrives on ANOTHER
@@ -475,17 +449,16 @@ static int set_stage_rows(brov_solver* s, double* dst, const double* p, int w, i
     if (per_stage) return copy_in(s, dst, p, tot, host, st);
     HIPCHK(hipSetDevice(s->device));
     const double* src = p;
-    double* tmp = nullptr;
+    ScopedDeviceBuffer<double> tmp;   // host rows: staged on the device until the kernel has read them
     if (!host) { if (int rc = order_behind_last(s, (hipStream_t)st)) return rc; }
     if (host) {
         HIPCHK(sync_last(s));
-        HIPCHK(hipMalloc((void**)&tmp, (size_t)s->B * w * sizeof(double)));
-        hipError_t e = hipMemcpy(tmp, p, (size_t)s->B * w * sizeof(double), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { hipFree(tmp); g_err = hipGetErrorString(e); return BROV_ERR_HIP; }
-        src = tmp;
+        HIPCHK(tmp.init((size_t)s->B * w));
+        HIPCHK(hipMemcpy(tmp.p, p, (size_t)s->B * w * sizeof(double), hipMemcpyHostToDevice));
+        src = tmp.p;
     }
     hipLaunchKernelGGL(bcast_rows_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)st, src, dst, s->B, (int)N1, w);
-    if (host) { hipStreamSynchronize((hipStream_t)st); hipFree(tmp); }
+    if (host) hipStreamSynchronize((hipStream_t)st);
     HIPCHK(hipGetLastError());
     return BROV_OK;
 }
@@ -557,8 +530,8 @@ extern "C" int brov_enable_dist6(brov_solver* s, int on) {
     HIPCHK(sync_last(s));
     if (on && !s->par_rp) {
         const size_t n = (size_t)s->B * (s->N + 1) * 2;
-        int rc = dalloc(s, &s->par_rp, n);
-        if (rc == BROV_OK) rc = dalloc(s, &s->prp_plant, (size_t)s->B * 2);
+        int rc = s->mem.alloc(&s->par_rp, n, g_err);
+        if (rc == BROV_OK) rc = s->mem.alloc(&s->prp_plant, (size_t)s->B * 2, g_err);
         if (rc != BROV_OK) return rc;
         HIPCHK(hipMemset(s->par_rp, 0, n * sizeof(double)));
         HIPCHK(hipMemset(s->prp_plant, 0, (size_t)s->B * 2 * sizeof(double)));
@@ -594,15 +567,11 @@ extern "C" int brov_set_params18_host(brov_solver* s, const double* p18, int per
     HIPCHK(hipSetDevice(s->device));
     HIPCHK(sync_last(s));
     const size_t N1 = s->N + 1, rows = (size_t)s->B * N1, nsrc = (per_stage ? rows : (size_t)s->B) * 18;
-    double* tmp = nullptr;
-    HIPCHK(hipMalloc((void**)&tmp, nsrc * sizeof(double)));
-    hipError_t e = hipMemcpy(tmp, p18, nsrc * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(split_p18_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, nullptr, tmp, s->par, s->par_rp, rows, (int)N1, per_stage);
-        e = hipDeviceSynchronize();
-    }
-    hipFree(tmp);
-    if (e != hipSuccess) { g_err = hipGetErrorString(e); return BROV_ERR_HIP; }
+    ScopedDeviceBuffer<double> tmp;
+    HIPCHK(tmp.init(nsrc));
+    HIPCHK(hipMemcpy(tmp.p, p18, nsrc * sizeof(double), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(split_p18_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, nullptr, tmp.p, s->par, s->par_rp, rows, (int)N1, per_stage);
+    HIPCHK(hipDeviceSynchronize());
     s->pplant_stale = true;
     return BROV_OK;
 }
@@ -764,7 +733,7 @@ extern "C" int brov_plant_wrench_constant_host(brov_solver* s, const double* w) 
     if (!s || !w) return BROV_ERR_ARG;
     HIPCHK(hipSetDevice(s->device));
     HIPCHK(sync_last(s));   // a plant step in flight may still read the buffer
-    if (!s->wr_const) { if (int rc = dalloc(s, &s->wr_const, (size_t)s->B * 6)) return rc; }
+    if (!s->wr_const) { if (int rc = s->mem.alloc(&s->wr_const, (size_t)s->B * 6, g_err)) return rc; }
     HIPCHK(hipMemcpy(s->wr_const, w, (size_t)s->B * 6 * sizeof(double), hipMemcpyHostToDevice));
     s->wr.mode = BROV_WRENCH_CONSTANT; s->wr.w = s->wr_const;
     return BROV_OK;
@@ -784,15 +753,14 @@ extern "C" int brov_plant_wrench_table_host(brov_solver* s, const double* tab, i
     if (!s || !tab || rows < 1) return BROV_ERR_ARG;
     HIPCHK(hipSetDevice(s->device));
     HIPCHK(sync_last(s));
-    if (gain && !s->wr_gain) { if (int rc = dalloc(s, &s->wr_gain, (size_t)s->B)) return rc; }
-    double* nt = nullptr;
-    HIPCHK(hipMalloc((void**)&nt, (size_t)rows * 6 * sizeof(double)));
-    hipError_t e = hipMemcpy(nt, tab, (size_t)rows * 6 * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess && gain) e = hipMemcpy(s->wr_gain, gain, (size_t)s->B * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { hipFree(nt); g_err = hipGetErrorString(e); return BROV_ERR_HIP; }
+    if (gain && !s->wr_gain) { if (int rc = s->mem.alloc(&s->wr_gain, (size_t)s->B, g_err)) return rc; }
+    ScopedDeviceBuffer<double> nt;   // the table in force stays until the new one is complete
+    HIPCHK(nt.init((size_t)rows * 6));
+    HIPCHK(hipMemcpy(nt.p, tab, (size_t)rows * 6 * sizeof(double), hipMemcpyHostToDevice));
+    if (gain) HIPCHK(hipMemcpy(s->wr_gain, gain, (size_t)s->B * sizeof(double), hipMemcpyHostToDevice));
     if (s->wr_tab) hipFree(s->wr_tab);
-    s->wr_tab = nt;
-    s->wr.mode = BROV_WRENCH_TABLE; s->wr.tab = nt; s->wr.rows = rows; s->wr.gain = gain ? s->wr_gain : nullptr;
+    s->wr_tab = nt.release();
+    s->wr.mode = BROV_WRENCH_TABLE; s->wr.tab = s->wr_tab; s->wr.rows = rows; s->wr.gain = gain ? s->wr_gain : nullptr;
     return BROV_OK;
 }
 extern "C" int brov_plant_wrench_off(brov_solver* s) {
@@ -813,7 +781,7 @@ extern "C" int brov_plant_wrench_eval_host(brov_solver* s, int64_t tick, double*
     if (int rc = wrench_tick_ok(s, (long long)tick, "brov_plant_wrench_eval_host")) return rc;
     HIPCHK(hipSetDevice(s->device));
     HIPCHK(sync_last(s));
-    if (!s->wr_eval) { if (int rc = dalloc(s, &s->wr_eval, (size_t)s->B * 6)) return rc; }
+    if (!s->wr_eval) { if (int rc = s->mem.alloc(&s->wr_eval, (size_t)s->B * 6, g_err)) return rc; }
     launch_wrench_eval(s->wr, s->B, (long long)tick, s->wr_eval, s->last_stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s->last_stream));
@@ -946,65 +914,89 @@ static void launch_lds(brov_solver* s, const DevParams& P, int family, hipStream
 }
 
 static int ticks_kernel(const brov_solver* s);
-// Device-side logs of the closed loops (brov_closed_loop_ex, brov_closed_loop_dob): a buffer per HOST log the caller asked for, the start
-// state and the zeroed wrench log enqueued on the loop's stream, everything copied back after the loop's one host wait.  Logs come back
-// only from a loop that completed: a failing call leaves the caller's arrays as they were.
+// DEVICE logs of a run of consecutive ticks, entry j = tick j of the run (x: the plant state AFTER it, behind `lead` rows that belong to the
+// owner); a null block is not logged.  The whole-loop logs of brov_closed_loop_ex / _dob and the one-chunk logs of brov_closed_loop_track are
+// both allocated, handed to the tick runners and freed so.
+struct TickLogs {
+    size_t B = 0, lead = 0;
+    double *dx = nullptr, *du = nullptr, *dw = nullptr, *de = nullptr;
+    int* dst = nullptr;
+    DeviceAllocs mem;
+    double* x(int j) const { return dx ? dx + ((size_t)j + lead) * B * 12 : nullptr; }
+    double* u(int j) const { return du ? du + (size_t)j * B * 4 : nullptr; }
+    double* w(int j) const { return dw ? dw + (size_t)j * B * 6 : nullptr; }
+    double* est(int j) const { return de ? de + (size_t)j * B * 6 : nullptr; }
+    int* status(int j) const { return dst ? dst + (size_t)j * B : nullptr; }
+    // the blocks asked for, for `n` ticks of `B_` instances
+    int alloc(size_t B_, size_t n, size_t lead_, bool x_, bool u_, bool st_, bool w_, bool est_, const char* who) {
+        B = B_; lead = lead_;
+        int rc = BROV_OK;
+        if (x_) rc = mem.alloc(&dx, (n + lead) * B * 12, g_err);
+        if (u_ && rc == BROV_OK) rc = mem.alloc(&du, n * B * 4, g_err);
+        if (st_ && rc == BROV_OK) rc = mem.alloc(&dst, n * B, g_err);
+        if (w_ && rc == BROV_OK) rc = mem.alloc(&dw, n * B * 6, g_err);
+        if (est_ && rc == BROV_OK) rc = mem.alloc(&de, n * B * 6, g_err);
+        if (rc != BROV_OK) g_err = std::string(who) + ": " + g_err;
+        return rc;
+    }
+    void free() { mem.free_all(); }
+};
+// The whole-loop logs of brov_closed_loop_ex / _dob: a device block per HOST log the caller asked for and, ahead of the states, the start
+// state; that and the zeroed wrench log are enqueued on the loop's stream, everything is copied back after the loop's one host wait.  Logs come
+// back only from a loop that completed: a failing call leaves the caller's arrays as they were.
 struct LoopLogs {
-    size_t B = 0, ticks = 0;
+    TickLogs T;
+    size_t ticks = 0;
     double *hx = nullptr, *hu = nullptr, *hw = nullptr, *he = nullptr;   // HOST
     int32_t* hst = nullptr;
-    double *dx = nullptr, *du = nullptr, *dw = nullptr, *de = nullptr;   // DEVICE
-    int* dst = nullptr;
-    double* x(int k) const { return dx ? dx + (size_t)k * B * 12 : nullptr; }   // x(0): before the first tick
-    double* u(int k) const { return du ? du + (size_t)k * B * 4 : nullptr; }
-    double* w(int k) const { return dw ? dw + (size_t)k * B * 6 : nullptr; }
-    double* est(int k) const { return de ? de + (size_t)k * B * 6 : nullptr; }
-    int* status(int k) const { return dst ? dst + (size_t)k * B : nullptr; }
     int begin(const brov_solver* s, int ticks_, double* u_log, double* x_log, int32_t* st_log, double* w_log, double* est_log, hipStream_t st,
               const char* who) {
-        B = s->B; ticks = ticks_; hx = x_log; hu = u_log; hst = st_log; hw = w_log; he = est_log;
+        ticks = ticks_; hx = x_log; hu = u_log; hst = st_log; hw = w_log; he = est_log;
+        if (int rc = T.alloc(s->B, ticks, 1, hx, hu, hst, hw, he, who)) return rc;
+        const size_t B = T.B;
         hipError_t e = hipSuccess;
-        if (hx && e == hipSuccess) e = hipMalloc((void**)&dx, (ticks + 1) * B * 12 * sizeof(double));
-        if (hu && e == hipSuccess) e = hipMalloc((void**)&du, ticks * B * 4 * sizeof(double));
-        if (hst && e == hipSuccess) e = hipMalloc((void**)&dst, ticks * B * sizeof(int));
-        if (hw && e == hipSuccess) e = hipMalloc((void**)&dw, ticks * B * 6 * sizeof(double));
-        if (he && e == hipSuccess) e = hipMalloc((void**)&de, ticks * B * 6 * sizeof(double));
-        if (e != hipSuccess) { g_err = std::string(who) + ": hipMalloc: " + hipGetErrorString(e); return BROV_ERR_ALLOC; }
-        if (dw) e = hipMemsetAsync(dw, 0, ticks * B * 6 * sizeof(double), st);   // (mode OFF: no wrench, nothing writes it)
-        if (dx && e == hipSuccess) e = hipMemcpyAsync(dx, s->x0, B * 12 * sizeof(double), hipMemcpyDeviceToDevice, st);
+        if (T.dw) e = hipMemsetAsync(T.dw, 0, ticks * B * 6 * sizeof(double), st);   // (mode OFF: no wrench, nothing writes it)
+        if (T.dx && e == hipSuccess) e = hipMemcpyAsync(T.dx, s->x0, B * 12 * sizeof(double), hipMemcpyDeviceToDevice, st);
         if (e != hipSuccess) { g_err = std::string(who) + ": log initialisation failed"; return BROV_ERR_HIP; }
         return BROV_OK;
     }
     // after the host wait: copies back when the loop succeeded, frees in any case; returns rc
     int end(int rc) {
+        const size_t B = T.B;
         if (rc == BROV_OK) {
-            if (dx) hipMemcpy(hx, dx, (ticks + 1) * B * 12 * sizeof(double), hipMemcpyDeviceToHost);
-            if (du) hipMemcpy(hu, du, ticks * B * 4 * sizeof(double), hipMemcpyDeviceToHost);
-            if (dst) hipMemcpy(hst, dst, ticks * B * sizeof(int), hipMemcpyDeviceToHost);
-            if (dw) hipMemcpy(hw, dw, ticks * B * 6 * sizeof(double), hipMemcpyDeviceToHost);
-            if (de) hipMemcpy(he, de, ticks * B * 6 * sizeof(double), hipMemcpyDeviceToHost);
+            if (T.dx) hipMemcpy(hx, T.dx, (ticks + 1) * B * 12 * sizeof(double), hipMemcpyDeviceToHost);
+            if (T.du) hipMemcpy(hu, T.du, ticks * B * 4 * sizeof(double), hipMemcpyDeviceToHost);
+            if (T.dst) hipMemcpy(hst, T.dst, ticks * B * sizeof(int), hipMemcpyDeviceToHost);
+            if (T.dw) hipMemcpy(hw, T.dw, ticks * B * 6 * sizeof(double), hipMemcpyDeviceToHost);
+            if (T.de) hipMemcpy(he, T.de, ticks * B * 6 * sizeof(double), hipMemcpyDeviceToHost);
         }
-        for (void* q : {(void*)dx, (void*)du, (void*)dst, (void*)dw, (void*)de})
-            if (q) hipFree(q);
+        T.free();
         return rc;
     }
 };
-// DEVICE logs of a run of consecutive ticks, entry j = tick j of the run (x: the plant state AFTER it); a null block is not logged.  The
-// whole-loop logs of brov_closed_loop_ex / _dob and the one-chunk logs of brov_closed_loop_track are both handed to the tick runners so.
-struct TickLogs {
-    size_t B = 0;
-    double *dx = nullptr, *du = nullptr, *dw = nullptr, *de = nullptr;
-    int* dst = nullptr;
-    double* x(int j) const { return dx ? dx + (size_t)j * B * 12 : nullptr; }
-    double* u(int j) const { return du ? du + (size_t)j * B * 4 : nullptr; }
-    double* w(int j) const { return dw ? dw + (size_t)j * B * 6 : nullptr; }
-    double* est(int j) const { return de ? de + (size_t)j * B * 6 : nullptr; }
-    int* status(int j) const { return dst ? dst + (size_t)j * B : nullptr; }
-};
-static TickLogs tick_logs(const LoopLogs& L) {
-    TickLogs T;
-    T.B = L.B; T.dx = L.x(1); T.du = L.du; T.dw = L.dw; T.de = L.de; T.dst = L.dst;
-    return T;
+// what the closed-loop entry points ask of their arguments alike, reported under the caller's name (an observer and an estimator are optional
+// here; brov_closed_loop_dob asks for its observer itself)
+static int loop_args_ok(const brov_solver* s, const brov_ekf* e, const brov_rls* r, int rls_mode, int ticks, int ncols, double dt, int substeps,
+                        const char* who) {
+    if (!s || (r && !e) || ticks < 1 || !s->traj || (ncols != 12 && ncols != 16) || !(dt > 0.0) || substeps < 1) {
+        g_err = std::string(who) + ": bad argument (needs ticks >= 1, ncols 12 or 16, dt > 0, substeps >= 1, an observer with an estimator, and a "
+                                   "trajectory table, see brov_traj_set_host)";
+        return BROV_ERR_ARG;
+    }
+    if ((e && brov_ekf_batch(e) != s->B) || (r && brov_rls_batch(r) != s->B)) { g_err = std::string(who) + ": batch sizes differ"; return BROV_ERR_ARG; }
+    if (r && rls_mode != BROV_RLS_APPLY_DISTURBANCE && rls_mode != BROV_RLS_APPLY_MODEL) { g_err = std::string(who) + ": unknown rls_mode"; return BROV_ERR_ARG; }
+    return wrench_tick_ok(s, s->wr_tick + ticks - 1, who);
+}
+// the statuses of the step just enqueued on `st` into a DEVICE log row (null: not logged)
+static void gather_status(const brov_solver* s, int* out, hipStream_t st) {
+    if (out) hipLaunchKernelGGL(gather_status_kernel, dim3((unsigned)((s->B + 255) / 256)), dim3(256), 0, st, s->res, out, (int)s->B);
+}
+// the end of a closed loop: its one host wait, then a launch error nobody has picked up, then the code
+static int finish_loop(hipStream_t st, int rc) {
+    hipError_t err = hipStreamSynchronize(st);
+    if (rc == BROV_OK && err == hipSuccess) err = hipGetLastError();
+    if (rc == BROV_OK && err != hipSuccess) { g_err = hipGetErrorString(err); rc = BROV_ERR_HIP; }
+    return rc;
 }
 // whether brov_closed_loop_ex runs `ticks` ticks from `line0` as one launch, and with which kernel.
 // One launch for the whole loop where the fused kernels serve the solver and every window is rows of the table in place (round 5,
@@ -1020,7 +1012,6 @@ static bool loop_in_one_launch(const brov_solver* s, int ticks, int line0, int n
 // `n` ticks of the plain loop (window -> RTI step -> plant step) from trajectory row `line` on `st`, logged into T
 static int run_loop_ticks(brov_solver* s, int n, int line, int ncols, double dt, int substeps, bool one_launch, int which, const TickLogs& T,
                           hipStream_t st) {
-    const size_t B = s->B;
     int rc = BROV_OK;
     if (one_launch) {
         rc = brov_set_yref_from_traj(s, line, 16, st);
@@ -1043,7 +1034,7 @@ static int run_loop_ticks(brov_solver* s, int n, int line, int ncols, double dt,
         launch_window(s->traj, s->traj_rows, nullptr, line + k, 1, s->N, ncols, s->yref_sh, st);
         s->yref_shared = true;
         rc = brov_solve_phase(s, st, 0);
-        if (T.status(k)) hipLaunchKernelGGL(gather_status_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, s->res, T.status(k), (int)B);
+        gather_status(s, T.status(k), st);
         plant_step_on(s, dt, substeps, T.x(k), T.u(k), T.w(k), st);
     }
     return rc;
@@ -1062,7 +1053,7 @@ static int run_dob_ticks(brov_solver* s, brov_ekf* e, brov_rls* r, int rls_mode,
         rc = brov_set_yref_from_traj(s, line + k, ncols, st);
         if (rc == BROV_OK) rc = brov_solve_phase(s, st, 0);
         if (rc != BROV_OK) break;
-        if (T.status(k)) hipLaunchKernelGGL(gather_status_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, s->res, T.status(k), (int)B);
+        gather_status(s, T.status(k), st);
         ensure_plant_params(s, st);   // (the hand-off below rewrites the controller's stage 0, which a plant without parameters of its own follows)
         plant_step_on(s, dt, substeps, T.x(k), T.u(k), T.w(k), st);
         if (!sub(brov_ekf_update_from_solver(e, s, st), brov_ekf_last_error())) break;
@@ -1078,11 +1069,7 @@ extern "C" int brov_closed_loop(brov_solver* s, int ticks, int line0, int ncols,
 }
 extern "C" int brov_closed_loop_ex(brov_solver* s, int ticks, int line0, int ncols, double dt, int substeps, double* u_log, double* x_log,
                                    int32_t* st_log, double* w_log) {
-    if (!s || ticks < 1 || !s->traj || (ncols != 12 && ncols != 16) || !(dt > 0.0) || substeps < 1) {
-        g_err = "brov_closed_loop: bad argument (needs a trajectory table, see brov_traj_set_host)";
-        return BROV_ERR_ARG;
-    }
-    if (int wrc = wrench_tick_ok(s, s->wr_tick + ticks - 1, "brov_closed_loop")) return wrc;
+    if (int rc = loop_args_ok(s, nullptr, nullptr, 0, ticks, ncols, dt, substeps, "brov_closed_loop")) return rc;
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = s->last_stream;
     ensure_plant_params(s, st);
@@ -1090,31 +1077,21 @@ extern "C" int brov_closed_loop_ex(brov_solver* s, int ticks, int line0, int nco
     int rc = L.begin(s, ticks, u_log, x_log, st_log, w_log, nullptr, st, "brov_closed_loop");
     int which = 0;
     const bool one_launch = loop_in_one_launch(s, ticks, line0, ncols, &which);
-    if (rc == BROV_OK) rc = run_loop_ticks(s, ticks, line0, ncols, dt, substeps, one_launch, which, tick_logs(L), st);
-    hipError_t e = hipStreamSynchronize(st);
-    if (rc == BROV_OK && e != hipSuccess) { g_err = hipGetErrorString(e); rc = BROV_ERR_HIP; }
-    return L.end(rc);
+    if (rc == BROV_OK) rc = run_loop_ticks(s, ticks, line0, ncols, dt, substeps, one_launch, which, L.T, st);
+    return L.end(finish_loop(st, rc));
 }
 
 // The DOB / AMPC loop on the device: per tick the five public calls of the header, on one stream, one host wait at the end.
 extern "C" int brov_closed_loop_dob(brov_solver* s, brov_ekf* e, brov_rls* r, int rls_mode, int ticks, int line0, int ncols, double dt, int substeps,
                                     double* u_log, double* x_log, int32_t* st_log, double* w_log, double* est_log) {
-    if (!s || !e || ticks < 1 || !s->traj || (ncols != 12 && ncols != 16) || !(dt > 0.0) || substeps < 1) {
-        g_err = "brov_closed_loop_dob: bad argument (needs an observer and a trajectory table, see brov_traj_set_host)";
-        return BROV_ERR_ARG;
-    }
-    if (brov_ekf_batch(e) != s->B || (r && brov_rls_batch(r) != s->B)) { g_err = "brov_closed_loop_dob: batch sizes differ"; return BROV_ERR_ARG; }
-    if (r && rls_mode != BROV_RLS_APPLY_DISTURBANCE && rls_mode != BROV_RLS_APPLY_MODEL) { g_err = "brov_closed_loop_dob: unknown rls_mode"; return BROV_ERR_ARG; }
-    if (int wrc = wrench_tick_ok(s, s->wr_tick + ticks - 1, "brov_closed_loop_dob")) return wrc;
+    if (!e) { g_err = "brov_closed_loop_dob: bad argument (needs an observer)"; return BROV_ERR_ARG; }
+    if (int rc = loop_args_ok(s, e, r, rls_mode, ticks, ncols, dt, substeps, "brov_closed_loop_dob")) return rc;
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = s->last_stream;
     LoopLogs L;
     int rc = L.begin(s, ticks, u_log, x_log, st_log, w_log, est_log, st, "brov_closed_loop_dob");
-    if (rc == BROV_OK) rc = run_dob_ticks(s, e, r, rls_mode, ticks, line0, ncols, dt, substeps, tick_logs(L), st, "brov_closed_loop_dob");
-    hipError_t err = hipStreamSynchronize(st);
-    if (rc == BROV_OK && err == hipSuccess) err = hipGetLastError();
-    if (rc == BROV_OK && err != hipSuccess) { g_err = hipGetErrorString(err); rc = BROV_ERR_HIP; }
-    return L.end(rc);
+    if (rc == BROV_OK) rc = run_dob_ticks(s, e, r, rls_mode, ticks, line0, ncols, dt, substeps, L.T, st, "brov_closed_loop_dob");
+    return L.end(finish_loop(st, rc));
 }
 
 namespace brov {
@@ -1126,31 +1103,19 @@ int track_accumulate_on(brov_track* t, const double* x, const double* u, const i
 // every chunk on the same stream, one host wait at the end.
 extern "C" int brov_closed_loop_track(brov_solver* s, brov_ekf* e, brov_rls* r, int rls_mode, brov_track* t, int ticks, int line0, int ncols,
                                       double dt, int substeps, int chunk) {
-    if (!s || !t || (r && !e) || ticks < 1 || chunk < 0 || !s->traj || (ncols != 12 && ncols != 16) || !(dt > 0.0) || substeps < 1) {
-        g_err = "brov_closed_loop_track: bad argument (needs a tracker, ticks >= 1, chunk >= 0 and a trajectory table, see brov_traj_set_host)";
-        return BROV_ERR_ARG;
-    }
-    if (brov_track_batch(t) != s->B || (e && brov_ekf_batch(e) != s->B) || (r && brov_rls_batch(r) != s->B)) {
-        g_err = "brov_closed_loop_track: batch sizes differ";
-        return BROV_ERR_ARG;
-    }
-    if (r && rls_mode != BROV_RLS_APPLY_DISTURBANCE && rls_mode != BROV_RLS_APPLY_MODEL) { g_err = "brov_closed_loop_track: unknown rls_mode"; return BROV_ERR_ARG; }
-    if (int wrc = wrench_tick_ok(s, s->wr_tick + ticks - 1, "brov_closed_loop_track")) return wrc;
+    if (!t || chunk < 0) { g_err = "brov_closed_loop_track: bad argument (needs a tracker and chunk >= 0)"; return BROV_ERR_ARG; }
+    if (int rc = loop_args_ok(s, e, r, rls_mode, ticks, ncols, dt, substeps, "brov_closed_loop_track")) return rc;
+    if (brov_track_batch(t) != s->B) { g_err = "brov_closed_loop_track: batch sizes differ"; return BROV_ERR_ARG; }
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = s->last_stream;
     if (!e) ensure_plant_params(s, st);
     int which = 0;
     const bool one_launch = !e && loop_in_one_launch(s, ticks, line0, ncols, &which);   // decided for the whole run, as brov_closed_loop_ex does
-    const size_t B = s->B, C = (size_t)std::min(chunk == 0 ? 64 : chunk, ticks);
+    const int C = std::min(chunk == 0 ? 64 : chunk, ticks);
     TickLogs T;
-    T.B = B;
-    hipError_t he = hipMalloc((void**)&T.dx, C * B * 12 * sizeof(double));
-    if (he == hipSuccess) he = hipMalloc((void**)&T.du, C * B * 4 * sizeof(double));
-    if (he == hipSuccess) he = hipMalloc((void**)&T.dst, C * B * sizeof(int));
-    int rc = BROV_OK;
-    if (he != hipSuccess) { (void)hipGetLastError(); g_err = std::string("brov_closed_loop_track: hipMalloc: ") + hipGetErrorString(he); rc = BROV_ERR_ALLOC; }
-    for (int k0 = 0; k0 < ticks && rc == BROV_OK; k0 += (int)C) {
-        const int n = std::min((int)C, ticks - k0);
+    int rc = T.alloc(s->B, C, 0, true, true, true, false, false, "brov_closed_loop_track");
+    for (int k0 = 0; k0 < ticks && rc == BROV_OK; k0 += C) {
+        const int n = std::min(C, ticks - k0);
         rc = e ? run_dob_ticks(s, e, r, rls_mode, n, line0 + k0, ncols, dt, substeps, T, st, "brov_closed_loop_track")
                : run_loop_ticks(s, n, line0 + k0, ncols, dt, substeps, one_launch, which, T, st);
         if (rc != BROV_OK) break;
@@ -1158,11 +1123,8 @@ extern "C" int brov_closed_loop_track(brov_solver* s, brov_ekf* e, brov_rls* r, 
         rc = track_accumulate_on(t, T.dx, T.du, T.dst, n, s->traj, s->traj_rows, line0 + k0 + 1, s->opts.lbu, s->opts.ubu, st);
         if (rc != BROV_OK) g_err = std::string("brov_closed_loop_track: ") + brov_track_last_error();
     }
-    hipError_t err = hipStreamSynchronize(st);
-    if (rc == BROV_OK && err == hipSuccess) err = hipGetLastError();
-    if (rc == BROV_OK && err != hipSuccess) { g_err = hipGetErrorString(err); rc = BROV_ERR_HIP; }
-    for (void* q : {(void*)T.dx, (void*)T.du, (void*)T.dst})
-        if (q) hipFree(q);
+    rc = finish_loop(st, rc);
+    T.free();
     return rc;
 }
 
@@ -1265,7 +1227,7 @@ extern "C" int brov_solve_ticks(brov_solver* s, void* stream, int ticks, int row
             if (k > 0 && row_stride > 0)
                 if (int rc = brov_set_yref_from_traj(s, line0 + k * row_stride, ncols, stream)) return rc;
             if (int rc = brov_solve_phase(s, stream, 0)) return rc;
-            if (status_log) hipLaunchKernelGGL(gather_status_kernel, dim3((unsigned)((s->B + 255) / 256)), dim3(256), 0, st, s->res, status_log + (size_t)k * s->B, (int)s->B);
+            gather_status(s, status_log ? status_log + (size_t)k * s->B : nullptr, st);
         }
         HIPCHK(hipGetLastError());
         return BROV_OK;

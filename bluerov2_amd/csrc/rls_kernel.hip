@@ -218,20 +218,12 @@ __global__ void rls_apply_kernel(int B, int stages, int model, double cc, double
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
+#include "host_common.hpp"   // (here, not at the top: the kernels above keep their line numbers in the compiler's resource report)
+
 using namespace brov;
 
 static thread_local std::string g_rls_err;
-#define RLSCHK(call)                                                                                          \
-    do {                                                                                                      \
-        hipError_t e_ = (call);                                                                               \
-        if (e_ != hipSuccess) {                                                                               \
-            g_rls_err = std::string(#call) + ": " + hipGetErrorString(e_);                                    \
-            (void)hipGetLastError();                                                                          \
-            return (e_ == hipErrorNoDevice || e_ == hipErrorInvalidDevice || e_ == hipErrorInsufficientDriver) \
-                       ? BROV_ERR_NO_DEVICE                                                                   \
-                       : BROV_ERR_HIP;                                                                        \
-        }                                                                                                     \
-    } while (0)
+#define HIPCHK(call) BROV_HIPCHK(g_rls_err, call)
 
 struct brov_rls {
     int device = 0, B = 0, G = 0;
@@ -240,9 +232,8 @@ struct brov_rls {
     int *cs = nullptr, *hs = nullptr, *cl = nullptr, *hl = nullptr, *status = nullptr;
     double *y = nullptr, *acc = nullptr, *vel = nullptr, *rpy = nullptr, *vprev = nullptr, *wf = nullptr, *mp = nullptr;
     hipStream_t last_stream = nullptr, upd_stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    bool ev_valid = false;
-    std::vector<void*> allocs;
+    KernelTimer timer;   // around the last update kernel
+    DeviceAllocs mem;
 };
 
 extern "C" const char* brov_rls_last_error(void) { return g_rls_err.c_str(); }
@@ -264,22 +255,12 @@ extern "C" void brov_rls_default_params(brov_rls_params* p) {
     p->rotor_constant = 0.026546960744430276;
 }
 
-template <typename T>
-static int rls_alloc(brov_rls* r, T** p, size_t n) {
-    void* q = nullptr;
-    if (hipMalloc(&q, n * sizeof(T)) != hipSuccess) { g_rls_err = "hipMalloc failed"; return BROV_ERR_ALLOC; }
-    r->allocs.push_back(q);
-    *p = (T*)q;
-    return BROV_OK;
-}
-
 extern "C" void brov_rls_destroy(brov_rls* r) {
     if (!r) return;
     (void)hipSetDevice(r->device);
     if (r->last_stream) (void)hipStreamSynchronize(r->last_stream);
-    for (void* q : r->allocs) (void)hipFree(q);
-    for (auto& ev : r->ev)
-        if (ev) (void)hipEventDestroy(ev);
+    r->mem.free_all();
+    r->timer.destroy();
     delete r;
 }
 
@@ -288,15 +269,15 @@ extern "C" int brov_rls_batch(const brov_rls* r) { return r ? r->B : 0; }
 // windows emptied; every pointer is written in full before it is next read
 static int empty_windows(brov_rls* r) {
     const size_t n = (size_t)r->G * sizeof(int);
-    RLSCHK(hipMemset(r->cs, 0, n));
-    RLSCHK(hipMemset(r->hs, 0, n));
-    RLSCHK(hipMemset(r->cl, 0, n));
-    RLSCHK(hipMemset(r->hl, 0, n));
+    HIPCHK(hipMemset(r->cs, 0, n));
+    HIPCHK(hipMemset(r->hs, 0, n));
+    HIPCHK(hipMemset(r->cl, 0, n));
+    HIPCHK(hipMemset(r->hl, 0, n));
     return BROV_OK;
 }
 
 static int sync_last(brov_rls* r) {
-    RLSCHK(hipStreamSynchronize(r->last_stream));
+    HIPCHK(hipStreamSynchronize(r->last_stream));
     return BROV_OK;
 }
 
@@ -307,33 +288,33 @@ static int upload_state(brov_rls* r, const double* th, const double* P, const do
         std::vector<double> h(4 * G);
         for (size_t g = 0; g < G; g++)
             for (int i = 0; i < 4; i++) h[i * G + g] = th[g * 4 + i];
-        RLSCHK(hipMemcpy(r->theta, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(r->theta, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
     }
     if (P) {
         std::vector<double> h(16 * G);
         for (size_t g = 0; g < G; g++)
             for (int i = 0; i < 16; i++) h[i * G + g] = P[g * 16 + i];
-        RLSCHK(hipMemcpy(r->P, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(r->P, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
     }
-    if (lam) RLSCHK(hipMemcpy(r->lam, lam, G * sizeof(double), hipMemcpyHostToDevice));
+    if (lam) HIPCHK(hipMemcpy(r->lam, lam, G * sizeof(double), hipMemcpyHostToDevice));
     return BROV_OK;
 }
 
 extern "C" int brov_rls_reset(brov_rls* r) {
     if (!r) return BROV_ERR_ARG;
-    RLSCHK(hipSetDevice(r->device));
+    HIPCHK(hipSetDevice(r->device));
     if (int rc = sync_last(r)) return rc;
     const size_t G = r->G;
     std::vector<double> th(4 * G, 0.0), P(16 * G, 0.0), lam(G, r->par.lambda0);
     for (size_t g = 0; g < G; g++)
         for (int i = 0; i < 4; i++) P[g * 16 + i * 5] = r->par.p0;
     if (int rc = upload_state(r, th.data(), P.data(), lam.data())) return rc;
-    RLSCHK(hipMemset(r->vprev, 0, G * sizeof(double)));
-    RLSCHK(hipMemset(r->F, 0, G * sizeof(double)));
-    RLSCHK(hipMemset(r->e, 0, G * sizeof(double)));
-    RLSCHK(hipMemset(r->mp, 0, G * sizeof(double)));
-    RLSCHK(hipMemset(r->wf, 0, (size_t)r->B * 6 * sizeof(double)));
-    RLSCHK(hipMemset(r->status, 0, (size_t)r->B * sizeof(int)));
+    HIPCHK(hipMemset(r->vprev, 0, G * sizeof(double)));
+    HIPCHK(hipMemset(r->F, 0, G * sizeof(double)));
+    HIPCHK(hipMemset(r->e, 0, G * sizeof(double)));
+    HIPCHK(hipMemset(r->mp, 0, G * sizeof(double)));
+    HIPCHK(hipMemset(r->wf, 0, (size_t)r->B * 6 * sizeof(double)));
+    HIPCHK(hipMemset(r->status, 0, (size_t)r->B * sizeof(int)));
     return empty_windows(r);
 }
 
@@ -350,27 +331,25 @@ extern "C" int brov_rls_create(brov_rls** out, int device, int B, const brov_rls
         g_rls_err = "brov_rls_create: need 0 < lambda_min <= lambda0 <= lambda_max and dt > 0";
         return BROV_ERR_ARG;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
+    if (!usable_device(device)) {
         g_rls_err = "brov_rls_create: no usable HIP device (the estimator has no CPU path)";
         return BROV_ERR_NO_DEVICE;
     }
-    RLSCHK(hipSetDevice(device));
+    HIPCHK(hipSetDevice(device));
     brov_rls* r = new brov_rls();
     r->device = device; r->B = B; r->G = 4 * B; r->par = q;
     const size_t G = r->G;
     int rc = BROV_OK;
-    if ((rc = rls_alloc(r, &r->theta, 4 * G)) || (rc = rls_alloc(r, &r->P, 16 * G)) || (rc = rls_alloc(r, &r->lam, G)) ||
-        (rc = rls_alloc(r, &r->F, G)) || (rc = rls_alloc(r, &r->e, G)) || (rc = rls_alloc(r, &r->ws, (size_t)q.n_short * G)) ||
-        (rc = rls_alloc(r, &r->wl, (size_t)q.n_long * G)) || (rc = rls_alloc(r, &r->cs, G)) || (rc = rls_alloc(r, &r->hs, G)) ||
-        (rc = rls_alloc(r, &r->cl, G)) || (rc = rls_alloc(r, &r->hl, G)) || (rc = rls_alloc(r, &r->status, (size_t)B)) ||
-        (rc = rls_alloc(r, &r->y, G)) || (rc = rls_alloc(r, &r->acc, G)) || (rc = rls_alloc(r, &r->vel, G)) ||
-        (rc = rls_alloc(r, &r->rpy, (size_t)B * 3)) || (rc = rls_alloc(r, &r->vprev, G)) || (rc = rls_alloc(r, &r->wf, (size_t)B * 6)) ||
-        (rc = rls_alloc(r, &r->mp, G))) {
+    auto al = [&](auto** p, size_t n) { return rc = r->mem.alloc(p, n, g_rls_err); };
+    if (al(&r->theta, 4 * G) || al(&r->P, 16 * G) || al(&r->lam, G) || al(&r->F, G) || al(&r->e, G) || al(&r->ws, (size_t)q.n_short * G) ||
+        al(&r->wl, (size_t)q.n_long * G) || al(&r->cs, G) || al(&r->hs, G) || al(&r->cl, G) || al(&r->hl, G) || al(&r->status, (size_t)B) ||
+        al(&r->y, G) || al(&r->acc, G) || al(&r->vel, G) || al(&r->rpy, (size_t)B * 3) || al(&r->vprev, G) || al(&r->wf, (size_t)B * 6) ||
+        al(&r->mp, G)) {
+        g_rls_err = "brov_rls_create: " + g_rls_err;
         brov_rls_destroy(r);
         return rc;
     }
-    if (hipEventCreate(&r->ev[0]) != hipSuccess || hipEventCreate(&r->ev[1]) != hipSuccess) {
+    if (r->timer.create() != hipSuccess) {
         g_rls_err = "brov_rls_create: device initialisation failed";
         brov_rls_destroy(r);
         return BROV_ERR_HIP;
@@ -383,7 +362,7 @@ extern "C" int brov_rls_create(brov_rls** out, int device, int B, const brov_rls
 
 extern "C" int brov_rls_set_state_host(brov_rls* r, const double* theta, const double* P, const double* lambda) {
     if (!r) return BROV_ERR_ARG;
-    RLSCHK(hipSetDevice(r->device));
+    HIPCHK(hipSetDevice(r->device));
     if (int rc = sync_last(r)) return rc;
     if (int rc = upload_state(r, theta, P, lambda)) return rc;
     return empty_windows(r);
@@ -391,24 +370,24 @@ extern "C" int brov_rls_set_state_host(brov_rls* r, const double* theta, const d
 
 extern "C" int brov_rls_get_state_host(brov_rls* r, double* theta, double* P, double* lambda, double* F, double* e) {
     if (!r) return BROV_ERR_ARG;
-    RLSCHK(hipSetDevice(r->device));
+    HIPCHK(hipSetDevice(r->device));
     if (int rc = sync_last(r)) return rc;
     const size_t G = r->G;
     if (theta) {
         std::vector<double> h(4 * G);
-        RLSCHK(hipMemcpy(h.data(), r->theta, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(h.data(), r->theta, h.size() * sizeof(double), hipMemcpyDeviceToHost));
         for (size_t g = 0; g < G; g++)
             for (int i = 0; i < 4; i++) theta[g * 4 + i] = h[i * G + g];
     }
     if (P) {
         std::vector<double> h(16 * G);
-        RLSCHK(hipMemcpy(h.data(), r->P, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(h.data(), r->P, h.size() * sizeof(double), hipMemcpyDeviceToHost));
         for (size_t g = 0; g < G; g++)
             for (int i = 0; i < 16; i++) P[g * 16 + i] = h[i * G + g];
     }
-    if (lambda) RLSCHK(hipMemcpy(lambda, r->lam, G * sizeof(double), hipMemcpyDeviceToHost));
-    if (F) RLSCHK(hipMemcpy(F, r->F, G * sizeof(double), hipMemcpyDeviceToHost));
-    if (e) RLSCHK(hipMemcpy(e, r->e, G * sizeof(double), hipMemcpyDeviceToHost));
+    if (lambda) HIPCHK(hipMemcpy(lambda, r->lam, G * sizeof(double), hipMemcpyDeviceToHost));
+    if (F) HIPCHK(hipMemcpy(F, r->F, G * sizeof(double), hipMemcpyDeviceToHost));
+    if (e) HIPCHK(hipMemcpy(e, r->e, G * sizeof(double), hipMemcpyDeviceToHost));
     return BROV_OK;
 }
 
@@ -420,31 +399,30 @@ static int launch_update(brov_rls* r, const double* y, const double* acc, const 
     a.theta = r->theta; a.P = r->P; a.lam = r->lam; a.F = r->F; a.e = r->e; a.ws = r->ws; a.wl = r->wl;
     a.cs = r->cs; a.hs = r->hs; a.cl = r->cl; a.hl = r->hl;
     a.y = y; a.acc = acc; a.vel = vel; a.rpy = rpy; a.wf = r->wf; a.mp = r->mp; a.status = r->status;
-    RLSCHK(hipEventRecord(r->ev[0], st));
+    HIPCHK(r->timer.start(st));
     hipLaunchKernelGGL(rls_update_kernel, dim3((r->G + kRlsBlock - 1) / kRlsBlock), dim3(kRlsBlock), 0, st, a);
-    RLSCHK(hipGetLastError());
-    RLSCHK(hipEventRecord(r->ev[1], st));
-    r->ev_valid = true;
+    HIPCHK(hipGetLastError());
+    HIPCHK(r->timer.stop(st));
     r->last_stream = r->upd_stream = st;
     return BROV_OK;
 }
 
 extern "C" int brov_rls_update_device(brov_rls* r, const double* y, const double* acc, const double* vel, const double* rpy, void* stream) {
     if (!r || !y || !acc || !vel || !rpy) { g_rls_err = "brov_rls_update_device: null argument"; return BROV_ERR_ARG; }
-    RLSCHK(hipSetDevice(r->device));
+    HIPCHK(hipSetDevice(r->device));
     return launch_update(r, y, acc, vel, rpy, (hipStream_t)stream);
 }
 
 extern "C" int brov_rls_update_host(brov_rls* r, const double* y, const double* acc, const double* vel, const double* rpy, void* stream) {
     if (!r || !y || !acc || !vel || !rpy) { g_rls_err = "brov_rls_update_host: null argument"; return BROV_ERR_ARG; }
-    RLSCHK(hipSetDevice(r->device));
+    HIPCHK(hipSetDevice(r->device));
     hipStream_t st = (hipStream_t)stream;
     if (r->last_stream != st) if (int rc = sync_last(r)) return rc;   // the input buffers may still be read by the last update
     const size_t G = r->G;
-    RLSCHK(hipMemcpyAsync(r->y, y, G * sizeof(double), hipMemcpyHostToDevice, st));
-    RLSCHK(hipMemcpyAsync(r->acc, acc, G * sizeof(double), hipMemcpyHostToDevice, st));
-    RLSCHK(hipMemcpyAsync(r->vel, vel, G * sizeof(double), hipMemcpyHostToDevice, st));
-    RLSCHK(hipMemcpyAsync(r->rpy, rpy, (size_t)r->B * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(r->y, y, G * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(r->acc, acc, G * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(r->vel, vel, G * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(r->rpy, rpy, (size_t)r->B * 3 * sizeof(double), hipMemcpyHostToDevice, st));
     return launch_update(r, r->y, r->acc, r->vel, r->rpy, st);
 }
 
@@ -453,53 +431,49 @@ extern "C" int brov_rls_update_from_ekf(brov_rls* r, const brov_ekf* ekf, brov_s
         g_rls_err = "brov_rls_update_from_ekf: batch sizes differ";
         return BROV_ERR_ARG;
     }
-    RLSCHK(hipSetDevice(r->device));
+    HIPCHK(hipSetDevice(r->device));
     hipStream_t st = (hipStream_t)stream;
     if (brov_order_stream(s, stream) != BROV_OK) { g_rls_err = "brov_rls_update_from_ekf: could not order behind the solver's last stream"; return BROV_ERR_HIP; }
     if (ekf_wait_last_update(ekf, st) != BROV_OK) { g_rls_err = "brov_rls_update_from_ekf: could not order behind the EKF's last update"; return BROV_ERR_HIP; }
     if (r->last_stream != st) if (int rc = sync_last(r)) return rc;
     hipLaunchKernelGGL(rls_inputs_kernel, dim3((r->G + kRlsBlock - 1) / kRlsBlock), dim3(kRlsBlock), 0, st, r->G, r->par.dt,
                        (const double*)brov_x0_device(s), brov_ekf_x_device(ekf), r->vprev, r->y, r->acc, r->vel, r->rpy);
-    RLSCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return launch_update(r, r->y, r->acc, r->vel, r->rpy, st);
 }
 
 extern "C" int brov_rls_apply_to_solver(brov_rls* r, brov_solver* s, int mode, void* stream) {
     if (!r || !s || brov_batch(s) != r->B) { g_rls_err = "brov_rls_apply_to_solver: batch sizes differ"; return BROV_ERR_ARG; }
     if (mode != BROV_RLS_APPLY_DISTURBANCE && mode != BROV_RLS_APPLY_MODEL) { g_rls_err = "brov_rls_apply_to_solver: unknown mode"; return BROV_ERR_ARG; }
-    RLSCHK(hipSetDevice(r->device));
+    HIPCHK(hipSetDevice(r->device));
     brov_opts o;
     if (brov_get_opts(s, &o) != BROV_OK) return BROV_ERR_ARG;
     const int stages = o.N + 1;
     const long long n = (long long)r->B * stages;
     hipStream_t st = (hipStream_t)stream;
     if (brov_order_stream(s, stream) != BROV_OK) { g_rls_err = "brov_rls_apply_to_solver: could not order behind the solver's last stream"; return BROV_ERR_HIP; }
-    if (r->ev_valid && r->upd_stream != st) RLSCHK(hipStreamWaitEvent(st, r->ev[1], 0));
+    if (r->timer.valid && r->upd_stream != st) HIPCHK(hipStreamWaitEvent(st, r->timer.stop_event(), 0));
     hipLaunchKernelGGL(rls_apply_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, r->B, stages, mode,
                        r->par.compensate_coef, r->par.rotor_constant, (const double*)r->theta, brov_params_device(s));
-    RLSCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     r->last_stream = st;
     return BROV_OK;
 }
 
 extern "C" int brov_rls_get_outputs_host(brov_rls* r, double* mpc_p, double* wf_env, int* status) {
     if (!r) return BROV_ERR_ARG;
-    RLSCHK(hipSetDevice(r->device));
+    HIPCHK(hipSetDevice(r->device));
     if (int rc = sync_last(r)) return rc;
-    if (mpc_p) RLSCHK(hipMemcpy(mpc_p, r->mp, (size_t)r->G * sizeof(double), hipMemcpyDeviceToHost));
-    if (wf_env) RLSCHK(hipMemcpy(wf_env, r->wf, (size_t)r->B * 6 * sizeof(double), hipMemcpyDeviceToHost));
-    if (status) RLSCHK(hipMemcpy(status, r->status, (size_t)r->B * sizeof(int), hipMemcpyDeviceToHost));
+    if (mpc_p) HIPCHK(hipMemcpy(mpc_p, r->mp, (size_t)r->G * sizeof(double), hipMemcpyDeviceToHost));
+    if (wf_env) HIPCHK(hipMemcpy(wf_env, r->wf, (size_t)r->B * 6 * sizeof(double), hipMemcpyDeviceToHost));
+    if (status) HIPCHK(hipMemcpy(status, r->status, (size_t)r->B * sizeof(int), hipMemcpyDeviceToHost));
     return BROV_OK;
 }
 
 extern "C" const double* brov_rls_theta_device(const brov_rls* r) { return r ? r->theta : nullptr; }
 
 extern "C" int brov_rls_last_update_seconds(brov_rls* r, double* seconds) {
-    if (!r || !seconds || !r->ev_valid) return BROV_ERR_ARG;
-    RLSCHK(hipSetDevice(r->device));
-    RLSCHK(hipEventSynchronize(r->ev[1]));
-    float ms = 0.f;
-    RLSCHK(hipEventElapsedTime(&ms, r->ev[0], r->ev[1]));
-    *seconds = ms * 1e-3;
-    return BROV_OK;
+    if (!r || !seconds || !r->timer.valid) return BROV_ERR_ARG;
+    HIPCHK(hipSetDevice(r->device));
+    return r->timer.seconds(seconds, g_rls_err);
 }

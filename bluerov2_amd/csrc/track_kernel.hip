@@ -179,20 +179,12 @@ __global__ void track_finish_kernel(const TrackPartial* __restrict__ partial, in
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
+#include "host_common.hpp"   // (here, not at the top: the kernels above keep their line numbers in the compiler's resource report)
+
 using namespace brov;
 
 static thread_local std::string g_track_err;
-#define TRKCHK(call)                                                                                          \
-    do {                                                                                                      \
-        hipError_t e_ = (call);                                                                               \
-        if (e_ != hipSuccess) {                                                                               \
-            g_track_err = std::string(#call) + ": " + hipGetErrorString(e_);                                  \
-            (void)hipGetLastError();                                                                          \
-            return (e_ == hipErrorNoDevice || e_ == hipErrorInvalidDevice || e_ == hipErrorInsufficientDriver) \
-                       ? BROV_ERR_NO_DEVICE                                                                   \
-                       : BROV_ERR_HIP;                                                                        \
-        }                                                                                                     \
-    } while (0)
+#define HIPCHK(call) BROV_HIPCHK(g_track_err, call)
 
 struct brov_track {
     int device = 0, B = 0;
@@ -202,8 +194,10 @@ struct brov_track {
     void* stage = nullptr;                 // brov_track_accumulate_host: the caller's logs and table on the device (grows, never shrinks)
     size_t stage_bytes = 0;
     hipStream_t last_stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr}, ev_done = nullptr;   // around the last accumulate kernel; behind the last enqueued work
-    bool ev_valid = false, done_valid = false;
+    KernelTimer timer;                     // around the last accumulate kernel
+    hipEvent_t ev_done = nullptr;          // behind the last enqueued work
+    bool done_valid = false;
+    DeviceAllocs mem;                      // rec, partial
 };
 
 extern "C" const char* brov_track_last_error(void) { return g_track_err.c_str(); }
@@ -219,10 +213,10 @@ extern "C" void brov_track_destroy(brov_track* t) {
     if (!t) return;
     (void)hipSetDevice(t->device);
     (void)hipStreamSynchronize(t->last_stream);
-    for (void* q : {(void*)t->rec, (void*)t->partial, t->stage})
-        if (q) (void)hipFree(q);
-    for (hipEvent_t ev : {t->ev[0], t->ev[1], t->ev_done})
-        if (ev) (void)hipEventDestroy(ev);
+    t->mem.free_all();
+    if (t->stage) (void)hipFree(t->stage);
+    t->timer.destroy();
+    if (t->ev_done) (void)hipEventDestroy(t->ev_done);
     delete t;
 }
 
@@ -230,11 +224,11 @@ extern "C" int brov_track_batch(const brov_track* t) { return t ? t->B : 0; }
 
 // work on `st` behind whatever the tracker enqueued last, without a host wait
 static int order_behind(brov_track* t, hipStream_t st) {
-    if (t->done_valid && t->last_stream != st) TRKCHK(hipStreamWaitEvent(st, t->ev_done, 0));
+    if (t->done_valid && t->last_stream != st) HIPCHK(hipStreamWaitEvent(st, t->ev_done, 0));
     return BROV_OK;
 }
 static int enqueued_on(brov_track* t, hipStream_t st) {
-    TRKCHK(hipEventRecord(t->ev_done, st));
+    HIPCHK(hipEventRecord(t->ev_done, st));
     t->done_valid = true;
     t->last_stream = st;
     return BROV_OK;
@@ -242,14 +236,14 @@ static int enqueued_on(brov_track* t, hipStream_t st) {
 
 extern "C" int brov_track_reset(brov_track* t) {
     if (!t) { g_track_err = "brov_track_reset: null argument"; return BROV_ERR_ARG; }
-    TRKCHK(hipSetDevice(t->device));
-    TRKCHK(hipStreamSynchronize(t->last_stream));
+    HIPCHK(hipSetDevice(t->device));
+    HIPCHK(hipStreamSynchronize(t->last_stream));
     brov_track_stats z;
     std::memset(&z, 0, sizeof z);
     z.first_failed = -1;
     z.worst_tick = -1;
     std::vector<brov_track_stats> h((size_t)t->B, z);
-    TRKCHK(hipMemcpy(t->rec, h.data(), h.size() * sizeof(brov_track_stats), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(t->rec, h.data(), h.size() * sizeof(brov_track_stats), hipMemcpyHostToDevice));
     return BROV_OK;
 }
 
@@ -260,29 +254,26 @@ extern "C" int brov_track_create(brov_track** out, int device, int B, const brov
     if (p) q = *p; else brov_track_default_params(&q);
     for (int c = 0; c < BROV_NU; c++)
         if (!(q.lbu[c] <= q.ubu[c])) { g_track_err = "brov_track_create: need lbu <= ubu"; return BROV_ERR_ARG; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
-        (void)hipGetLastError();
+    if (!usable_device(device)) {
         g_track_err = "brov_track_create: no usable HIP device (the statistics have no CPU path)";
         return BROV_ERR_NO_DEVICE;
     }
-    TRKCHK(hipSetDevice(device));
+    HIPCHK(hipSetDevice(device));
     brov_track* t = new brov_track();
     t->device = device; t->B = B; t->par = q;
-    if (hipMalloc((void**)&t->rec, (size_t)B * sizeof(brov_track_stats)) != hipSuccess ||
-        hipMalloc((void**)&t->partial, (size_t)(kTrackMaxPartials + 1) * sizeof(TrackPartial)) != hipSuccess) {
-        (void)hipGetLastError();
-        g_track_err = "brov_track_create: hipMalloc failed";
+    int rc = t->mem.alloc(&t->rec, (size_t)B, g_track_err);
+    if (rc == BROV_OK) rc = t->mem.alloc(&t->partial, (size_t)(kTrackMaxPartials + 1), g_track_err);
+    if (rc != BROV_OK) {
+        g_track_err = "brov_track_create: " + g_track_err;
         brov_track_destroy(t);
-        return BROV_ERR_ALLOC;
+        return rc;
     }
-    if (hipEventCreate(&t->ev[0]) != hipSuccess || hipEventCreate(&t->ev[1]) != hipSuccess ||
-        hipEventCreateWithFlags(&t->ev_done, hipEventDisableTiming) != hipSuccess) {
+    if (t->timer.create() != hipSuccess || hipEventCreateWithFlags(&t->ev_done, hipEventDisableTiming) != hipSuccess) {
         g_track_err = "brov_track_create: device initialisation failed";
         brov_track_destroy(t);
         return BROV_ERR_HIP;
     }
-    if (int rc = brov_track_reset(t)) { brov_track_destroy(t); return rc; }
+    if ((rc = brov_track_reset(t)) != BROV_OK) { brov_track_destroy(t); return rc; }
     *out = t;
     return BROV_OK;
 }
@@ -295,17 +286,16 @@ int track_accumulate_on(brov_track* t, const double* x, const double* u, const i
         g_track_err = "brov_track_accumulate: bad argument (needs logs, K >= 1 and a table of at least one row)";
         return BROV_ERR_ARG;
     }
-    TRKCHK(hipSetDevice(t->device));
+    HIPCHK(hipSetDevice(t->device));
     if (int rc = order_behind(t, st)) return rc;
     TrackArgs a;
     a.B = t->B; a.K = K; a.rows = rows; a.line1 = line1;
     a.x = x; a.u = u; a.status = status; a.ref = ref; a.rec = t->rec;
     for (int c = 0; c < 4; c++) { a.lbu[c] = lbu[c]; a.ubu[c] = ubu[c]; }
-    TRKCHK(hipEventRecord(t->ev[0], st));
+    HIPCHK(t->timer.start(st));
     hipLaunchKernelGGL(track_accumulate_kernel, dim3((t->B + kTrackBlock - 1) / kTrackBlock), dim3(kTrackBlock), 0, st, a);
-    TRKCHK(hipGetLastError());
-    TRKCHK(hipEventRecord(t->ev[1], st));
-    t->ev_valid = true;
+    HIPCHK(hipGetLastError());
+    HIPCHK(t->timer.stop(st));
     return enqueued_on(t, st);
 }
 }  // namespace brov
@@ -319,8 +309,8 @@ extern "C" int brov_track_accumulate_device(brov_track* t, const double* x, cons
 extern "C" int brov_track_accumulate_host(brov_track* t, const double* x, const double* u, const int32_t* status, int K, const double* ref,
                                           int rows, int line1) {
     if (!t || !x || !u || !ref || K < 1 || rows < 1) { g_track_err = "brov_track_accumulate_host: bad argument"; return BROV_ERR_ARG; }
-    TRKCHK(hipSetDevice(t->device));
-    TRKCHK(hipStreamSynchronize(t->last_stream));   // the staging buffer may still be read by the last accumulate
+    HIPCHK(hipSetDevice(t->device));
+    HIPCHK(hipStreamSynchronize(t->last_stream));   // the staging buffer may still be read by the last accumulate
     const size_t n = (size_t)K * t->B;
     const size_t bx = n * 12 * sizeof(double), bu = n * 4 * sizeof(double), br = (size_t)rows * 16 * sizeof(double), bs = n * sizeof(int32_t);
     const size_t need = bx + bu + br + bs;          // doubles first: every block stays 8-byte aligned
@@ -336,35 +326,35 @@ extern "C" int brov_track_accumulate_host(brov_track* t, const double* x, const 
     char* base = (char*)t->stage;
     double *dx = (double*)base, *du = (double*)(base + bx), *dr = (double*)(base + bx + bu);
     int* ds = (int*)(base + bx + bu + br);
-    TRKCHK(hipMemcpy(dx, x, bx, hipMemcpyHostToDevice));
-    TRKCHK(hipMemcpy(du, u, bu, hipMemcpyHostToDevice));
-    TRKCHK(hipMemcpy(dr, ref, br, hipMemcpyHostToDevice));
-    if (status) TRKCHK(hipMemcpy(ds, status, bs, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dx, x, bx, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(du, u, bu, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dr, ref, br, hipMemcpyHostToDevice));
+    if (status) HIPCHK(hipMemcpy(ds, status, bs, hipMemcpyHostToDevice));
     return track_accumulate_on(t, dx, du, status ? ds : nullptr, K, dr, rows, line1, t->par.lbu, t->par.ubu, nullptr);
 }
 
 extern "C" int brov_track_get_stats_host(brov_track* t, brov_track_stats* stats) {
     if (!t || !stats) { g_track_err = "brov_track_get_stats_host: null argument"; return BROV_ERR_ARG; }
-    TRKCHK(hipSetDevice(t->device));
-    TRKCHK(hipStreamSynchronize(t->last_stream));
-    TRKCHK(hipMemcpy(stats, t->rec, (size_t)t->B * sizeof(brov_track_stats), hipMemcpyDeviceToHost));
+    HIPCHK(hipSetDevice(t->device));
+    HIPCHK(hipStreamSynchronize(t->last_stream));
+    HIPCHK(hipMemcpy(stats, t->rec, (size_t)t->B * sizeof(brov_track_stats), hipMemcpyDeviceToHost));
     return BROV_OK;
 }
 
 extern "C" int brov_track_get_summary_host(brov_track* t, brov_track_summary* out) {
     if (!t || !out) { g_track_err = "brov_track_get_summary_host: null argument"; return BROV_ERR_ARG; }
-    TRKCHK(hipSetDevice(t->device));
+    HIPCHK(hipSetDevice(t->device));
     hipStream_t st = t->last_stream;
     int blocks = (t->B + kTrackBlock - 1) / kTrackBlock;
     if (blocks > kTrackMaxPartials) blocks = kTrackMaxPartials;
     hipLaunchKernelGGL(track_reduce_kernel, dim3(blocks), dim3(kTrackBlock), 0, st, (const brov_track_stats*)t->rec, t->B, t->partial);
-    TRKCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(track_finish_kernel, dim3(1), dim3(64), 0, st, (const TrackPartial*)t->partial, blocks, t->partial + kTrackMaxPartials);
-    TRKCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     if (int rc = enqueued_on(t, st)) return rc;
-    TRKCHK(hipStreamSynchronize(st));
+    HIPCHK(hipStreamSynchronize(st));
     TrackPartial p;
-    TRKCHK(hipMemcpy(&p, t->partial + kTrackMaxPartials, sizeof p, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&p, t->partial + kTrackMaxPartials, sizeof p, hipMemcpyDeviceToHost));
     std::memset(out, 0, sizeof *out);
     out->worst_instance = -1;
     out->ticks = p.ticks; out->failed = p.failed; out->saturated = p.sat; out->nonfinite = p.nonf;
@@ -379,11 +369,7 @@ extern "C" int brov_track_get_summary_host(brov_track* t, brov_track_summary* ou
 }
 
 extern "C" int brov_track_last_seconds(brov_track* t, double* seconds) {
-    if (!t || !seconds || !t->ev_valid) { g_track_err = "brov_track_last_seconds: no accumulate yet"; return BROV_ERR_ARG; }
-    TRKCHK(hipSetDevice(t->device));
-    TRKCHK(hipEventSynchronize(t->ev[1]));
-    float ms = 0.f;
-    TRKCHK(hipEventElapsedTime(&ms, t->ev[0], t->ev[1]));
-    *seconds = ms * 1e-3;
-    return BROV_OK;
+    if (!t || !seconds || !t->timer.valid) { g_track_err = "brov_track_last_seconds: no accumulate yet"; return BROV_ERR_ARG; }
+    HIPCHK(hipSetDevice(t->device));
+    return t->timer.seconds(seconds, g_track_err);
 }

@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from .solver import _load, NoDeviceError, BatchSolver
+from .solver import _Handle, _arr, _arr_opt, _bind, _dp, _load, BatchSolver
 
 
 class EkfParams(C.Structure):
@@ -21,84 +21,40 @@ class EkfParams(C.Structure):
         return p
 
 
-_bound = False
+def _protos(L):
+    vp, dp, ip = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    L.brov_ekf_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.POINTER(EkfParams)]
+    _bind(L, {"brov_ekf_last_error": []}, C.c_char_p)
+    _bind(L, {"brov_ekf_default_params": [C.POINTER(EkfParams)], "brov_ekf_destroy": [vp]}, None)
+    _bind(L, {"brov_ekf_x_device": [vp], "brov_ekf_P_device": [vp], "brov_ekf_mpc_p_device": [vp]}, vp)
+    _bind(L, {
+        "brov_ekf_batch": [vp], "brov_ekf_reset": [vp, dp, dp], "brov_ekf_set_state_host": [vp, dp, dp],
+        "brov_ekf_get_state_host": [vp, dp, dp], "brov_ekf_update_host": [vp, dp, dp, dp, vp],
+        "brov_ekf_update_device": [vp, vp, vp, vp, vp], "brov_ekf_get_outputs_host": [vp, dp, dp, ip],
+        "brov_ekf_update_from_solver": [vp, vp, vp], "brov_ekf_apply_to_solver": [vp, vp, vp],
+        "brov_ekf_last_update_seconds": [vp, dp],
+    })
 
 
 def _ekf_lib():
-    global _bound
-    L = _load()
-    if not _bound:
-        vp, dp, ip = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32)
-        L.brov_ekf_last_error.restype = C.c_char_p
-        L.brov_ekf_default_params.argtypes = [C.POINTER(EkfParams)]
-        L.brov_ekf_default_params.restype = None
-        L.brov_ekf_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.POINTER(EkfParams)]
-        L.brov_ekf_destroy.argtypes = [vp]
-        L.brov_ekf_destroy.restype = None
-        for name, args in {
-            "brov_ekf_batch": [vp], "brov_ekf_reset": [vp, dp, dp], "brov_ekf_set_state_host": [vp, dp, dp],
-            "brov_ekf_get_state_host": [vp, dp, dp], "brov_ekf_update_host": [vp, dp, dp, dp, vp],
-            "brov_ekf_update_device": [vp, vp, vp, vp, vp], "brov_ekf_get_outputs_host": [vp, dp, dp, ip],
-            "brov_ekf_update_from_solver": [vp, vp, vp], "brov_ekf_apply_to_solver": [vp, vp, vp],
-            "brov_ekf_last_update_seconds": [vp, dp],
-        }.items():
-            fn = getattr(L, name)
-            fn.argtypes = args
-            fn.restype = C.c_int
-        for name in ("brov_ekf_x_device", "brov_ekf_P_device", "brov_ekf_mpc_p_device"):
-            fn = getattr(L, name)
-            fn.argtypes = [vp]
-            fn.restype = vp
-        _bound = True
-    return L
+    return _load(_protos)
 
 
-def _dp(a):
-    return a.ctypes.data_as(C.POINTER(C.c_double))
-
-
-def _c(a, shape):
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    if a.shape != tuple(shape):
-        raise ValueError(f"expected shape {tuple(shape)}, got {a.shape}")
-    return a
-
-
-class BatchEkf:
+class BatchEkf(_Handle):
     """B independent 18-state observers resident on one GPU; update() = one EKF tick of each."""
+    _last_error, _destroy = "brov_ekf_last_error", "brov_ekf_destroy"
 
     def __init__(self, batch, params=None, device=0):
         L = _ekf_lib()
         self.B = int(batch)
         self.params = params if params is not None else EkfParams.default()
-        h = C.c_void_p()
-        rc = L.brov_ekf_create(C.byref(h), int(device), self.B, C.byref(self.params))
-        if rc == -2:
-            raise NoDeviceError(L.brov_ekf_last_error().decode() or "no HIP device")
-        if rc != 0:
-            raise RuntimeError(f"brov_ekf_create failed ({rc}): {L.brov_ekf_last_error().decode()}")
-        self._h, self._L = h, L
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.brov_ekf_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def _chk(self, rc, what):
-        if rc != 0:
-            raise RuntimeError(f"{what} failed ({rc}): {self._L.brov_ekf_last_error().decode()}")
+        self._create(L, "brov_ekf_create", int(device), self.B, C.byref(self.params))
 
     def reset(self, x0=None, P0=None):
-        x0 = None if x0 is None else _c(x0, (18,))
-        P0 = None if P0 is None else _c(P0, (18, 18))
-        self._chk(self._L.brov_ekf_reset(self._h, None if x0 is None else _dp(x0), None if P0 is None else _dp(P0)), "reset")
+        self._chk(self._L.brov_ekf_reset(self._h, _dp(_arr_opt(x0, (18,))), _dp(_arr_opt(P0, (18, 18)))), "reset")
 
     def set_state(self, x=None, P=None):
-        x = None if x is None else _c(x, (self.B, 18))
-        P = None if P is None else _c(P, (self.B, 18, 18))
-        self._chk(self._L.brov_ekf_set_state_host(self._h, None if x is None else _dp(x), None if P is None else _dp(P)), "set_state")
+        self._chk(self._L.brov_ekf_set_state_host(self._h, _dp(_arr_opt(x, (self.B, 18))), _dp(_arr_opt(P, (self.B, 18, 18)))), "set_state")
 
     def state(self):
         x = np.empty((self.B, 18)); P = np.empty((self.B, 18, 18))
@@ -106,7 +62,7 @@ class BatchEkf:
         return x, P
 
     def update(self, thrust, y12, acc, stream=0):
-        thrust = _c(thrust, (self.B, 6)); y12 = _c(y12, (self.B, 12)); acc = _c(acc, (self.B, 6))
+        thrust = _arr(thrust, (self.B, 6)); y12 = _arr(y12, (self.B, 12)); acc = _arr(acc, (self.B, 6))
         self._chk(self._L.brov_ekf_update_host(self._h, _dp(thrust), _dp(y12), _dp(acc), C.c_void_p(stream)), "update")
 
     def update_device(self, thrust_ptr, y12_ptr, acc_ptr, stream=0):

@@ -6,48 +6,33 @@ import ctypes as C
 
 import numpy as np
 
-from .solver import BatchSolver, NoDeviceError, RESULT_DTYPE, SolverOptions, _arr, _dp, _load
+from .solver import BatchSolver, RESULT_DTYPE, SolverOptions, _Handle, _arr, _bind, _dp, _load
 
 GATHER_RECORDS, GATHER_PACKED = 0, 1
 COLLECTIVE_RCCL, COLLECTIVE_COPY = 0, 1
-_bound = False
+
+
+def _protos(L):
+    vp, dp, ip = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)
+    L.brov_group_create.argtypes = [C.POINTER(vp), ip, C.c_int, C.c_int, vp]
+    _bind(L, {"brov_group_last_error": []}, C.c_char_p)
+    _bind(L, {"brov_group_destroy": [vp]}, None)
+    _bind(L, {"brov_group_solver": [vp, C.c_int], "brov_group_stream": [vp, C.c_int], "brov_group_gathered_device": [vp, C.c_int]}, vp)
+    _bind(L, {"brov_group_create_ex": [C.POINTER(vp), ip, C.c_int, C.c_int, vp, C.c_int],
+              "brov_group_create_rank": [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_char_p, ip, vp],
+              "brov_group_create_rank_ex": [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_char_p, ip, vp, C.c_int],
+              "brov_group_unique_id": [C.c_char_p],
+              "brov_group_set_copy_wait_seconds": [C.c_int], "brov_group_collective": [vp], "brov_group_world": [vp], "brov_group_first_rank": [vp], "brov_group_rccl_version": [ip], "brov_group_size": [vp], "brov_group_total": [vp], "brov_group_shard": [vp, C.c_int, ip, ip],
+              "brov_group_set_x0_host": [vp, dp], "brov_group_set_params_host": [vp, dp, C.c_int],
+              "brov_group_set_yref_host": [vp, dp, C.c_int], "brov_group_set_candidate_params_host": [vp, C.c_int, dp, dp, dp],
+              "brov_group_set_yref_candidates": [vp, C.c_double, C.c_double], "brov_group_solve": [vp], "brov_group_gather": [vp, C.c_int],
+              "brov_group_select_best": [vp, ip, vp], "brov_group_synchronize": [vp], "brov_group_get_results_host": [vp, vp],
+              "brov_group_slots_per_rank": [vp], "brov_group_enable_timing": [vp, C.c_int],
+              "brov_group_last_seconds": [vp, dp, dp, dp]})
 
 
 def _lib():
-    global _bound
-    L = _load()
-    if not _bound:
-        vp, dp, ip = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)
-        L.brov_group_last_error.restype = C.c_char_p
-        L.brov_group_create.argtypes = [C.POINTER(vp), ip, C.c_int, C.c_int, vp]
-        L.brov_group_create_ex.argtypes = [C.POINTER(vp), ip, C.c_int, C.c_int, vp, C.c_int]
-        L.brov_group_create_ex.restype = C.c_int
-        L.brov_group_create_rank_ex.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_char_p, ip, vp, C.c_int]
-        L.brov_group_create_rank_ex.restype = C.c_int
-        L.brov_group_destroy.argtypes = [vp]
-        L.brov_group_destroy.restype = None
-        L.brov_group_solver.argtypes = [vp, C.c_int]
-        L.brov_group_solver.restype = vp
-        L.brov_group_stream.argtypes = [vp, C.c_int]
-        L.brov_group_stream.restype = vp
-        L.brov_group_gathered_device.argtypes = [vp, C.c_int]
-        L.brov_group_gathered_device.restype = vp
-        L.brov_group_unique_id.argtypes = [C.c_char_p]
-        L.brov_group_unique_id.restype = C.c_int
-        L.brov_group_create_rank.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_char_p, ip, vp]
-        L.brov_group_create_rank.restype = C.c_int
-        for name, args in {"brov_group_set_copy_wait_seconds": [C.c_int], "brov_group_collective": [vp], "brov_group_world": [vp], "brov_group_first_rank": [vp], "brov_group_rccl_version": [ip], "brov_group_size": [vp], "brov_group_total": [vp], "brov_group_shard": [vp, C.c_int, ip, ip],
-                           "brov_group_set_x0_host": [vp, dp], "brov_group_set_params_host": [vp, dp, C.c_int],
-                           "brov_group_set_yref_host": [vp, dp, C.c_int], "brov_group_set_candidate_params_host": [vp, C.c_int, dp, dp, dp],
-                           "brov_group_set_yref_candidates": [vp, C.c_double, C.c_double], "brov_group_solve": [vp], "brov_group_gather": [vp, C.c_int],
-                           "brov_group_select_best": [vp, ip, vp], "brov_group_synchronize": [vp], "brov_group_get_results_host": [vp, vp],
-                           "brov_group_slots_per_rank": [vp], "brov_group_enable_timing": [vp, C.c_int],
-                           "brov_group_last_seconds": [vp, dp, dp, dp]}.items():
-            fn = getattr(L, name)
-            fn.argtypes = args
-            fn.restype = C.c_int
-        _bound = True
-    return L
+    return _load(_protos)
 
 
 def rccl_version():
@@ -69,8 +54,6 @@ class _Shard(BatchSolver):
     def close(self):
         self._h = None
 
-    __del__ = close
-
 
 def unique_id():
     """128 opaque bytes (ncclGetUniqueId): rank 0 of a one-process-per-GPU group creates them, every rank needs them"""
@@ -81,58 +64,47 @@ def unique_id():
     return buf.raw
 
 
-class SolverGroup:
+class SolverGroup(_Handle):
     """devices + total: ONE process holds every device of the group.  rank= / world= / uid= / counts= (with devices = [this process's
     device]): one process per GPU, this process holds rank `rank` of `world` (uid: unique_id() of rank 0, handed to every rank by the
     launcher).  The whole-batch setters take GLOBAL arrays in both forms (every process uses the slice of its own shard);
     `shards[0]` is the local shard's solver for everything else.  collective="copy" (BROV_COLLECTIVE_COPY): the all-gather as
     device-to-device copies instead of RCCL -- `devices` may then repeat a GPU (several ranks on one device: the 1-GPU test route),
     and the ranks of a rank= group must live in one process, one thread each."""
+    _last_error, _destroy = "brov_group_last_error", "brov_group_destroy"
 
     def __init__(self, devices, total=None, opts=None, rank=None, world=None, uid=None, counts=None, collective="rccl"):
         L = _lib()
         self.opts = opts if opts is not None else SolverOptions()
         self.devices = [int(d) for d in devices]
         self.N = int(self.opts.N)
-        h = C.c_void_p()
+        self.shards = []
         coll = {"rccl": COLLECTIVE_RCCL, "copy": COLLECTIVE_COPY}[collective]
         self.collective = collective
         if rank is None:
             self.total = int(total)
             arr = (C.c_int * len(self.devices))(*self.devices)
-            rc = L.brov_group_create_ex(C.byref(h), arr, len(self.devices), self.total, C.byref(self.opts._o), coll)
+            self._create(L, "brov_group_create_ex", arr, len(self.devices), self.total, C.byref(self.opts._o), coll, what="brov_group_create")
         else:
             cnt = (C.c_int * int(world))(*[int(c) for c in counts])
-            rc = L.brov_group_create_rank_ex(C.byref(h), self.devices[0], int(rank), int(world), C.c_char_p(bytes(uid)), cnt, C.byref(self.opts._o), coll)
             self.total = int(sum(counts))
-        if rc == -2:
-            raise NoDeviceError(L.brov_group_last_error().decode() or "no HIP device")
-        if rc != 0:
-            raise RuntimeError(f"brov_group_create failed ({rc}): {L.brov_group_last_error().decode()}")
-        self._h, self._L = h, L
+            self._create(L, "brov_group_create_rank_ex", self.devices[0], int(rank), int(world), C.c_char_p(bytes(uid)), cnt, C.byref(self.opts._o), coll,
+                         what="brov_group_create")
+        h = self._h
         self.world, self.first_rank = int(L.brov_group_world(h)), int(L.brov_group_first_rank(h))
         self.bounds = []
         for r in range(self.world):
             lo, hi = C.c_int(0), C.c_int(0)
             L.brov_group_shard(h, r, C.byref(lo), C.byref(hi))
             self.bounds.append((lo.value, hi.value))
-        self.shards = []
         for d in range(len(self.devices)):
             lo, hi = self.bounds[self.first_rank + d]
             self.shards.append(_Shard(L.brov_group_solver(h, d), hi - lo, self.opts, self.devices[d], L))
 
     def close(self):
-        if getattr(self, "_h", None):
-            for s in self.shards:
-                s.close()
-            self._L.brov_group_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def _chk(self, rc, what):
-        if rc != 0:
-            raise RuntimeError(f"{what} failed ({rc}): {self._L.brov_group_last_error().decode()}")
+        for s in getattr(self, "shards", ()):   # the shards' handles die with the group's
+            s.close()
+        super().close()
 
     def stream(self, rank):
         return int(self._L.brov_group_stream(self._h, rank) or 0)

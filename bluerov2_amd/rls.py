@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from .solver import _load, NoDeviceError, BatchSolver
+from .solver import _Handle, _arr, _arr_opt, _bind, _dp, _load, BatchSolver
 
 APPLY_DISTURBANCE = 0   # BROV_RLS_APPLY_DISTURBANCE: p[0..3] (the shipped AMPC)
 APPLY_MODEL = 1         # BROV_RLS_APPLY_MODEL: also p[4..15] from theta(0), theta(1), theta(3)
@@ -23,82 +23,42 @@ class RlsParams(C.Structure):
         return p
 
 
-_bound = False
+def _protos(L):
+    vp, dp, ip = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    L.brov_rls_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.POINTER(RlsParams)]
+    _bind(L, {"brov_rls_last_error": []}, C.c_char_p)
+    _bind(L, {"brov_rls_default_params": [C.POINTER(RlsParams)], "brov_rls_destroy": [vp]}, None)
+    _bind(L, {"brov_rls_theta_device": [vp]}, vp)
+    _bind(L, {
+        "brov_rls_batch": [vp], "brov_rls_reset": [vp], "brov_rls_set_state_host": [vp, dp, dp, dp],
+        "brov_rls_get_state_host": [vp, dp, dp, dp, dp, dp], "brov_rls_update_host": [vp, dp, dp, dp, dp, vp],
+        "brov_rls_update_device": [vp, vp, vp, vp, vp, vp], "brov_rls_update_from_ekf": [vp, vp, vp, vp],
+        "brov_rls_apply_to_solver": [vp, vp, C.c_int, vp], "brov_rls_get_outputs_host": [vp, dp, dp, ip],
+        "brov_rls_last_update_seconds": [vp, dp],
+    })
 
 
 def _rls_lib():
-    global _bound
-    L = _load()
-    if not _bound:
-        vp, dp, ip = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32)
-        L.brov_rls_last_error.restype = C.c_char_p
-        L.brov_rls_default_params.argtypes = [C.POINTER(RlsParams)]
-        L.brov_rls_default_params.restype = None
-        L.brov_rls_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.POINTER(RlsParams)]
-        L.brov_rls_destroy.argtypes = [vp]
-        L.brov_rls_destroy.restype = None
-        for name, args in {
-            "brov_rls_batch": [vp], "brov_rls_reset": [vp], "brov_rls_set_state_host": [vp, dp, dp, dp],
-            "brov_rls_get_state_host": [vp, dp, dp, dp, dp, dp], "brov_rls_update_host": [vp, dp, dp, dp, dp, vp],
-            "brov_rls_update_device": [vp, vp, vp, vp, vp, vp], "brov_rls_update_from_ekf": [vp, vp, vp, vp],
-            "brov_rls_apply_to_solver": [vp, vp, C.c_int, vp], "brov_rls_get_outputs_host": [vp, dp, dp, ip],
-            "brov_rls_last_update_seconds": [vp, dp],
-        }.items():
-            fn = getattr(L, name)
-            fn.argtypes = args
-            fn.restype = C.c_int
-        L.brov_rls_theta_device.argtypes = [vp]
-        L.brov_rls_theta_device.restype = vp
-        _bound = True
-    return L
+    return _load(_protos)
 
 
-def _dp(a):
-    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
-
-
-def _c(a, shape):
-    if a is None:
-        return None
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    if a.shape != tuple(shape):
-        raise ValueError(f"expected shape {tuple(shape)}, got {a.shape}")
-    return a
-
-
-class BatchRls:
+class BatchRls(_Handle):
     """B independent four-axis RLS-FF estimators resident on one GPU; update() = one RLSFF() tick of each.
     Axis order X, Y, Z, N; theta [B, 4 axes, 4], P [B, 4, 4, 4], lambda / F / e [B, 4]."""
+    _last_error, _destroy = "brov_rls_last_error", "brov_rls_destroy"
 
     def __init__(self, batch, params=None, device=0):
         L = _rls_lib()
         self.B = int(batch)
         self.params = params if params is not None else RlsParams.default()
-        h = C.c_void_p()
-        rc = L.brov_rls_create(C.byref(h), int(device), self.B, C.byref(self.params))
-        if rc == -2:
-            raise NoDeviceError(L.brov_rls_last_error().decode() or "no HIP device")
-        if rc != 0:
-            raise RuntimeError(f"brov_rls_create failed ({rc}): {L.brov_rls_last_error().decode()}")
-        self._h, self._L = h, L
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.brov_rls_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def _chk(self, rc, what):
-        if rc != 0:
-            raise RuntimeError(f"{what} failed ({rc}): {self._L.brov_rls_last_error().decode()}")
+        self._create(L, "brov_rls_create", int(device), self.B, C.byref(self.params))
 
     def reset(self):
         self._chk(self._L.brov_rls_reset(self._h), "reset")
 
     def set_state(self, theta=None, P=None, lam=None):
         """any of theta [B,4,4], P [B,4,4,4], lambda [B,4]; the error windows are emptied"""
-        theta = _c(theta, (self.B, 4, 4)); P = _c(P, (self.B, 4, 4, 4)); lam = _c(lam, (self.B, 4))
+        theta = _arr_opt(theta, (self.B, 4, 4)); P = _arr_opt(P, (self.B, 4, 4, 4)); lam = _arr_opt(lam, (self.B, 4))
         self._chk(self._L.brov_rls_set_state_host(self._h, _dp(theta), _dp(P), _dp(lam)), "set_state")
 
     def state(self):
@@ -109,7 +69,7 @@ class BatchRls:
         return th, P, lam, F, e
 
     def update(self, y, acc, vel, rpy, stream=0):
-        y = _c(y, (self.B, 4)); acc = _c(acc, (self.B, 4)); vel = _c(vel, (self.B, 4)); rpy = _c(rpy, (self.B, 3))
+        y = _arr(y, (self.B, 4)); acc = _arr(acc, (self.B, 4)); vel = _arr(vel, (self.B, 4)); rpy = _arr(rpy, (self.B, 3))
         self._chk(self._L.brov_rls_update_host(self._h, _dp(y), _dp(acc), _dp(vel), _dp(rpy), C.c_void_p(stream)), "update")
 
     def update_device(self, y_ptr, acc_ptr, vel_ptr, rpy_ptr, stream=0):

@@ -57,30 +57,49 @@ def build_library(force=False):
 
 
 _lib = None
+_bound = set()
 
 
-def _load():
+def _bind(L, table, restype=C.c_int):
+    """prototypes of the entry points in `table` (name -> argtypes), all returning `restype`"""
+    for name, args in table.items():
+        fn = getattr(L, name)
+        fn.argtypes = args
+        fn.restype = restype
+
+
+def _load(protos=None):
+    """the library, loaded once; `protos(L)` -- a component's prototypes -- declared once"""
     global _lib
-    if _lib is not None:
-        return _lib
-    # PyTorch (device memory, streams, torch.distributed) ships its own HIP runtime; it has to be the first one mapped
-    # into the process or hipGetDeviceCount() of a second runtime copy reports no device.
-    try:
-        import torch  # noqa: F401
-    except ImportError:
-        pass
-    if not os.path.exists(_LIB):
-        raise FileNotFoundError(f"{_LIB} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
-                                "(the HIP extension is the only compute path; there is no fallback)")
-    L = C.CDLL(_LIB)
+    if _lib is None:
+        # PyTorch (device memory, streams, torch.distributed) ships its own HIP runtime; it has to be the first one mapped
+        # into the process or hipGetDeviceCount() of a second runtime copy reports no device.
+        try:
+            import torch  # noqa: F401
+        except ImportError:
+            pass
+        if not os.path.exists(_LIB):
+            raise FileNotFoundError(f"{_LIB} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
+                                    "(the HIP extension is the only compute path; there is no fallback)")
+        _lib = C.CDLL(_LIB)
+    for f in (_protos, protos):
+        if f is not None and f not in _bound:
+            f(_lib)
+            _bound.add(f)
+    return _lib
+
+
+def _protos(L):
     vp, dp, ip = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)
-    L.brov_last_error.restype = C.c_char_p
     L.brov_default_opts.argtypes = [C.POINTER(_Opts), C.c_int, C.c_double]
     L.brov_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.POINTER(_Opts)]
-    L.brov_destroy.argtypes = [vp]
-    L.brov_device_bytes.argtypes = [vp]
-    L.brov_device_bytes.restype = C.c_size_t
-    for name, args in {
+    _bind(L, {"brov_last_error": []}, C.c_char_p)
+    _bind(L, {"brov_destroy": [vp]}, None)
+    _bind(L, {"brov_device_bytes": [vp]}, C.c_size_t)
+    _bind(L, {"brov_plant_wrench_tick": [vp]}, C.c_int64)
+    _bind(L, {name: [vp] for name in ("brov_results_device", "brov_x0_device", "brov_yref_device", "brov_params_device", "brov_x_device",
+                                      "brov_u_device")}, vp)
+    _bind(L, {
         "brov_set_x0_host": [vp, dp], "brov_set_x0_device": [vp, vp, vp],
         "brov_set_yref_host": [vp, dp, C.c_int], "brov_set_yref_device": [vp, vp, C.c_int, vp],
         "brov_set_params_host": [vp, dp, C.c_int], "brov_set_params_device": [vp, vp, C.c_int, vp],
@@ -112,30 +131,61 @@ def _load():
         "brov_plant_wrench_seek": [vp, C.c_int64], "brov_plant_wrench_eval_host": [vp, C.c_int64, dp],
         "brov_closed_loop_ex": [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, dp, dp, C.POINTER(C.c_int32), dp],
         "brov_closed_loop_dob": [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, dp, dp, C.POINTER(C.c_int32), dp, dp],
-    }.items():
-        fn = getattr(L, name)
-        fn.argtypes = args
-        fn.restype = C.c_int
-    L.brov_plant_wrench_tick.argtypes = [vp]
-    L.brov_plant_wrench_tick.restype = C.c_int64
-    for name in ("brov_results_device", "brov_x0_device", "brov_yref_device", "brov_params_device", "brov_x_device",
-                 "brov_u_device"):
-        fn = getattr(L, name)
-        fn.argtypes = [vp]
-        fn.restype = vp
-    _lib = L
-    return L
+    })
 
 
 def _dp(a):
-    return a.ctypes.data_as(C.POINTER(C.c_double))
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
 
 
-def _arr(a, shape):
-    a = np.ascontiguousarray(a, dtype=np.float64)
+def _arr(a, shape, dtype=np.float64):
+    """a mandatory array argument, contiguous, of exactly `shape`"""
+    if a is None:
+        raise ValueError(f"expected an array of shape {tuple(shape)}, got None")
+    a = np.ascontiguousarray(a, dtype=dtype)
     if a.shape != tuple(shape):
         raise ValueError(f"expected shape {tuple(shape)}, got {a.shape}")
     return a
+
+
+def _arr_opt(a, shape):
+    """an optional array argument: None stays None (a null pointer in C)"""
+    return None if a is None else _arr(a, shape)
+
+
+class _Handle:
+    """A device object of the C ABI (brov_solver, brov_ekf, brov_rls, brov_track, brov_group): its handle, the library, the name of the
+    component's own *_last_error, and what every wrapper does with them."""
+    _h = None
+    _L = None
+    _last_error = "brov_last_error"
+    _destroy = "brov_destroy"
+
+    def _error_text(self):
+        return getattr(self._L, self._last_error)().decode()
+
+    def _create(self, L, fn, *args, what=None):
+        """self._h from the create call `fn(&handle, *args)`; without a usable device NoDeviceError"""
+        self._L = L
+        h = C.c_void_p()
+        rc = getattr(L, fn)(C.byref(h), *args)
+        if rc == -2:
+            raise NoDeviceError(self._error_text() or "no HIP device")
+        if rc != 0:
+            raise RuntimeError(f"{what or fn} failed ({rc}): {self._error_text()}")
+        self._h = h
+
+    def close(self):
+        if self._h:
+            getattr(self._L, self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def _chk(self, rc, what):
+        if rc != 0:
+            raise RuntimeError(f"{what} failed ({rc}): {self._error_text()}")
 
 
 class SolverOptions:
@@ -174,31 +224,15 @@ def thrust_allocation(u0):
                      -u0[..., 2] / c, -u0[..., 2] / c], axis=-1)
 
 
-class BatchSolver:
+class BatchSolver(_Handle):
     """B independent BlueROV2 OCP instances resident on one GPU; one solve() = one RTI step of each."""
 
     def __init__(self, batch, opts=None, device=0):
         L = _load()
         self.opts = opts if opts is not None else SolverOptions()
         self.B, self.N = int(batch), int(self.opts.N)
-        h = C.c_void_p()
-        rc = L.brov_create(C.byref(h), int(device), self.B, C.byref(self.opts._o))
-        if rc == -2:
-            raise NoDeviceError(L.brov_last_error().decode() or "no HIP device")
-        if rc != 0:
-            raise RuntimeError(f"brov_create failed ({rc}): {L.brov_last_error().decode()}")
-        self._h, self._L, self.device = h, L, int(device)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.brov_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def _chk(self, rc, what):
-        if rc != 0:
-            raise RuntimeError(f"{what} failed ({rc}): {self._L.brov_last_error().decode()}")
+        self._create(L, "brov_create", int(device), self.B, C.byref(self.opts._o))
+        self.device = int(device)
 
     def set_options(self, opts):
         """change weights / bounds / limits / policies at run time (brov_set_opts; the horizon is fixed at create)"""
@@ -281,11 +315,8 @@ class BatchSolver:
         """one control tick with ONE host wait (brov_tick_host): the inputs that changed (None = unchanged; x0 [B,12], ONE reference
         window shared by the batch [N+1,16], per-stage parameters [B,N+1,16]) + the step + the result records"""
         res = np.zeros(self.B, dtype=RESULT_DTYPE)
-        a = None if x0 is None else _arr(x0, (self.B, NX))
-        b = None if yref is None else _arr(yref, (self.N + 1, NY))
-        c = None if params is None else _arr(params, (self.B, self.N + 1, NP))
-        self._chk(self._L.brov_tick_host(self._h, None if a is None else _dp(a), None if b is None else _dp(b),
-                                         None if c is None else _dp(c), int(rti_phase), C.c_void_p(res.ctypes.data)), "tick")
+        a, b, c = _arr_opt(x0, (self.B, NX)), _arr_opt(yref, (self.N + 1, NY)), _arr_opt(params, (self.B, self.N + 1, NP))
+        self._chk(self._L.brov_tick_host(self._h, _dp(a), _dp(b), _dp(c), int(rti_phase), C.c_void_p(res.ctypes.data)), "tick")
         return res
 
     def solve_ticks(self, ticks, row_stride=0, stream=None, status_log_ptr=None, sync=False):
@@ -336,10 +367,10 @@ class BatchSolver:
 
     # ---- non-uniform grid / separate stage-0 weight (acados_solver_bluerov2.h:141,146; .c:422-441): streaming kernels ------------
     def set_time_steps(self, ts):
-        self._chk(self._L.brov_set_time_steps(self._h, None if ts is None else _dp(_arr(ts, (self.N,)))), "set_time_steps")
+        self._chk(self._L.brov_set_time_steps(self._h, _dp(_arr_opt(ts, (self.N,)))), "set_time_steps")
 
     def set_stage0_weight(self, W0):
-        self._chk(self._L.brov_set_stage0_weight(self._h, None if W0 is None else _dp(_arr(W0, (NY,)))), "set_stage0_weight")
+        self._chk(self._L.brov_set_stage0_weight(self._h, _dp(_arr_opt(W0, (NY,)))), "set_stage0_weight")
 
     # ---- 6-disturbance model variant: roll / pitch disturbance moments next to p[16] ---------------------
     def enable_dist6(self, on=True):
@@ -370,7 +401,7 @@ class BatchSolver:
             self._chk(self._L.brov_set_params18_host(self._h, _dp(_arr(p18, (self.B, self.N + 1, 18))), 1), "set_params18")
 
     def set_plant_rp_disturbance(self, d):
-        self._chk(self._L.brov_plant_set_rp_disturbance_host(self._h, None if d is None else _dp(_arr(d, (self.B, 2)))), "set_plant_rp_disturbance")
+        self._chk(self._L.brov_plant_set_rp_disturbance_host(self._h, _dp(_arr_opt(d, (self.B, 2)))), "set_plant_rp_disturbance")
 
     def set_plant_params(self, p):
         self._chk(self._L.brov_plant_set_params_host(self._h, _dp(_arr(p, (self.B, NP)))), "set_plant_params")
@@ -459,8 +490,8 @@ class BatchSolver:
             tab = np.ascontiguousarray(table, dtype=np.float64)
             if tab.ndim != 2 or tab.shape[1] != 6 or tab.shape[0] < 1:
                 raise ValueError("wrench table must be [rows][6]")
-            g = None if gain is None else _arr(gain, (self.B,))
-            self._chk(self._L.brov_plant_wrench_table_host(self._h, _dp(tab), tab.shape[0], None if g is None else _dp(g)), "plant_wrench_table")
+            g = _arr_opt(gain, (self.B,))
+            self._chk(self._L.brov_plant_wrench_table_host(self._h, _dp(tab), tab.shape[0], _dp(g)), "plant_wrench_table")
 
     def plant_wrench_off(self):
         self._chk(self._L.brov_plant_wrench_off(self._h), "plant_wrench_off")
@@ -484,12 +515,9 @@ class BatchSolver:
     # ---- iterate ----------------------------------------------------------------------------------------------
     def set_iterate(self, x=None, u=None, pi=None, lam=None):
         B, N = self.B, self.N
-        ax = _arr(x, (B, N + 1, NX)) if x is not None else None
-        au = _arr(u, (B, N, NU)) if u is not None else None
-        ap = _arr(pi, (B, N, NX)) if pi is not None else None
-        al = _arr(lam, (B, N, 8)) if lam is not None else None
-        f = lambda a: _dp(a) if a is not None else None  # noqa: E731
-        self._chk(self._L.brov_set_iterate_host(self._h, f(ax), f(au), f(ap), f(al)), "set_iterate")
+        ax, au = _arr_opt(x, (B, N + 1, NX)), _arr_opt(u, (B, N, NU))
+        ap, al = _arr_opt(pi, (B, N, NX)), _arr_opt(lam, (B, N, 8))
+        self._chk(self._L.brov_set_iterate_host(self._h, _dp(ax), _dp(au), _dp(ap), _dp(al)), "set_iterate")
 
     def get_iterate(self):
         B, N = self.B, self.N

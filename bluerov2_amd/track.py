@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from .solver import _load, NoDeviceError
+from .solver import _Handle, _arr, _bind, _dp, _load
 
 # brov_track_stats, 96 bytes per instance
 TRACK_STATS_DTYPE = np.dtype([("sum_pos2", "f8"), ("sum_yaw2", "f8"), ("max_pos2", "f8"), ("max_yaw", "f8"), ("sum_u2", "f8", (4,)),
@@ -31,72 +31,35 @@ class TrackSummary(C.Structure):
                 ("failed_instances", C.c_int32)]
 
 
-_bound = False
+def _protos(L):
+    vp, dp, ip = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    L.brov_track_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.POINTER(TrackParams)]
+    _bind(L, {"brov_track_last_error": []}, C.c_char_p)
+    _bind(L, {"brov_track_default_params": [C.POINTER(TrackParams)], "brov_track_destroy": [vp]}, None)
+    _bind(L, {
+        "brov_track_batch": [vp], "brov_track_reset": [vp],
+        "brov_track_accumulate_host": [vp, dp, dp, ip, C.c_int, dp, C.c_int, C.c_int],
+        "brov_track_accumulate_device": [vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp],
+        "brov_track_get_stats_host": [vp, vp], "brov_track_get_summary_host": [vp, C.POINTER(TrackSummary)],
+        "brov_track_last_seconds": [vp, dp],
+        "brov_closed_loop_track": [vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int],
+    })
 
 
 def _track_lib():
-    global _bound
-    L = _load()
-    if not _bound:
-        vp, dp, ip = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32)
-        L.brov_track_last_error.restype = C.c_char_p
-        L.brov_track_default_params.argtypes = [C.POINTER(TrackParams)]
-        L.brov_track_default_params.restype = None
-        L.brov_track_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.POINTER(TrackParams)]
-        L.brov_track_destroy.argtypes = [vp]
-        L.brov_track_destroy.restype = None
-        for name, args in {
-            "brov_track_batch": [vp], "brov_track_reset": [vp],
-            "brov_track_accumulate_host": [vp, dp, dp, ip, C.c_int, dp, C.c_int, C.c_int],
-            "brov_track_accumulate_device": [vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp],
-            "brov_track_get_stats_host": [vp, vp], "brov_track_get_summary_host": [vp, C.POINTER(TrackSummary)],
-            "brov_track_last_seconds": [vp, dp],
-            "brov_closed_loop_track": [vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int],
-        }.items():
-            fn = getattr(L, name)
-            fn.argtypes = args
-            fn.restype = C.c_int
-        _bound = True
-    return L
+    return _load(_protos)
 
 
-def _dp(a):
-    return a.ctypes.data_as(C.POINTER(C.c_double))
-
-
-def _c(a, shape, dtype=np.float64):
-    a = np.ascontiguousarray(a, dtype=dtype)
-    if a.shape != tuple(shape):
-        raise ValueError(f"expected shape {tuple(shape)}, got {a.shape}")
-    return a
-
-
-class BatchTrack:
+class BatchTrack(_Handle):
     """One tracking-statistics record per instance, resident on one GPU (brov_track).  Fed by accumulate() from logs or by
     BatchSolver.closed_loop_track(); stats() = the records, summary() = the whole batch."""
+    _last_error, _destroy = "brov_track_last_error", "brov_track_destroy"
 
     def __init__(self, batch, params=None, device=0):
         L = _track_lib()
         self.B = int(batch)
         self.params = params if params is not None else TrackParams.default()
-        h = C.c_void_p()
-        rc = L.brov_track_create(C.byref(h), int(device), self.B, C.byref(self.params))
-        if rc == -2:
-            raise NoDeviceError(L.brov_track_last_error().decode() or "no HIP device")
-        if rc != 0:
-            raise RuntimeError(f"brov_track_create failed ({rc}): {L.brov_track_last_error().decode()}")
-        self._h, self._L = h, L
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.brov_track_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def _chk(self, rc, what):
-        if rc != 0:
-            raise RuntimeError(f"{what} failed ({rc}): {self._L.brov_track_last_error().decode()}")
+        self._create(L, "brov_track_create", int(device), self.B, C.byref(self.params))
 
     def reset(self):
         self._chk(self._L.brov_track_reset(self._h), "reset")
@@ -106,13 +69,13 @@ class BatchTrack:
         row min(line1 + j, rows - 1)"""
         x = np.ascontiguousarray(x, dtype=np.float64)
         K = x.shape[0] if x.ndim == 3 else 0
-        x = _c(x, (K, self.B, 12)); u = _c(u, (K, self.B, 4))
+        x = _arr(x, (K, self.B, 12)); u = _arr(u, (K, self.B, 4))
         ref = np.ascontiguousarray(ref, dtype=np.float64)
         if ref.ndim != 2 or ref.shape[1] != 16:
             raise ValueError(f"expected a table [rows, 16], got {ref.shape}")
         sp = None
         if status is not None:
-            status = _c(status, (K, self.B), np.int32)
+            status = _arr(status, (K, self.B), np.int32)
             sp = status.ctypes.data_as(C.POINTER(C.c_int32))
         self._chk(self._L.brov_track_accumulate_host(self._h, _dp(x), _dp(u), sp, K, _dp(ref), ref.shape[0], int(line1)), "accumulate")
 
