@@ -1,0 +1,301 @@
+// fleet_api.hip -- host side of the fleet planning loop (include/bluerov2_nmpc.h, brov_fleet_*; kernels: fleet_kernel.hip).  A brov_fleet is
+// laid over a brov_solver of batch B = V * C and owns what the solver has no place for: the V vehicle states, the input each vehicle was
+// given last, the winners of the last select and the vehicles' true parameters.  It reaches the solver through its public calls
+// (brov_order_stream, brov_set_yref_candidates, brov_solve, the DEVICE pointers) and solver_view() of host_common.hpp.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <string>
+
+#include "fleet_kernel.hpp"
+#include "host_common.hpp"
+
+using namespace brov;
+
+static thread_local std::string g_fleet_err;
+#define HIPCHK(call) BROV_HIPCHK(g_fleet_err, call)
+
+struct brov_fleet {
+    brov_solver* s = nullptr;
+    int device = 0, V = 0, C = 0, B = 0, N = 0;
+    double* xv = nullptr;              // [V][12] measured vehicle states
+    double* u_hold = nullptr;          // [V][4] input applied last (zeros after reset)
+    double* pplant = nullptr;          // [V][16] true parameters (brov_fleet_set_plant_params_host)
+    bool pplant_set = false;
+    int32_t* winner = nullptr;         // [V] of the last select
+    int32_t* status = nullptr;         // [V] of the last step
+    brov_result* winner_rec = nullptr; // [V] brov_fleet_select_host
+    brov_result* stage_rec = nullptr;  // [B] brov_fleet_select_host: the caller's records on the device
+    long long ticks = 0;               // steps since the last reset
+    hipStream_t last_stream = nullptr;
+    KernelTimer timer;                 // around the last select kernel
+    hipEvent_t ev_done = nullptr;      // behind the last enqueued work
+    bool done_valid = false;
+    DeviceAllocs mem;
+};
+
+extern "C" const char* brov_fleet_last_error(void) { return g_fleet_err.c_str(); }
+
+extern "C" void brov_fleet_destroy(brov_fleet* f) {
+    if (!f) return;
+    (void)hipSetDevice(f->device);
+    (void)hipStreamSynchronize(f->last_stream);
+    f->mem.free_all();
+    f->timer.destroy();
+    if (f->ev_done) (void)hipEventDestroy(f->ev_done);
+    delete f;
+}
+
+extern "C" int brov_fleet_vehicles(const brov_fleet* f) { return f ? f->V : 0; }
+extern "C" int brov_fleet_candidates(const brov_fleet* f) { return f ? f->C : 0; }
+
+// work on `st` behind whatever the fleet enqueued last, without a host wait
+static int order_behind(brov_fleet* f, hipStream_t st) {
+    if (f->done_valid && f->last_stream != st) HIPCHK(hipStreamWaitEvent(st, f->ev_done, 0));
+    return BROV_OK;
+}
+static int enqueued_on(brov_fleet* f, hipStream_t st) {
+    HIPCHK(hipEventRecord(f->ev_done, st));
+    f->done_valid = true;
+    f->last_stream = st;
+    return BROV_OK;
+}
+// `st` behind the solver's last stream and behind the fleet's own
+static int order_both(brov_fleet* f, hipStream_t st, const char* who) {
+    if (brov_order_stream(f->s, st) != BROV_OK) {
+        g_fleet_err = std::string(who) + ": could not order behind the solver's last stream";
+        return BROV_ERR_HIP;
+    }
+    return order_behind(f, st);
+}
+// host-side wait for everything that may still touch the fleet's or the solver's arrays
+static int wait_all(brov_fleet* f, const char* who) {
+    if (int rc = order_both(f, nullptr, who)) return rc;
+    HIPCHK(hipStreamSynchronize(f->last_stream));
+    HIPCHK(hipStreamSynchronize(nullptr));
+    return BROV_OK;
+}
+
+extern "C" int brov_fleet_reset(brov_fleet* f) {
+    if (!f) { g_fleet_err = "brov_fleet_reset: null argument"; return BROV_ERR_ARG; }
+    HIPCHK(hipSetDevice(f->device));
+    if (int rc = wait_all(f, "brov_fleet_reset")) return rc;
+    HIPCHK(hipMemset(f->u_hold, 0, (size_t)f->V * 4 * sizeof(double)));
+    HIPCHK(hipMemset(f->status, 0, (size_t)f->V * sizeof(int32_t)));
+    HIPCHK(hipMemset(f->winner, 0xff, (size_t)f->V * sizeof(int32_t)));   // -1: no select yet
+    // xv[v] := x0 of candidate 0 of group v
+    HIPCHK(hipMemcpy2D(f->xv, 12 * sizeof(double), brov_x0_device(f->s), (size_t)f->C * 12 * sizeof(double), 12 * sizeof(double), (size_t)f->V,
+                       hipMemcpyDeviceToDevice));
+    f->ticks = 0;
+    return BROV_OK;
+}
+
+extern "C" int brov_fleet_create(brov_fleet** out, brov_solver* s, int candidates) {
+    if (!out || !s) { g_fleet_err = "brov_fleet_create: null argument"; return BROV_ERR_ARG; }
+    *out = nullptr;
+    const int B = brov_batch(s);
+    if (candidates < 1 || candidates > B || B % candidates != 0) {
+        g_fleet_err = "brov_fleet_create: the solver's batch of " + std::to_string(B) + " is not a whole number of groups of " +
+                      std::to_string(candidates) + " candidates (needs 1 <= candidates <= B and B % candidates == 0)";
+        return BROV_ERR_ARG;
+    }
+    const SolverView sv = solver_view(s);
+    HIPCHK(hipSetDevice(sv.device));
+    brov_fleet* f = new brov_fleet();
+    f->s = s; f->device = sv.device; f->B = B; f->C = candidates; f->V = B / candidates; f->N = brov_horizon(s);
+    const size_t V = (size_t)f->V;
+    int rc = f->mem.alloc(&f->xv, V * 12, g_fleet_err);
+    if (rc == BROV_OK) rc = f->mem.alloc(&f->u_hold, V * 4, g_fleet_err);
+    if (rc == BROV_OK) rc = f->mem.alloc(&f->pplant, V * 16, g_fleet_err);
+    if (rc == BROV_OK) rc = f->mem.alloc(&f->winner, V, g_fleet_err);
+    if (rc == BROV_OK) rc = f->mem.alloc(&f->status, V, g_fleet_err);
+    if (rc == BROV_OK) rc = f->mem.alloc(&f->winner_rec, V, g_fleet_err);
+    if (rc == BROV_OK) rc = f->mem.alloc(&f->stage_rec, (size_t)B, g_fleet_err);
+    if (rc != BROV_OK) {
+        g_fleet_err = "brov_fleet_create: " + g_fleet_err;
+        brov_fleet_destroy(f);
+        return rc;
+    }
+    if (f->timer.create() != hipSuccess || hipEventCreateWithFlags(&f->ev_done, hipEventDisableTiming) != hipSuccess) {
+        g_fleet_err = "brov_fleet_create: device initialisation failed";
+        brov_fleet_destroy(f);
+        return BROV_ERR_HIP;
+    }
+    if ((rc = brov_fleet_reset(f)) != BROV_OK) { brov_fleet_destroy(f); return rc; }
+    *out = f;
+    return BROV_OK;
+}
+
+extern "C" int brov_fleet_set_state_host(brov_fleet* f, const double* xv) {
+    if (!f || !xv) { g_fleet_err = "brov_fleet_set_state_host: null argument"; return BROV_ERR_ARG; }
+    HIPCHK(hipSetDevice(f->device));
+    if (int rc = wait_all(f, "brov_fleet_set_state_host")) return rc;
+    HIPCHK(hipMemcpy(f->xv, xv, (size_t)f->V * 12 * sizeof(double), hipMemcpyHostToDevice));
+    launch_fleet_bcast(f->xv, f->V, f->C, brov_x0_device(f->s), nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(nullptr));
+    return BROV_OK;
+}
+
+extern "C" int brov_fleet_get_state_host(brov_fleet* f, double* xv) {
+    if (!f || !xv) { g_fleet_err = "brov_fleet_get_state_host: null argument"; return BROV_ERR_ARG; }
+    HIPCHK(hipSetDevice(f->device));
+    HIPCHK(hipStreamSynchronize(f->last_stream));
+    HIPCHK(hipMemcpy(xv, f->xv, (size_t)f->V * 12 * sizeof(double), hipMemcpyDeviceToHost));
+    return BROV_OK;
+}
+
+extern "C" int brov_fleet_set_plant_params_host(brov_fleet* f, const double* p) {
+    if (!f) { g_fleet_err = "brov_fleet_set_plant_params_host: null argument"; return BROV_ERR_ARG; }
+    HIPCHK(hipSetDevice(f->device));
+    HIPCHK(hipStreamSynchronize(f->last_stream));   // a plant step in flight may still read the buffer
+    if (p) HIPCHK(hipMemcpy(f->pplant, p, (size_t)f->V * 16 * sizeof(double), hipMemcpyHostToDevice));
+    f->pplant_set = p != nullptr;
+    return BROV_OK;
+}
+
+// the select on `st`, timed; the caller has ordered the stream
+static int select_on(brov_fleet* f, const brov_result* rec, int32_t* winner, brov_result* winner_rec, hipStream_t st) {
+    HIPCHK(f->timer.start(st));
+    launch_fleet_select(rec, f->V, f->C, winner, winner_rec, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(f->timer.stop(st));
+    return BROV_OK;
+}
+
+extern "C" int brov_fleet_select_device(brov_fleet* f, const brov_result* rec, int32_t* winner, brov_result* winner_rec, void* stream) {
+    if (!f || !winner) { g_fleet_err = "brov_fleet_select_device: null argument"; return BROV_ERR_ARG; }
+    HIPCHK(hipSetDevice(f->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = order_both(f, st, "brov_fleet_select_device")) return rc;
+    if (int rc = select_on(f, rec ? rec : brov_results_device(f->s), winner, winner_rec, st)) return rc;
+    return enqueued_on(f, st);
+}
+
+extern "C" int brov_fleet_select_host(brov_fleet* f, const brov_result* rec_host, int32_t* winner, brov_result* winner_rec) {
+    if (!f || !winner) { g_fleet_err = "brov_fleet_select_host: null argument"; return BROV_ERR_ARG; }
+    HIPCHK(hipSetDevice(f->device));
+    if (int rc = wait_all(f, "brov_fleet_select_host")) return rc;   // the staging buffer and the winners may still be in use
+    if (rec_host) HIPCHK(hipMemcpy(f->stage_rec, rec_host, (size_t)f->B * sizeof(brov_result), hipMemcpyHostToDevice));
+    if (int rc = select_on(f, rec_host ? f->stage_rec : brov_results_device(f->s), f->winner, winner_rec ? f->winner_rec : nullptr, nullptr)) return rc;
+    if (int rc = enqueued_on(f, nullptr)) return rc;
+    HIPCHK(hipStreamSynchronize(nullptr));
+    HIPCHK(hipMemcpy(winner, f->winner, (size_t)f->V * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (winner_rec) HIPCHK(hipMemcpy(winner_rec, f->winner_rec, (size_t)f->V * sizeof(brov_result), hipMemcpyDeviceToHost));
+    return BROV_OK;
+}
+
+// what the plant of the fleet does not model (follow-ups)
+static int plant_modes_ok(const brov_fleet* f, const char* who) {
+    if (brov_plant_wrench_mode(f->s) != BROV_WRENCH_OFF) {
+        g_fleet_err = std::string(who) + ": a plant wrench mode is in force (brov_plant_wrench_*); the fleet's plant knows no wrench";
+        return BROV_ERR_ARG;
+    }
+    if (brov_dist6_enabled(f->s) == 1) {
+        g_fleet_err = std::string(who) + ": the 6-disturbance variant is on (brov_enable_dist6); the fleet's plant integrates the shipped model";
+        return BROV_ERR_ARG;
+    }
+    return BROV_OK;
+}
+
+// select + plant + broadcast on `st` (ordered by the caller), with optional DEVICE log rows of this tick
+static int step_on(brov_fleet* f, const brov_result* rec, double dt, int substeps, double* xlog, double* ulog, int32_t* stlog, int32_t* winlog,
+                   hipStream_t st) {
+    if (!rec) rec = brov_results_device(f->s);
+    if (int rc = select_on(f, rec, f->winner, nullptr, st)) return rc;
+    FleetPlantArgs a;
+    a.V = f->V; a.C = f->C; a.xv = f->xv; a.res = rec; a.winner = f->winner;
+    if (f->pplant_set) { a.pp = f->pplant; a.pp_stride = 16; }
+    else { a.pp = solver_view(f->s).par; a.pp_stride = (long long)f->C * (f->N + 1) * 16; }   // stage 0 of candidate 0, as it stands now
+    a.dt = dt; a.substeps = substeps; a.u_hold = f->u_hold; a.status = f->status;
+    a.xlog = xlog; a.ulog = ulog; a.stlog = stlog; a.winlog = winlog;
+    launch_fleet_plant(a, st);
+    HIPCHK(hipGetLastError());
+    launch_fleet_bcast(f->xv, f->V, f->C, brov_x0_device(f->s), st);
+    HIPCHK(hipGetLastError());
+    f->ticks++;
+    return enqueued_on(f, st);
+}
+
+extern "C" int brov_fleet_step(brov_fleet* f, const brov_result* rec, double dt, int substeps, void* stream) {
+    if (!f || !(dt > 0.0) || !std::isfinite(dt) || substeps < 1) {
+        g_fleet_err = "brov_fleet_step: bad argument (needs dt > 0 and substeps >= 1)";
+        return BROV_ERR_ARG;
+    }
+    if (int rc = plant_modes_ok(f, "brov_fleet_step")) return rc;
+    HIPCHK(hipSetDevice(f->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = order_both(f, st, "brov_fleet_step")) return rc;
+    return step_on(f, rec, dt, substeps, nullptr, nullptr, nullptr, nullptr, st);
+}
+
+extern "C" int brov_fleet_get_last_host(brov_fleet* f, double* u, int32_t* status, int32_t* winner) {
+    if (!f) { g_fleet_err = "brov_fleet_get_last_host: null argument"; return BROV_ERR_ARG; }
+    HIPCHK(hipSetDevice(f->device));
+    HIPCHK(hipStreamSynchronize(f->last_stream));
+    if (u) HIPCHK(hipMemcpy(u, f->u_hold, (size_t)f->V * 4 * sizeof(double), hipMemcpyDeviceToHost));
+    if (status) HIPCHK(hipMemcpy(status, f->status, (size_t)f->V * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (winner) HIPCHK(hipMemcpy(winner, f->winner, (size_t)f->V * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return BROV_OK;
+}
+
+extern "C" int brov_closed_loop_fleet(brov_fleet* f, int ticks, double t0, double dt_ref, double dt_node, double dt, int substeps, double* u_log,
+                                      double* x_log, int32_t* st_log, int32_t* win_log) {
+    if (!f || ticks < 0 || !std::isfinite(t0) || !std::isfinite(dt_ref) || !std::isfinite(dt_node) || !(dt > 0.0) || !std::isfinite(dt) ||
+        substeps < 1) {
+        g_fleet_err = "brov_closed_loop_fleet: bad argument (needs ticks >= 0, finite t0, dt_ref and dt_node, dt > 0, substeps >= 1)";
+        return BROV_ERR_ARG;
+    }
+    if (int rc = plant_modes_ok(f, "brov_closed_loop_fleet")) return rc;
+    const SolverView sv = solver_view(f->s);
+    if (!sv.cand_set) {
+        g_fleet_err = "brov_closed_loop_fleet: no candidate parameters (brov_set_candidate_params_host)";
+        return BROV_ERR_ARG;
+    }
+    HIPCHK(hipSetDevice(f->device));
+    hipStream_t st = sv.last_stream;
+    const size_t V = (size_t)f->V, n = (size_t)ticks;
+    // DEVICE logs for the whole run, a block per HOST log asked for; the states behind the start state
+    DeviceAllocs logs;
+    double *dx = nullptr, *du = nullptr;
+    int32_t *dst = nullptr, *dwin = nullptr;
+    int rc = BROV_OK;
+    if (x_log) rc = logs.alloc(&dx, (n + 1) * V * 12, g_fleet_err);
+    if (u_log && n && rc == BROV_OK) rc = logs.alloc(&du, n * V * 4, g_fleet_err);
+    if (st_log && n && rc == BROV_OK) rc = logs.alloc(&dst, n * V, g_fleet_err);
+    if (win_log && n && rc == BROV_OK) rc = logs.alloc(&dwin, n * V, g_fleet_err);
+    if (rc != BROV_OK) g_fleet_err = "brov_closed_loop_fleet: " + g_fleet_err;
+    if (rc == BROV_OK) rc = order_both(f, st, "brov_closed_loop_fleet");
+    if (rc == BROV_OK && dx && hipMemcpyAsync(dx, f->xv, V * 12 * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess) {
+        (void)hipGetLastError();
+        g_fleet_err = "brov_closed_loop_fleet: log initialisation failed";
+        rc = BROV_ERR_HIP;
+    }
+    for (int k = 0; k < ticks && rc == BROV_OK; k++) {
+        rc = brov_set_yref_candidates(f->s, t0 + k * dt_ref, dt_node, st);
+        if (rc == BROV_OK) rc = brov_solve(f->s, st);
+        if (rc != BROV_OK) { g_fleet_err = std::string("brov_closed_loop_fleet: ") + brov_last_error(); break; }
+        rc = step_on(f, nullptr, dt, substeps, dx ? dx + (size_t)(k + 1) * V * 12 : nullptr, du ? du + (size_t)k * V * 4 : nullptr,
+                     dst ? dst + (size_t)k * V : nullptr, dwin ? dwin + (size_t)k * V : nullptr, st);
+    }
+    // the one host wait, then a launch error nobody has picked up
+    hipError_t err = hipStreamSynchronize(st);
+    if (rc == BROV_OK && err == hipSuccess) err = hipGetLastError();
+    if (rc == BROV_OK && err != hipSuccess) { g_fleet_err = std::string("brov_closed_loop_fleet: ") + hipGetErrorString(err); rc = BROV_ERR_HIP; }
+    if (rc == BROV_OK) {   // logs only from a loop that completed
+        if (dx && hipMemcpy(x_log, dx, (n + 1) * V * 12 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = BROV_ERR_HIP;
+        if (du && hipMemcpy(u_log, du, n * V * 4 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = BROV_ERR_HIP;
+        if (dst && hipMemcpy(st_log, dst, n * V * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) rc = BROV_ERR_HIP;
+        if (dwin && hipMemcpy(win_log, dwin, n * V * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) rc = BROV_ERR_HIP;
+        if (rc != BROV_OK) { (void)hipGetLastError(); g_fleet_err = "brov_closed_loop_fleet: copying the logs back failed"; }
+    }
+    logs.free_all();
+    return rc;
+}
+
+extern "C" int brov_fleet_last_seconds(brov_fleet* f, double* select_seconds) {
+    if (!f || !select_seconds || !f->timer.valid) { g_fleet_err = "brov_fleet_last_seconds: no select yet"; return BROV_ERR_ARG; }
+    HIPCHK(hipSetDevice(f->device));
+    return f->timer.seconds(select_seconds, g_fleet_err);
+}

@@ -95,6 +95,16 @@ struct KernelTimer {
     }
 };
 
+// ---- what a component that is laid over a solver (brov_fleet) asks of it beyond the public accessors, without the side effects of the
+// public hand-outs (brov_params_device marks the plant's copy of the parameters stale); filled by nmpc_api.hip -------------------------------
+struct SolverView {
+    int device = 0;
+    const double* par = nullptr;          // [B][N+1][16] model parameters in force
+    bool cand_set = false;                // candidate shape parameters are resident (brov_set_candidate_params_host)
+    hipStream_t last_stream = nullptr;    // where the solver enqueued last: the stream its closed loops run on
+};
+SolverView solver_view(const brov_solver* s);
+
 // ---- a device buffer that lives as long as a scope: freed on every way out, unless release() hands it on ---------------------------------
 template <typename T>
 struct ScopedDeviceBuffer {

@@ -380,6 +380,13 @@ extern "C" void brov_destroy(brov_solver* s) {
     delete s;
 }
 
+namespace brov {
+SolverView solver_view(const brov_solver* s) {
+    SolverView v;
+    v.device = s->device; v.par = s->par; v.cand_set = s->cand_set; v.last_stream = s->last_stream;
+    return v;
+}
+}  // namespace brov
 extern "C" int brov_batch(const brov_solver* s) { return s ? s->B : 0; }
 extern "C" int brov_horizon(const brov_solver* s) { return s ? s->N : 0; }
 extern "C" size_t brov_device_bytes(const brov_solver* s) { return s ? s->mem.bytes : 0; }

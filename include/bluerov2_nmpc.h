@@ -619,6 +619,52 @@ int brov_track_last_seconds(brov_track* t, double* seconds);
 int brov_closed_loop_track(brov_solver* s, brov_ekf* e /*NULL: no observer*/, brov_rls* r /*NULL: DOB; else AMPC*/, int rls_mode, brov_track* t,
                            int ticks, int line0, int ncols, double dt, int substeps, int chunk);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Fleet planning loop: per-vehicle candidate selection on the device (BASELINE config 4 as a planner).
+ * A fleet is V vehicles x C candidates laid over ONE brov_solver of batch B = V * C: instance b = v * C + c is candidate c of vehicle v,
+ * and all candidates of a vehicle share that vehicle's measured state xv[v].  One planning tick: the candidates' windows are built
+ * (brov_set_yref_candidates), all B candidates are solved in one launch (brov_solve), and brov_fleet_step
+ *   selects  per vehicle the eligible candidate of the lowest cost, the lowest index on equal cost; eligible = status SUCCESS and a finite
+ *            cost (NaN and +-Inf never win); winner = its index c within the group, -1 when the group has no eligible candidate
+ *   steps    the vehicle's plant -- the ERK4 of brov_plant_step -- with the winner's u0 and the vehicle's true parameters.  Without a winner
+ *            the vehicle is stepped with the input it was given last (zeros after brov_fleet_reset): the zero-order hold brov_opts::on_failure
+ *            documents for one instance.  Logged status: 0 with a winner; without one the status of candidate 0 of the group if that is
+ *            non-zero, else BROV_STATUS_NAN (candidate 0 reported success with a cost that is not finite)
+ *   measures the new xv[v] becomes x0 of every candidate of vehicle v
+ * The candidates' iterates are left alone: each candidate warm-starts from its own last step (the iterate is not shifted).  The fleet does
+ * not own the solver, which must outlive it; the solver's x0 is the fleet's to write once a step has run.  The plant of the fleet knows
+ * neither a world-frame wrench (brov_plant_wrench_*) nor the 6-disturbance variant: brov_fleet_step and brov_closed_loop_fleet fail with
+ * BROV_ERR_ARG while either is in force, and brov_closed_loop_fleet also when no candidate parameters were uploaded
+ * (brov_set_candidate_params_host).  Every enqueueing call is ordered behind the solver's last stream (brov_order_stream).
+ * ------------------------------------------------------------------------------------------------------------------- */
+typedef struct brov_fleet brov_fleet;
+const char* brov_fleet_last_error(void); /* message of the last failing brov_fleet_* / brov_closed_loop_fleet call on this thread */
+int  brov_fleet_create(brov_fleet** out, brov_solver* s, int candidates);   /* B % candidates == 0, 1 <= candidates <= B; else BROV_ERR_ARG */
+void brov_fleet_destroy(brov_fleet* f);                                      /* does not destroy the solver */
+int  brov_fleet_vehicles(const brov_fleet* f);
+int  brov_fleet_candidates(const brov_fleet* f);
+int  brov_fleet_reset(brov_fleet* f);                    /* u_hold = 0; xv := x0 of candidate 0 of every group; tick counter 0 (done by create) */
+int  brov_fleet_set_state_host(brov_fleet* f, const double* xv /*[V][12]*/);   /* also broadcast into the solver's x0 */
+int  brov_fleet_get_state_host(brov_fleet* f, double* xv /*[V][12]*/);
+int  brov_fleet_set_plant_params_host(brov_fleet* f, const double* p /*[V][16]; NULL: stage-0 parameters of candidate 0 of each group, re-read at every step*/);
+/* segmented select alone.  rec: DEVICE [B] records, NULL = the solver's own (brov_results_device).  winner DEVICE [V], winner_rec DEVICE [V] or
+ * NULL: a copy of the winning record, zeros where winner == -1.  Two calls on the same records return the same bytes. */
+int  brov_fleet_select_device(brov_fleet* f, const brov_result* rec, int32_t* winner, brov_result* winner_rec, void* stream);
+int  brov_fleet_select_host(brov_fleet* f, const brov_result* rec_host /*[B] or NULL*/, int32_t* winner /*[V]*/, brov_result* winner_rec /*[V] or NULL*/);
+/* select + plant + broadcast from the given records (DEVICE [B]; NULL = the solver's).  Callers that re-score candidates
+ * (e.g. add a penalty to `cost`) pass their own records. */
+int  brov_fleet_step(brov_fleet* f, const brov_result* rec, double dt, int substeps, void* stream);
+/* of the last step, HOST, any may be NULL: the input every vehicle was given u [V][4], its status [V] and its winner [V] */
+int  brov_fleet_get_last_host(brov_fleet* f, double* u, int32_t* status, int32_t* winner);
+/* `ticks` planning ticks, one host wait at the end.  Per tick k: brov_set_yref_candidates(s, t0 + k*dt_ref, dt_node) -> brov_solve(s) -> brov_fleet_step,
+ * on the solver's last stream, from the solver's x0 as it stands (brov_fleet_reset / brov_fleet_set_state_host make it the fleet's xv).
+ * HOST logs, any may be NULL: u_log [ticks][V][4], x_log [ticks+1][V][12], st_log [ticks][V], win_log [ticks][V] -- the layouts of
+ * brov_track_accumulate_host at batch V.  Logs are delivered only when the whole loop succeeded (the contract of brov_closed_loop_ex). */
+int  brov_closed_loop_fleet(brov_fleet* f, int ticks, double t0, double dt_ref, double dt_node, double dt, int substeps,
+                            double* u_log, double* x_log, int32_t* st_log, int32_t* win_log);
+/* seconds of the last select kernel (HIP events on its stream) */
+int  brov_fleet_last_seconds(brov_fleet* f, double* select_seconds);
+
 #ifdef __cplusplus
 }
 #endif
