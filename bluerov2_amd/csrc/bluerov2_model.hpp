@@ -9,6 +9,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 namespace brov {
 
 constexpr int NX = 12, NU = 4, NP = 16, NY = 16;
@@ -99,45 +101,22 @@ struct StagePoint {
     double vu, vv, vw, wp, wq, wr;
 };
 
-// xdot = f(x,u,p); also returns the stage point record
-__device__ __forceinline__ void model_f(const double (&x)[NX], const Wrench& w, const ModelPar& m, double (&f)[NX],
-                                        StagePoint& sp) {
-    sincos_pio2(x[3], &sp.sph, &sp.cph);
-    sincos_pio2(x[4], &sp.sth, &sp.cth);
-    sincos_pio2(x[5], &sp.sps, &sp.cps);
-    sp.icth = 1.0 / sp.cth;
-    sp.vu = x[6]; sp.vv = x[7]; sp.vw = x[8]; sp.wp = x[9]; sp.wq = x[10]; sp.wr = x[11];
-    const double r00 = sp.cps * sp.cth, r01 = sp.cps * sp.sth * sp.sph - sp.sps * sp.cph,
-                 r02 = sp.sps * sp.sph + sp.cps * sp.cph * sp.sth;
-    const double r10 = sp.sps * sp.cth, r11 = sp.cps * sp.cph + sp.sph * sp.sth * sp.sps,
-                 r12 = sp.sth * sp.sps * sp.cph - sp.cps * sp.sph;
-    const double r21 = sp.cth * sp.sph, r22 = sp.cth * sp.cph;
-    f[0] = r00 * sp.vu + r01 * sp.vv + r02 * sp.vw;
-    f[1] = r10 * sp.vu + r11 * sp.vv + r12 * sp.vw;
-    f[2] = -sp.sth * sp.vu + r21 * sp.vv + r22 * sp.vw;
-    const double tth = sp.sth * sp.icth;
-    f[3] = sp.wp + sp.sps * tth * sp.wq + sp.cph * tth * sp.wr;  // sin(psi): reference quirk, bluerov2.py:133
-    f[4] = sp.cph * sp.wq + sp.sph * sp.wr;
-    f[5] = (sp.sph * sp.wq + sp.cph * sp.wr) * sp.icth;
-    f[6] = (w.k0 - kBouy * sp.sth + m.dx + m.lx * sp.vu + m.qx * fabs(sp.vu) * sp.vu) * m.imx;
-    f[7] = (w.k1 + kBouy * r21 + m.dy + m.ly * sp.vv + m.qy * fabs(sp.vv) * sp.vv) * m.imy;
-    f[8] = (w.k2 + kBouy * r22 + m.dz + m.lz * sp.vw + m.qz * fabs(sp.vw) * sp.vw) * m.imz;
-    f[9] = (w.k3 + (kIy - kIz) * sp.wq * sp.wr - kMzg * r21) * (1.0 / kIx);
-    f[10] = (w.k4 + (kIz - kIx) * sp.wp * sp.wr - kMzg * sp.sth) * (1.0 / kIy);
-    f[11] = (w.k5 - (kIy - kIx) * sp.wp * sp.wq + m.dn + m.ln * sp.wr + m.qn * fabs(sp.wr) * sp.wr) * m.imn;
-}
-
 // A wrench given in the WORLD frame (the reference's applyBodyWrench(), bluerov2_dob.cpp:876-890: reference_frame = "world"), constant
-// over a control tick; its body-frame image turns with the vehicle.
+// over a control tick; its body-frame image turns with the vehicle.  NoWorldWrench: the tag of a model without one.
 struct WorldWrench { double fx, fy, fz, tx, ty, tz; };
+struct NoWorldWrench {};
 
-// xdot = f(x,u,p) under an additional world-frame wrench: the plant of brov_plant_step with a wrench mode in force (plant_wrench.hip).
-// Force and torque are projected with THIS stage point's attitude, f_b = R^T f_w, t_b = R^T t_w -- from the trig values the model computes
-// anyway -- and enter where the model's own disturbances do: dx, dy, dz, k3, k4, dn, ahead of the mass scaling.  An overload with the rows
-// written out again, not a default argument of the function above: the solver kernels that inline that one sit at their register limit
-// behind the build's scratch gate and ISA checkers, and must compile to the code they compiled to before this overload existed.
-__device__ __forceinline__ void model_f(const double (&x)[NX], const Wrench& w, const ModelPar& m, const WorldWrench& ww, double (&f)[NX],
+// xdot = f(x,u,p), WW = NoWorldWrench: the model of the OCP; also returns the stage point record.
+// WW = WorldWrench: the same model under an additional world-frame wrench, the plant of brov_plant_step with a wrench mode in force
+// (plant_wrench.hip).  Force and torque are projected with THIS stage point's attitude, f_b = R^T f_w, t_b = R^T t_w -- from the trig
+// values the model computes anyway -- and enter where the model's own disturbances do: dx, dy, dz, k3, k4, dn, ahead of the mass scaling.
+// One body for both: the projection sits under `if constexpr`, so the NoWorldWrench instantiation holds no statement of it and the
+// solver kernels that inline it -- at their register limit, behind the build's scratch gate and ISA checkers -- compile to the code they
+// compiled to when the function had no such parameter (profiles/plant_step_refactor_isa.txt: instruction for instruction).
+template <class WW>
+__device__ __forceinline__ void model_f(const double (&x)[NX], const Wrench& w, const ModelPar& m, const WW& ww, double (&f)[NX],
                                         StagePoint& sp) {
+    static_assert(std::is_same_v<WW, WorldWrench> || std::is_same_v<WW, NoWorldWrench>, "a world wrench or the tag for none");
     sincos_pio2(x[3], &sp.sph, &sp.cph);
     sincos_pio2(x[4], &sp.sth, &sp.cth);
     sincos_pio2(x[5], &sp.sps, &sp.cps);
@@ -148,15 +127,18 @@ __device__ __forceinline__ void model_f(const double (&x)[NX], const Wrench& w, 
     const double r10 = sp.sps * sp.cth, r11 = sp.cps * sp.cph + sp.sph * sp.sth * sp.sps,
                  r12 = sp.sth * sp.sps * sp.cph - sp.cps * sp.sph;
     const double r20 = -sp.sth, r21 = sp.cth * sp.sph, r22 = sp.cth * sp.cph;
-    const double dx = m.dx + (r00 * ww.fx + r10 * ww.fy + r20 * ww.fz);
-    const double dy = m.dy + (r01 * ww.fx + r11 * ww.fy + r21 * ww.fz);
-    const double dz = m.dz + (r02 * ww.fx + r12 * ww.fy + r22 * ww.fz);
-    const double k3 = w.k3 + (r00 * ww.tx + r10 * ww.ty + r20 * ww.tz);
-    const double k4 = w.k4 + (r01 * ww.tx + r11 * ww.ty + r21 * ww.tz);
-    const double dn = m.dn + (r02 * ww.tx + r12 * ww.ty + r22 * ww.tz);
+    double dx = m.dx, dy = m.dy, dz = m.dz, k3 = w.k3, k4 = w.k4, dn = m.dn;
+    if constexpr (std::is_same_v<WW, WorldWrench>) {
+        dx += (r00 * ww.fx + r10 * ww.fy + r20 * ww.fz);
+        dy += (r01 * ww.fx + r11 * ww.fy + r21 * ww.fz);
+        dz += (r02 * ww.fx + r12 * ww.fy + r22 * ww.fz);
+        k3 += (r00 * ww.tx + r10 * ww.ty + r20 * ww.tz);
+        k4 += (r01 * ww.tx + r11 * ww.ty + r21 * ww.tz);
+        dn += (r02 * ww.tx + r12 * ww.ty + r22 * ww.tz);
+    }
     f[0] = r00 * sp.vu + r01 * sp.vv + r02 * sp.vw;
     f[1] = r10 * sp.vu + r11 * sp.vv + r12 * sp.vw;
-    f[2] = r20 * sp.vu + r21 * sp.vv + r22 * sp.vw;
+    f[2] = r20 * sp.vu + r21 * sp.vv + r22 * sp.vw;   // (r20 * vu is the product -sth * vu: the unary minus binds first)
     const double tth = sp.sth * sp.icth;
     f[3] = sp.wp + sp.sps * tth * sp.wq + sp.cph * tth * sp.wr;  // sin(psi): reference quirk, bluerov2.py:133
     f[4] = sp.cph * sp.wq + sp.sph * sp.wr;
@@ -167,6 +149,67 @@ __device__ __forceinline__ void model_f(const double (&x)[NX], const Wrench& w, 
     f[9] = (k3 + (kIy - kIz) * sp.wq * sp.wr - kMzg * r21) * (1.0 / kIx);
     f[10] = (k4 + (kIz - kIx) * sp.wp * sp.wr - kMzg * sp.sth) * (1.0 / kIy);
     f[11] = (w.k5 - (kIy - kIx) * sp.wp * sp.wq + dn + m.ln * sp.wr + m.qn * fabs(sp.wr) * sp.wr) * m.imn;
+}
+
+// ---- the one plant step of the device ------------------------------------------------------------------------------------------------
+// One explicit RK4 step of size h (gen/acados_solver_bluerov2.c:633-641: 4 stages), xn = x+; sp[i] = the stage point of stage i, which
+// the linearisation keeps (lin_device.hpp, rk4_state) and the plants below let die.
+template <class WW>
+__device__ __forceinline__ void erk4_step(const double (&x)[NX], const Wrench& w, const ModelPar& m, const WW& ww, double h,
+                                          StagePoint (&sp)[4], double (&xn)[NX]) {
+    double k[NX], xs[NX];
+    model_f(x, w, m, ww, k, sp[0]);
+#pragma unroll
+    for (int j = 0; j < NX; j++) { xn[j] = x[j] + (h / 6.0) * k[j]; xs[j] = x[j] + 0.5 * h * k[j]; }
+    model_f(xs, w, m, ww, k, sp[1]);
+#pragma unroll
+    for (int j = 0; j < NX; j++) { xn[j] += (h / 3.0) * k[j]; xs[j] = x[j] + 0.5 * h * k[j]; }
+    model_f(xs, w, m, ww, k, sp[2]);
+#pragma unroll
+    for (int j = 0; j < NX; j++) { xn[j] += (h / 3.0) * k[j]; xs[j] = x[j] + h * k[j]; }
+    model_f(xs, w, m, ww, k, sp[3]);
+#pragma unroll
+    for (int j = 0; j < NX; j++) xn[j] += (h / 6.0) * k[j];
+}
+
+// x <- the state one control period dt later, in `substeps` ERK4 steps with input and wrenches held.  The plant of plant_kernel
+// (plant_wrench.hip) and fleet_plant_kernel (fleet_kernel.hip).  NOT of plant_wrench_kernel (plant_wrench.hip) and plant_step_wave
+// (qp/fused.hpp), which restate erk4_step's statements for the reasons given there: a change to the step is made here AND in those two.
+template <class WW>
+__device__ __forceinline__ void plant_erk4(double (&x)[NX], const Wrench& w, const ModelPar& m, const WW& ww, double dt, int substeps) {
+    const double h = dt / substeps;
+    StagePoint sp[4];
+    double xn[NX];
+    for (int s = 0; s < substeps; s++) {
+        erk4_step(x, w, m, ww, h, sp, xn);
+#pragma unroll
+        for (int j = 0; j < NX; j++) x[j] = xn[j];
+    }
+}
+
+// what a plant step of one instance starts from: x, u = its state and input, p = its 16 true parameters; 6-disturbance variant: its two
+// roll / pitch disturbance moments at rp[rp_off], rp[rp_off + 1] (rp = nullptr: the shipped model, none)
+__device__ __forceinline__ void plant_inputs(const double* x0, const double* u0, const double* p, const double* rp,
+                                             size_t rp_off, double (&x)[NX], double (&u)[NU], ModelPar& m, Wrench& w) {
+#pragma unroll
+    for (int j = 0; j < NX; j++) x[j] = x0[j];
+#pragma unroll
+    for (int j = 0; j < NU; j++) u[j] = u0[j];
+    m = make_par(p);
+    w = make_wrench(u);
+    if (rp) { w.k3 = rp[rp_off]; w.k4 = rp[rp_off + 1]; }
+}
+
+// dst[0 .. n) = v
+template <int n>
+__device__ __forceinline__ void store_row(double* dst, const double (&v)[n]) {
+#pragma unroll
+    for (int j = 0; j < n; j++) dst[j] = v[j];
+}
+// row `row` of a log of n doubles per row, if the log is kept (log = nullptr: it is not)
+template <int n>
+__device__ __forceinline__ void log_row(double* log, size_t row, const double (&v)[n]) {
+    if (log) store_row(log + row * n, v);
 }
 
 }  // namespace brov

@@ -10,8 +10,8 @@
 // `cost` and `status` of a record are read (16 of its 104 bytes), then the winner's record once.  Eligible: status SUCCESS and a finite cost,
 // tested on the exponent bits as track_accumulate_kernel does (an ordering comparison is false for NaN on either side).
 //
-// fleet_plant_kernel: one lane per vehicle; the ERK4 of plant_kernel (traj_kernel.hip): the same make_par / make_wrench / model_f calls and
-// the same update expressions in the same order.
+// fleet_plant_kernel: one lane per vehicle; where its input comes from and what it records is its own, the step between is plant_erk4
+// (bluerov2_model.hpp), the function plant_kernel calls.
 #include <hip/hip_runtime.h>
 
 #include "fleet_kernel.hpp"
@@ -64,56 +64,29 @@ __global__ __launch_bounds__(kFleetSelectBlock) void fleet_select_kernel(const b
 __global__ __launch_bounds__(128) void fleet_plant_kernel(FleetPlantArgs A) {
     const int v = blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= A.V) return;
-    double x[NX], u[NU], k[NX], xs[NX], acc[NX];
-#pragma unroll
-    for (int j = 0; j < NX; j++) x[j] = A.xv[(size_t)v * NX + j];
     const int win = A.winner[v];
     const brov_result* __restrict__ g = A.res + (size_t)v * A.C;
+    const double* usrc;
     int status = BROV_STATUS_SUCCESS;
     if (win >= 0) {
-#pragma unroll
-        for (int j = 0; j < NU; j++) u[j] = g[win].u0[j];
+        usrc = g[win].u0;
     } else {
         // zero-order hold: the input applied last (zeros after a reset); the status is candidate 0's, or NAN where candidate 0 reported
         // success with a cost that is not finite
-#pragma unroll
-        for (int j = 0; j < NU; j++) u[j] = A.u_hold[(size_t)v * NU + j];
+        usrc = A.u_hold + (size_t)v * NU;
         const int s0 = g[0].status;
         status = s0 != BROV_STATUS_SUCCESS ? s0 : BROV_STATUS_NAN;
     }
-    const ModelPar m = make_par(A.pp + (size_t)v * A.pp_stride);
-    Wrench w = make_wrench(u);
-    const double dt = A.dt;
-    const int substeps = A.substeps;
-    const double h = dt / substeps;
-    StagePoint sp;
-    for (int s = 0; s < substeps; s++) {
-        model_f(x, w, m, k, sp);
-#pragma unroll
-        for (int j = 0; j < NX; j++) { acc[j] = x[j] + (h / 6.0) * k[j]; xs[j] = x[j] + 0.5 * h * k[j]; }
-        model_f(xs, w, m, k, sp);
-#pragma unroll
-        for (int j = 0; j < NX; j++) { acc[j] += (h / 3.0) * k[j]; xs[j] = x[j] + 0.5 * h * k[j]; }
-        model_f(xs, w, m, k, sp);
-#pragma unroll
-        for (int j = 0; j < NX; j++) { acc[j] += (h / 3.0) * k[j]; xs[j] = x[j] + h * k[j]; }
-        model_f(xs, w, m, k, sp);
-#pragma unroll
-        for (int j = 0; j < NX; j++) x[j] = acc[j] + (h / 6.0) * k[j];
-    }
-#pragma unroll
-    for (int j = 0; j < NX; j++) A.xv[(size_t)v * NX + j] = x[j];
-#pragma unroll
-    for (int j = 0; j < NU; j++) A.u_hold[(size_t)v * NU + j] = u[j];
+    double x[NX], u[NU];
+    ModelPar m;
+    Wrench w;
+    plant_inputs(A.xv + (size_t)v * NX, usrc, A.pp + (size_t)v * A.pp_stride, nullptr, 0, x, u, m, w);
+    plant_erk4(x, w, m, NoWorldWrench{}, A.dt, A.substeps);
+    store_row(A.xv + (size_t)v * NX, x);
+    store_row(A.u_hold + (size_t)v * NU, u);
     A.status[v] = status;
-    if (A.xlog) {
-#pragma unroll
-        for (int j = 0; j < NX; j++) A.xlog[(size_t)v * NX + j] = x[j];
-    }
-    if (A.ulog) {
-#pragma unroll
-        for (int j = 0; j < NU; j++) A.ulog[(size_t)v * NU + j] = u[j];
-    }
+    log_row(A.xlog, v, x);
+    log_row(A.ulog, v, u);
     if (A.stlog) A.stlog[v] = status;
     if (A.winlog) A.winlog[v] = win;
 }

@@ -1,5 +1,5 @@
 // lin_device.hpp -- building blocks of the wave-wide linearisation (qp_kernel.hip: lin_phase, used by rti_fused_kernel and
-// by the streaming path's lin_wave_kernel): ERK4 of the state (gen/acados_solver_bluerov2.c:633-641: 4 stages, 1 step),
+// by the streaming path's lin_wave_kernel): ERK4 of the state (1 step of erk4_step, bluerov2_model.hpp, the stage points kept),
 // sensitivity columns S[:,c] of S = d x+ / d [x;u] through stage records kept in LDS, NLP KKT rows.
 #pragma once
 #include "bluerov2_model.hpp"
@@ -21,24 +21,14 @@ struct KktAcc {
     __device__ __forceinline__ void upd(double v) { mx = fmax(mx, fabs(v)); nan = nan || (v != v); }
 };
 
-// Stage points of the 4 RK stages + x+
+// Stage points of the 4 RK stages + x+: one step of the device's one ERK4 (bluerov2_model.hpp, erk4_step -- the step every plant takes),
+// without a world wrench, with the stage points kept for the sensitivities below
 __device__ __forceinline__ void rk4_state(const double* __restrict__ xi, const Wrench& w, const ModelPar& m, double h,
                                           StagePoint (&sp)[4], double (&xn)[NX]) {
-    double x[NX], k[NX], xs[NX];
+    double x[NX];
 #pragma unroll
     for (int j = 0; j < NX; j++) x[j] = xi[j];
-    model_f(x, w, m, k, sp[0]);
-#pragma unroll
-    for (int j = 0; j < NX; j++) { xn[j] = x[j] + (h / 6.0) * k[j]; xs[j] = x[j] + 0.5 * h * k[j]; }
-    model_f(xs, w, m, k, sp[1]);
-#pragma unroll
-    for (int j = 0; j < NX; j++) { xn[j] += (h / 3.0) * k[j]; xs[j] = x[j] + 0.5 * h * k[j]; }
-    model_f(xs, w, m, k, sp[2]);
-#pragma unroll
-    for (int j = 0; j < NX; j++) { xn[j] += (h / 3.0) * k[j]; xs[j] = x[j] + h * k[j]; }
-    model_f(xs, w, m, k, sp[3]);
-#pragma unroll
-    for (int j = 0; j < NX; j++) xn[j] += (h / 6.0) * k[j];
+    erk4_step(x, w, m, NoWorldWrench{}, h, sp, xn);
 }
 
 // ---- stage records in LDS ---------------------------------------------------------------------------------------------

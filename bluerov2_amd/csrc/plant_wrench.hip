@@ -1,6 +1,6 @@
 // plant_wrench.hip -- the device plant under a time-varying WORLD-frame wrench: the disturbance scenarios of the reference's
 // applyBodyWrench() (bluerov2_dobmpc/src/bluerov2_dob.cpp:754-892; bluerov2_ampc.cpp:1050-1150 is the same code with a
-// slower phase rate), which the constant body-frame parameters p[0..3] of plant_kernel (traj_kernel.hip) cannot pose:
+// slower phase rate), which the constant body-frame parameters p[0..3] of the plant cannot pose:
 //   constant   (10, 10, 10, 0) N / Nm in the world frame (:813-816)
 //   periodic   sin(t) times amplitudes redrawn every half period (:776-795), the yaw torque from the Y amplitude (:787)
 //   table      recorded force / torque rows, one per tick (:869-873)
@@ -8,9 +8,10 @@
 // evaluated again (brov_plant_wrench_eval_host).  The arithmetic of the generator is written with explicitly rounded operations under
 // `fp contract(off)` (hipcc otherwise contracts a product and a sum into an FMA, also across inlined calls): the evaluation kernel, the plant kernel and the numpy restatement of tests/wrench_restatement.py then agree bit for bit
 // except through sin().
-// plant_wrench_kernel: one lane per instance, FP64, no scratch; the ERK4 of plant_kernel with the world wrench projected into the body
-// frame at EVERY stage with that stage's attitude (bluerov2_model.hpp, the model_f overload).  ~660 FP64 ops, 240 B + 48 B in, 96 B (+ logs)
-// out per instance.
+// plant_kernel / plant_wrench_kernel: the plant update of the closed loops without / with such a wrench: one lane per instance, FP64, no
+// scratch.  plant_kernel is the device's one plant step (bluerov2_model.hpp: plant_inputs, plant_erk4, store_row / log_row);
+// plant_wrench_kernel restates it (see there) with the wrench projected into the body frame at EVERY stage with that stage's attitude
+// (model_f<WorldWrench>).  ~600 / ~660 FP64 ops, 240 B (+ 48 B) in, 96 B (+ logs) out per instance.
 #include <hip/hip_runtime.h>
 
 #include "nmpc_device.hpp"
@@ -69,6 +70,30 @@ __global__ __launch_bounds__(128) void wrench_eval_kernel(WrenchGen g, int B, lo
     for (int c = 0; c < 6; c++) out[(size_t)b * 6 + c] = w[c];
 }
 
+// x0 <- ERK4(x0, u0, p_plant, dt): the step immediately AFTER the hot path, the plant update of closed-loop Monte-Carlo
+// roll-outs.  The same 12-state model the OCP uses (bluerov2.py:103-137) integrated over one control period with the first optimal input
+// of the last solve, per-instance TRUE parameters (disturbance draw, model mismatch).  ~600 FP64 ops, 240 B in / 96 B out.
+// Gather inputs -> plant_erk4 -> store, all three from bluerov2_model.hpp.
+__global__ __launch_bounds__(128) void plant_kernel(double* __restrict__ x0, const brov_result* __restrict__ res, const double* __restrict__ pplant,
+                             const double* __restrict__ prp, int rp_stride, int B, double dt, int substeps, double* __restrict__ xlog,
+                             double* __restrict__ ulog) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double x[NX], u[NU];
+    ModelPar m;
+    Wrench w;
+    plant_inputs(x0 + (size_t)b * NX, res[b].u0, pplant + (size_t)b * NP, prp, (size_t)b * rp_stride, x, u, m, w);
+    plant_erk4(x, w, m, NoWorldWrench{}, dt, substeps);
+    store_row(x0 + (size_t)b * NX, x);
+    log_row(xlog, b, x);
+    log_row(ulog, b, u);
+}
+
+// The same step under the wrench of generator g at `tick`, held over the tick like the reference's service call.  Its statements are those of
+// plant_inputs / erk4_step / store_row written out, NOT calls of them: every form of this kernel that called them, or shared a templated
+// body with plant_kernel, compiled to other code, and the one that was measured ran 2 ... 3 % slower per launch at B = 16384
+// (profiles/plant_step_refactor_isa.txt, sections 3 and 6).  As it stands it is instruction for instruction the parent's kernel.  A change
+// to the step is made in erk4_step (bluerov2_model.hpp), here, and in plant_step_wave (qp/fused.hpp).
 __global__ __launch_bounds__(128) void plant_wrench_kernel(double* __restrict__ x0, const brov_result* __restrict__ res,
                                                            const double* __restrict__ pplant, const double* __restrict__ prp, int rp_stride, int B,
                                                            double dt, int substeps, double* __restrict__ xlog, double* __restrict__ ulog,
@@ -125,6 +150,10 @@ __global__ void gather_cols_kernel(const double* __restrict__ src, int B, int sr
     dst[t] = src[(size_t)b * src_stride + col0 + c];
 }
 
+void launch_plant(double* x0, const brov_result* res, const double* pplant, const double* prp, int rp_stride, int B, double dt, int substeps,
+                  double* xlog, double* ulog, hipStream_t st) {
+    hipLaunchKernelGGL(plant_kernel, dim3((B + 127) / 128), dim3(128), 0, st, x0, res, pplant, prp, rp_stride, B, dt, substeps, xlog, ulog);
+}
 void launch_plant_wrench(double* x0, const brov_result* res, const double* pplant, const double* prp, int rp_stride, int B, double dt, int substeps,
                          double* xlog, double* ulog, const WrenchGen& g, long long tick, double* wlog, hipStream_t st) {
     hipLaunchKernelGGL(plant_wrench_kernel, dim3((B + 127) / 128), dim3(128), 0, st, x0, res, pplant, prp, rp_stride, B, dt, substeps, xlog, ulog,

@@ -81,8 +81,12 @@ __device__ __forceinline__ bool rti_fused_step(const DevParams& P, int b, int la
     qp_body<W, std::conditional_t<GRID, InstGrid, Inst>, DF>(P, I, b, part, nanp);
     return I.ran_loop;
 }
-// the plant update of brov_closed_loop inside the step loop (traj_kernel.hip, plant_kernel: the same arithmetic, one lane per instance there;
-// here every lane of the instance's wave computes it -- a wave's issue slots cost the same for one lane as for sixty-four -- and lane 0 stores)
+// the plant update of brov_closed_loop inside the step loop: the arithmetic of plant_kernel (plant_wrench.hip; one lane per instance there;
+// here every lane of the instance's wave computes it -- a wave's issue slots cost the same for one lane as for sixty-four -- and lane 0
+// stores).  The one plant that does NOT call plant_inputs / plant_erk4 (bluerov2_model.hpp) but restates their statements in their order:
+// called through them, the four *_ticks kernels around it -- at their register limit -- allocate their registers differently
+// (profiles/plant_step_refactor_isa.txt, section 4), and a solver kernel that differs from its parent is not shipped for a clean-up.
+// tests/test_gpu_ticks.py holds this copy to plant_kernel bit for bit.
 __device__ __forceinline__ void plant_step_wave(const DevParams& P, int b, int lane, int tk) {
     double x[NX], u[NU], k[NX], xs[NX], acc[NX];
     double* x0 = P.x0_rw + (size_t)b * NX;
@@ -96,16 +100,16 @@ __device__ __forceinline__ void plant_step_wave(const DevParams& P, int b, int l
     const double h = P.plant_dt / P.plant_substeps;
     StagePoint sp;
     for (int s = 0; s < P.plant_substeps; s++) {
-        model_f(x, w, m, k, sp);
+        model_f(x, w, m, NoWorldWrench{}, k, sp);
 #pragma unroll
         for (int j = 0; j < NX; j++) { acc[j] = x[j] + (h / 6.0) * k[j]; xs[j] = x[j] + 0.5 * h * k[j]; }
-        model_f(xs, w, m, k, sp);
+        model_f(xs, w, m, NoWorldWrench{}, k, sp);
 #pragma unroll
         for (int j = 0; j < NX; j++) { acc[j] += (h / 3.0) * k[j]; xs[j] = x[j] + 0.5 * h * k[j]; }
-        model_f(xs, w, m, k, sp);
+        model_f(xs, w, m, NoWorldWrench{}, k, sp);
 #pragma unroll
         for (int j = 0; j < NX; j++) { acc[j] += (h / 3.0) * k[j]; xs[j] = x[j] + h * k[j]; }
-        model_f(xs, w, m, k, sp);
+        model_f(xs, w, m, NoWorldWrench{}, k, sp);
 #pragma unroll
         for (int j = 0; j < NX; j++) x[j] = acc[j] + (h / 6.0) * k[j];
     }

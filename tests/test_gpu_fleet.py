@@ -134,6 +134,51 @@ def test_one_candidate_per_vehicle_is_the_existing_loop(ba):
     f.close(); a.close(); b.close()
 
 
+def test_three_loops_step_one_plant(ba):
+    """The same closed loop three ways from the same start: brov_closed_loop in one launch (the plant inside the *_ticks kernel),
+    brov_closed_loop as three launches per tick (plant_kernel) and the fleet loop with one candidate per vehicle (fleet_plant_kernel).  The
+    first two log the same bytes.  The fleet's plant is the same plant_inputs / plant_erk4 call as plant_kernel's, compiled into another
+    kernel; on the MI355X it logs the same bytes as well (profiles/plant_step_refactor_isa.txt, section 5), and that is asserted.
+        Ts = 1/16, a power of two: the node times (k + i) Ts of the table rows and k Ts + i Ts of the
+    fleet's windows are then the same doubles, and the table is cut from the device's own generator."""
+    import os
+    B, ticks, Ts = 8, 3, 0.0625
+    rng = np.random.default_rng(21)
+    amp, frq, ph = np.full(B, 2.0), np.full(B, 0.5), np.full(B, 0.4)          # one shape: the table of brov_closed_loop is shared
+    x0 = np.zeros((B, 12)); x0[:, 0] = 2.0 * np.cos(0.4); x0[:, 1] = 2.0 * np.sin(0.4) * np.cos(0.4); x0[:, 2] = -20.0
+    x0 += rng.normal(size=(B, 12)) * 0.02
+    pp = np.tile(ba.P_NOMINAL, (B, 1)); pp[:, :4] = rng.uniform(-5, 5, (B, 4)); pp[:, 4:] *= rng.uniform(0.9, 1.1, (B, 12))
+    logs = []
+    for fused in ("1", "0"):
+        os.environ["BROV_CLOSED_LOOP_FUSED"] = fused
+        try:
+            s = ba.BatchSolver(B, ba.SolverOptions(N, Ts))
+        finally:
+            os.environ.pop("BROV_CLOSED_LOOP_FUSED", None)
+        s.set_params(ba.P_NOMINAL); s.set_plant_params(pp)
+        s.set_yref_candidates("lemniscate", amp, frq, ph, t0=0.0, dt=Ts); head = s.get_yref()[0]
+        s.set_yref_candidates("lemniscate", amp, frq, ph, t0=ticks * Ts, dt=Ts); tail = s.get_yref()[0]
+        assert np.array_equal(head[ticks:], tail[:N + 1 - ticks])             # the rows are functions of the node time alone
+        s.set_trajectory(np.vstack([head, tail[N + 1 - ticks:]]))
+        s.set_x0(x0)
+        logs.append(s.closed_loop(ticks, line0=0, ncols=16, dt=0.05, substeps=2))
+        s.close()
+    (u1, x1, s1), (u0, x0l, s0) = logs
+    assert not s1.any() and np.array_equal(s1, s0)
+    assert u1.tobytes() == u0.tobytes() and x1.tobytes() == x0l.tobytes()
+    a = ba.BatchSolver(B, ba.SolverOptions(N, Ts))
+    a.set_params(ba.P_NOMINAL); a.set_x0(x0); a.set_candidate_params("lemniscate", amp, frq, ph)
+    f = ba.Fleet(a, 1)
+    f.set_plant_params(pp)
+    uf, xf, sf, wf = f.closed_loop(ticks, t0=0.0, dt_ref=Ts, dt_node=Ts, dt=0.05, substeps=2)
+    f.close(); a.close()
+    assert not sf.any() and not wf.any()
+    err = np.abs(xf - x1).max()
+    print(f"[three loops] fleet against brov_closed_loop: u bit-identical: {uf.tobytes() == u1.tobytes()}, max |dx| = {err:.3e}, "
+          f"x bit-identical: {xf.tobytes() == x1.tobytes()}")
+    assert uf.tobytes() == u1.tobytes() and xf.tobytes() == x1.tobytes()
+
+
 @pytest.mark.parametrize("V,C", [(5, 3), (2, 65)])
 def test_closed_loop_against_a_loop_composed_on_the_host(ba, V, C):
     B, ticks = V * C, 4

@@ -47,8 +47,8 @@ def test_python_mirror_names_the_modes():
 
 
 def test_plant_wrench_kernel_uses_no_scratch():
-    """the backend's own resource report of plant_wrench.hip (device-only compile): both kernels without scratch; the plant kernel at no
-    more than 256 registers (measured: 204), so that two waves per SIMD stay resident as the backend reports today"""
+    """the backend's own resource report of plant_wrench.hip (device-only compile): its kernels, plant_kernel among them, without scratch;
+    the plant kernels at no more than 256 registers (measured: 204), so that two waves per SIMD stay resident as the backend reports today"""
     out = subprocess.run(["bash", os.path.join(ROOT, "scripts", "dev", "kernel_resources.sh"), "plant_wrench.hip"], capture_output=True,
                          text=True, timeout=600).stdout
     rep = {}
@@ -56,7 +56,7 @@ def test_plant_wrench_kernel_uses_no_scratch():
         m = re.match(r"Name: (\S+)", ln)
         if m:
             rep[m.group(1)] = {k: int(v) for k, v in re.findall(r"\|([A-Za-z ]+): (\d+)", ln)}
-    for short in ("plant_wrench_kernel", "wrench_eval_kernel"):
+    for short in ("plant_kernel", "plant_wrench_kernel", "wrench_eval_kernel"):
         hit = [r for m, r in rep.items() if re.search(r"\d+%sE" % short, m)]
         assert len(hit) == 1, (short, sorted(rep))
         assert hit[0]["scratch"] == 0, (short, hit[0])
