@@ -3,6 +3,10 @@
 //   fleet_select_kernel   per vehicle the cheapest eligible candidate (segmented arg-min over the 104-byte result records)
 //   fleet_plant_kernel    the vehicle's plant stepped with the winner's u0 -- or, without a winner, with the input applied last
 //   fleet_bcast_kernel    the measured state of every vehicle into x0 of all its candidates
+// Under disturbance (brov_vehicle_*):
+//   fleet_plant_wrench_kernel    fleet_plant_kernel under a world-frame wrench per vehicle, evaluated for the tick by wrench_eval_kernel
+//   fleet_observe_inputs_kernel  what the disturbance observer is fed per vehicle: measured state, thrust allocation of the input given, acceleration
+//   fleet_apply_kernel           the observer's estimate of vehicle v into p[0..3] of every stage of all its candidates
 //
 // fleet_select_kernel: one wavefront per vehicle, four vehicles per block.  Lane l scans candidates l, l + 64, ... in ascending order, the
 // wave folds (cost, index) pairs with shuffles; at every level the lower cost wins and on equal cost the lower index.  That is a total
@@ -10,8 +14,8 @@
 // `cost` and `status` of a record are read (16 of its 104 bytes), then the winner's record once.  Eligible: status SUCCESS and a finite cost,
 // tested on the exponent bits as track_accumulate_kernel does (an ordering comparison is false for NaN on either side).
 //
-// fleet_plant_kernel: one lane per vehicle; where its input comes from and what it records is its own, the step between is plant_erk4
-// (bluerov2_model.hpp), the function plant_kernel calls.
+// fleet_plant_kernel / fleet_plant_wrench_kernel: one lane per vehicle; where its input comes from and what it records is its own
+// (fleet_plant_vehicle), the step between is plant_erk4 (bluerov2_model.hpp), the function plant_kernel calls, without / with a WorldWrench.
 #include <hip/hip_runtime.h>
 
 #include "fleet_kernel.hpp"
@@ -61,9 +65,10 @@ __global__ __launch_bounds__(kFleetSelectBlock) void fleet_select_kernel(const b
     }
 }
 
-__global__ __launch_bounds__(128) void fleet_plant_kernel(FleetPlantArgs A) {
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v >= A.V) return;
+// the plant step of vehicle v: the input from the winner or the zero-order hold, the status rule, plant_erk4 under `ww`, state / held input /
+// status and the log rows of this tick
+template <class WW>
+__device__ __forceinline__ void fleet_plant_vehicle(const FleetPlantArgs& A, int v, const WW& ww) {
     const int win = A.winner[v];
     const brov_result* __restrict__ g = A.res + (size_t)v * A.C;
     const double* usrc;
@@ -81,7 +86,7 @@ __global__ __launch_bounds__(128) void fleet_plant_kernel(FleetPlantArgs A) {
     ModelPar m;
     Wrench w;
     plant_inputs(A.xv + (size_t)v * NX, usrc, A.pp + (size_t)v * A.pp_stride, nullptr, 0, x, u, m, w);
-    plant_erk4(x, w, m, NoWorldWrench{}, A.dt, A.substeps);
+    plant_erk4(x, w, m, ww, A.dt, A.substeps);
     store_row(A.xv + (size_t)v * NX, x);
     store_row(A.u_hold + (size_t)v * NU, u);
     A.status[v] = status;
@@ -89,6 +94,22 @@ __global__ __launch_bounds__(128) void fleet_plant_kernel(FleetPlantArgs A) {
     log_row(A.ulog, v, u);
     if (A.stlog) A.stlog[v] = status;
     if (A.winlog) A.winlog[v] = win;
+}
+
+__global__ __launch_bounds__(128) void fleet_plant_kernel(FleetPlantArgs A) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= A.V) return;
+    fleet_plant_vehicle(A, v, NoWorldWrench{});
+}
+
+// the same step under the world-frame wrench wv[v][0..5] of this tick (wrench_eval_kernel wrote it: a fleet buffer or the tick's row of the
+// wrench log), held over the tick and projected into the body frame at every RK stage (model_f<WorldWrench>)
+__global__ __launch_bounds__(128) void fleet_plant_wrench_kernel(FleetPlantArgs A, const double* __restrict__ wv) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= A.V) return;
+    const double* __restrict__ w6 = wv + (size_t)v * 6;
+    const WorldWrench ww = {w6[0], w6[1], w6[2], w6[3], w6[4], w6[5]};
+    fleet_plant_vehicle(A, v, ww);
 }
 
 // one thread per double of x0: consecutive threads write consecutive doubles, the C * 12 readers of a vehicle share its 96 bytes
@@ -100,12 +121,61 @@ __global__ __launch_bounds__(256) void fleet_bcast_kernel(const double* __restri
     x0[t] = xv[(b / C) * NX + j];
 }
 
+// measurement assembly for the observer, one lane per vehicle: y12 = the measured state, thrust = the reference's allocation of the input the
+// vehicle was given (the expressions of ekf_inputs_from_solver_kernel, in its order), acc = (v - v_prev) / dt with v_prev kept here
+__global__ __launch_bounds__(128) void fleet_observe_inputs_kernel(int V, double dt, double inv_rc, const double* __restrict__ xv,
+                                                                   const double* __restrict__ u_hold, double* __restrict__ vprev,
+                                                                   double* __restrict__ thrust, double* __restrict__ y12, double* __restrict__ acc) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= V) return;
+    const double* xs = xv + (size_t)v * NX;
+#pragma unroll
+    for (int j = 0; j < NX; j++) y12[(size_t)v * NX + j] = xs[j];
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+        const double vel = xs[6 + j];
+        acc[(size_t)v * 6 + j] = (vel - vprev[(size_t)v * 6 + j]) / dt;
+        vprev[(size_t)v * 6 + j] = vel;
+    }
+    const double* uh = u_hold + (size_t)v * NU;
+    const double u0 = uh[0], u1 = uh[1], u2 = uh[2], u3 = uh[3];
+    double* t = thrust + (size_t)v * 6;
+    t[0] = (-u0 + u1 + u3) * inv_rc;
+    t[1] = (-u0 - u1 - u3) * inv_rc;
+    t[2] = (u0 + u1 - u3) * inv_rc;
+    t[3] = (u0 - u1 + u3) * inv_rc;
+    t[4] = (-u2) * inv_rc;
+    t[5] = (-u2) * inv_rc;
+}
+
+// one thread per (instance, stage): p[0..3] := the estimate of the instance's vehicle; p[4..15] are left alone
+__global__ __launch_bounds__(256) void fleet_apply_kernel(int B, int C, int stages, const double* __restrict__ mp, double* __restrict__ par) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;   // (B * stages fits an int, as in ekf_apply_kernel: par holds 128 bytes per k)
+    if (k >= B * stages) return;
+    const int v = k / stages / C;
+    double* p = par + (size_t)k * NP;
+#pragma unroll
+    for (int j = 0; j < 4; j++) p[j] = mp[(size_t)v * 4 + j];
+}
+
 void launch_fleet_select(const brov_result* rec, int V, int C, int32_t* winner, brov_result* winner_rec, hipStream_t st) {
     hipLaunchKernelGGL(fleet_select_kernel, dim3((unsigned)((V + kFleetSelectWaves - 1) / kFleetSelectWaves)), dim3(kFleetSelectBlock), 0, st, rec, V,
                        C, winner, winner_rec);
 }
 void launch_fleet_plant(const FleetPlantArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(fleet_plant_kernel, dim3((unsigned)((a.V + 127) / 128)), dim3(128), 0, st, a);
+}
+void launch_fleet_plant_wrench(const FleetPlantArgs& a, const double* wv, hipStream_t st) {
+    hipLaunchKernelGGL(fleet_plant_wrench_kernel, dim3((unsigned)((a.V + 127) / 128)), dim3(128), 0, st, a, wv);
+}
+void launch_fleet_observe_inputs(int V, double dt, const double* xv, const double* u_hold, double* vprev, double* thrust, double* y12, double* acc,
+                                 hipStream_t st) {
+    hipLaunchKernelGGL(fleet_observe_inputs_kernel, dim3((unsigned)((V + 127) / 128)), dim3(128), 0, st, V, dt, 1.0 / kRotor, xv, u_hold, vprev,
+                       thrust, y12, acc);
+}
+void launch_fleet_apply(int V, int C, int stages, const double* mp, double* par, hipStream_t st) {
+    const int B = V * C;
+    hipLaunchKernelGGL(fleet_apply_kernel, dim3((unsigned)((B * stages + 255) / 256)), dim3(256), 0, st, B, C, stages, mp, par);
 }
 void launch_fleet_bcast(const double* xv, int V, int C, double* x0, hipStream_t st) {
     const long long total = (long long)V * C * NX;

@@ -28,6 +28,17 @@ struct FleetPlantArgs {
 };
 void launch_fleet_plant(const FleetPlantArgs& a, hipStream_t st);
 
+// the same step under the world-frame wrench wv[v][0..5] (DEVICE [V][6]), held over the tick
+void launch_fleet_plant_wrench(const FleetPlantArgs& a, const double* wv, hipStream_t st);
+
+// what the disturbance observer is fed per vehicle: y12[v] = xv[v], thrust[v] = allocation of u_hold[v] / kRotor, acc[v] = (v - vprev[v]) / dt;
+// vprev[v] := the velocities of xv[v]
+void launch_fleet_observe_inputs(int V, double dt, const double* xv, const double* u_hold, double* vprev, double* thrust, double* y12, double* acc,
+                                 hipStream_t st);
+
+// par[v * C + c][stage][0..3] = mp[v][0..3] for every candidate c and every stage; [4..15] untouched
+void launch_fleet_apply(int V, int C, int stages, const double* mp, double* par, hipStream_t st);
+
 // x0[v * C + c][:] = xv[v][:] for every candidate c
 void launch_fleet_bcast(const double* xv, int V, int C, double* x0, hipStream_t st);
 

@@ -1,10 +1,11 @@
-"""Host-side mirror of the fleet planning loop (include/bluerov2_nmpc.h, brov_fleet_*): V vehicles x C candidates laid over one
-BatchSolver of batch V * C, instance v * C + c = candidate c of vehicle v.  ctypes over the HIP library -- no CPU path."""
+"""Host-side mirror of the fleet planning loop (include/bluerov2_nmpc.h, brov_fleet_*, brov_vehicle_*): V vehicles x C candidates laid over
+one BatchSolver of batch V * C, instance v * C + c = candidate c of vehicle v; a world-frame wrench per vehicle and a BatchEkf of batch V
+closing the loop.  ctypes over the HIP library -- no CPU path."""
 import ctypes as C
 
 import numpy as np
 
-from .solver import RESULT_DTYPE, _Handle, _arr, _bind, _dp, _load
+from .solver import RESULT_DTYPE, _Handle, _arr, _arr_opt, _bind, _dp, _load
 
 
 def _protos(L):
@@ -19,7 +20,13 @@ def _protos(L):
         "brov_fleet_step": [vp, vp, C.c_double, C.c_int, vp], "brov_fleet_get_last_host": [vp, dp, ip, ip],
         "brov_closed_loop_fleet": [vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, dp, dp, ip, ip],
         "brov_fleet_last_seconds": [vp, dp],
+        "brov_vehicle_wrench_constant_host": [vp, dp], "brov_vehicle_wrench_periodic": [vp, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_double],
+        "brov_vehicle_wrench_table_host": [vp, dp, C.c_int, dp], "brov_vehicle_wrench_off": [vp], "brov_vehicle_wrench_mode": [vp],
+        "brov_vehicle_wrench_seek": [vp, C.c_int64], "brov_vehicle_wrench_eval_host": [vp, C.c_int64, dp],
+        "brov_vehicle_observe": [vp, vp, C.c_double, vp], "brov_vehicle_apply_estimate": [vp, vp, vp],
+        "brov_closed_loop_fleet_dob": [vp, vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, dp, dp, ip, ip, dp, dp],
     })
+    _bind(L, {"brov_vehicle_wrench_tick": [vp]}, C.c_int64)
 
 
 def _fleet_lib():
@@ -98,6 +105,77 @@ class Fleet(_Handle):
         self._chk(self._L.brov_closed_loop_fleet(self._h, ticks, float(t0), float(dt_ref), float(dt_node), float(dt), int(substeps), _dp(u), _dp(x),
                                                  _ip(st), _ip(win)), "closed_loop")
         return (u, x, st, win) if log else None
+
+    # ---- the fleet under disturbance (brov_vehicle_*) -------------------------------------------------------------------------------
+    def set_wrench(self, constant=None, periodic=None, table=None, gain=None):
+        """the vehicles' world-frame wrench, BatchSolver.set_plant_wrench at batch V: exactly one of
+            constant=w         [6] or [V, 6], world frame [fx fy fz tx ty tz]
+            periodic=dict(seed=0, scale=6.0, phase0=0.0, dphi=0.125, tz_div=3.0)   (any subset)
+            table=tab          [rows, 6], row min(tick, rows - 1); gain=[V] scales it per vehicle"""
+        if (constant is not None) + (periodic is not None) + (table is not None) != 1:
+            raise ValueError("set_wrench takes exactly one of constant=, periodic=, table=")
+        if gain is not None and table is None:
+            raise ValueError("gain= goes with table=")
+        if constant is not None:
+            w = np.ascontiguousarray(constant, dtype=np.float64)
+            if w.shape == (6,):
+                w = np.ascontiguousarray(np.broadcast_to(w, (self.V, 6)))
+            self._chk(self._L.brov_vehicle_wrench_constant_host(self._h, _dp(_arr(w, (self.V, 6)))), "wrench_constant")
+        elif periodic is not None:
+            kw = dict(seed=0, scale=6.0, phase0=0.0, dphi=0.125, tz_div=3.0)
+            unknown = set(periodic) - set(kw)
+            if unknown:
+                raise ValueError(f"unknown periodic wrench parameters {sorted(unknown)}")
+            kw.update(periodic)
+            self._chk(self._L.brov_vehicle_wrench_periodic(self._h, int(kw["seed"]) & 0xFFFFFFFFFFFFFFFF, float(kw["scale"]), float(kw["phase0"]),
+                                                           float(kw["dphi"]), float(kw["tz_div"])), "wrench_periodic")
+        else:
+            tab = np.ascontiguousarray(table, dtype=np.float64)
+            if tab.ndim != 2 or tab.shape[1] != 6 or tab.shape[0] < 1:
+                raise ValueError("wrench table must be [rows][6]")
+            self._chk(self._L.brov_vehicle_wrench_table_host(self._h, _dp(tab), tab.shape[0], _dp(_arr_opt(gain, (self.V,)))), "wrench_table")
+
+    def wrench_off(self):
+        self._chk(self._L.brov_vehicle_wrench_off(self._h), "wrench_off")
+
+    def wrench_mode(self):
+        return int(self._L.brov_vehicle_wrench_mode(self._h))
+
+    def wrench(self, tick):
+        """[V, 6]: the wrench of every vehicle at `tick`, evaluated by the device generator (moves nothing; zeros while off)"""
+        w = np.empty((self.V, 6))
+        self._chk(self._L.brov_vehicle_wrench_eval_host(self._h, int(tick), _dp(w)), "wrench_eval")
+        return w
+
+    def wrench_seek(self, tick):
+        self._chk(self._L.brov_vehicle_wrench_seek(self._h, int(tick)), "wrench_seek")
+
+    def wrench_tick(self):
+        """the tick counter: fleet steps since the last reset or seek (step and every closed-loop tick add one)"""
+        return int(self._L.brov_vehicle_wrench_tick(self._h))
+
+    def observe(self, ekf, dt=0.05, stream=0):
+        """one tick of the observer `ekf` (BatchEkf of batch V) on the vehicles' states, the inputs they were given and (v - v_prev) / dt"""
+        self._chk(self._L.brov_vehicle_observe(self._h, ekf._h, float(dt), C.c_void_p(stream)), "observe")
+
+    def apply_estimate(self, ekf, stream=0):
+        """p[0..3] of every stage of every candidate of vehicle v := the estimate of vehicle v; needs set_plant_params"""
+        self._chk(self._L.brov_vehicle_apply_estimate(self._h, ekf._h, C.c_void_p(stream)), "apply_estimate")
+
+    def closed_loop_dob(self, ekf, ticks, t0=0.0, dt_ref=0.05, dt_node=0.05, dt=0.05, substeps=1, log=True):
+        """closed_loop() under the fleet's wrench with observe + apply_estimate behind every step (ekf=None: neither), one host wait.  With
+        log: dict(u [ticks, V, 4], x [ticks + 1, V, 12], status [ticks, V], winner [ticks, V], wrench [ticks, V, 6], est [ticks, V, 6] or
+        None without an observer)"""
+        ticks = int(ticks)
+        u = x = st = win = w = est = None
+        if log:
+            n = max(ticks, 0)
+            u = np.empty((n, self.V, 4)); x = np.empty((n + 1, self.V, 12))
+            st = np.empty((n, self.V), dtype=np.int32); win = np.empty((n, self.V), dtype=np.int32)
+            w = np.empty((n, self.V, 6)); est = np.empty((n, self.V, 6)) if ekf is not None else None
+        self._chk(self._L.brov_closed_loop_fleet_dob(self._h, None if ekf is None else ekf._h, ticks, float(t0), float(dt_ref), float(dt_node),
+                                                     float(dt), int(substeps), _dp(u), _dp(x), _ip(st), _ip(win), _dp(w), _dp(est)), "closed_loop_dob")
+        return dict(u=u, x=x, status=st, winner=win, wrench=w, est=est) if log else None
 
     def last_seconds(self):
         """seconds of the last select kernel"""

@@ -626,16 +626,21 @@ int brov_closed_loop_track(brov_solver* s, brov_ekf* e /*NULL: no observer*/, br
  * (brov_set_yref_candidates), all B candidates are solved in one launch (brov_solve), and brov_fleet_step
  *   selects  per vehicle the eligible candidate of the lowest cost, the lowest index on equal cost; eligible = status SUCCESS and a finite
  *            cost (NaN and +-Inf never win); winner = its index c within the group, -1 when the group has no eligible candidate
- *   steps    the vehicle's plant -- the ERK4 of brov_plant_step -- with the winner's u0 and the vehicle's true parameters.  Without a winner
+ *   steps    the vehicle's plant -- the ERK4 of brov_plant_step -- with the winner's u0 and the vehicle's true parameters, under the
+ *            vehicle's world-frame wrench of this tick when a mode of brov_vehicle_wrench_* is in force.  Without a winner
  *            the vehicle is stepped with the input it was given last (zeros after brov_fleet_reset): the zero-order hold brov_opts::on_failure
  *            documents for one instance.  Logged status: 0 with a winner; without one the status of candidate 0 of the group if that is
  *            non-zero, else BROV_STATUS_NAN (candidate 0 reported success with a cost that is not finite)
  *   measures the new xv[v] becomes x0 of every candidate of vehicle v
+ * With a disturbance observer of batch V the tick goes on: brov_vehicle_observe feeds it the vehicles' measurements, and
+ * brov_vehicle_apply_estimate hands its estimate to all candidates of each vehicle; brov_closed_loop_fleet_dob is the whole loop.
  * The candidates' iterates are left alone: each candidate warm-starts from its own last step (the iterate is not shifted).  The fleet does
- * not own the solver, which must outlive it; the solver's x0 is the fleet's to write once a step has run.  The plant of the fleet knows
- * neither a world-frame wrench (brov_plant_wrench_*) nor the 6-disturbance variant: brov_fleet_step and brov_closed_loop_fleet fail with
- * BROV_ERR_ARG while either is in force, and brov_closed_loop_fleet also when no candidate parameters were uploaded
- * (brov_set_candidate_params_host).  Every enqueueing call is ordered behind the solver's last stream (brov_order_stream).
+ * not own the solver, which must outlive it; the solver's x0 is the fleet's to write once a step has run.
+ * Disturbance is a property of the VEHICLE, so it is the fleet's: the solver's own wrench (brov_plant_wrench_*) is indexed by the instance
+ * v * C + c and means nothing here, and the 6-disturbance variant has no per-vehicle source.  brov_fleet_step and the fleet's loops fail with
+ * BROV_ERR_ARG while either is in force on the solver, and the loops also when no candidate parameters were uploaded
+ * (brov_set_candidate_params_host).  Every enqueueing call is ordered behind the solver's last stream (brov_order_stream) and behind the
+ * fleet's own last work.
  * ------------------------------------------------------------------------------------------------------------------- */
 typedef struct brov_fleet brov_fleet;
 const char* brov_fleet_last_error(void); /* message of the last failing brov_fleet_* / brov_closed_loop_fleet call on this thread */
@@ -643,7 +648,7 @@ int  brov_fleet_create(brov_fleet** out, brov_solver* s, int candidates);   /* B
 void brov_fleet_destroy(brov_fleet* f);                                      /* does not destroy the solver */
 int  brov_fleet_vehicles(const brov_fleet* f);
 int  brov_fleet_candidates(const brov_fleet* f);
-int  brov_fleet_reset(brov_fleet* f);                    /* u_hold = 0; xv := x0 of candidate 0 of every group; tick counter 0 (done by create) */
+int  brov_fleet_reset(brov_fleet* f);                    /* u_hold = 0; v_prev = 0; xv := x0 of candidate 0 of every group; tick counter 0 (done by create) */
 int  brov_fleet_set_state_host(brov_fleet* f, const double* xv /*[V][12]*/);   /* also broadcast into the solver's x0 */
 int  brov_fleet_get_state_host(brov_fleet* f, double* xv /*[V][12]*/);
 int  brov_fleet_set_plant_params_host(brov_fleet* f, const double* p /*[V][16]; NULL: stage-0 parameters of candidate 0 of each group, re-read at every step*/);
@@ -656,14 +661,51 @@ int  brov_fleet_select_host(brov_fleet* f, const brov_result* rec_host /*[B] or 
 int  brov_fleet_step(brov_fleet* f, const brov_result* rec, double dt, int substeps, void* stream);
 /* of the last step, HOST, any may be NULL: the input every vehicle was given u [V][4], its status [V] and its winner [V] */
 int  brov_fleet_get_last_host(brov_fleet* f, double* u, int32_t* status, int32_t* winner);
-/* `ticks` planning ticks, one host wait at the end.  Per tick k: brov_set_yref_candidates(s, t0 + k*dt_ref, dt_node) -> brov_solve(s) -> brov_fleet_step,
- * on the solver's last stream, from the solver's x0 as it stands (brov_fleet_reset / brov_fleet_set_state_host make it the fleet's xv).
+/* `ticks` planning ticks, one host wait at the end.  Per tick k: brov_set_yref_candidates(s, t0 + k*dt_ref, dt_node) -> brov_solve(s) -> brov_fleet_step
+ * (under the fleet's wrench mode), on the solver's last stream, from the solver's x0 as it stands (brov_fleet_reset / brov_fleet_set_state_host make it the fleet's xv).
  * HOST logs, any may be NULL: u_log [ticks][V][4], x_log [ticks+1][V][12], st_log [ticks][V], win_log [ticks][V] -- the layouts of
  * brov_track_accumulate_host at batch V.  Logs are delivered only when the whole loop succeeded (the contract of brov_closed_loop_ex). */
 int  brov_closed_loop_fleet(brov_fleet* f, int ticks, double t0, double dt_ref, double dt_node, double dt, int substeps,
                             double* u_log, double* x_log, int32_t* st_log, int32_t* win_log);
 /* seconds of the last select kernel (HIP events on its stream) */
 int  brov_fleet_last_seconds(brov_fleet* f, double* select_seconds);
+
+/* ---- the fleet under disturbance.  (These calls take a brov_fleet and act per vehicle; brov_fleet_last_error() has their texts.) -----------
+ * A world-frame wrench per vehicle: brov_plant_wrench_* at batch V, owned by the fleet.  The generator is the solver's, with the vehicle v as
+ * its instance index: vehicle v draws what instance v of a solver of batch V draws under the same settings.  The tick counter counts fleet
+ * steps: +1 in every brov_fleet_step and in every tick of the fleet's loops, whatever the mode; brov_fleet_reset sets it to 0,
+ * brov_vehicle_wrench_seek to `tick`.  Arguments are checked as the solver's are (tz_div != 0, rows >= 1, the periodic half-period index of
+ * every tick a call will touch below 2^22: a step or a loop that would leave that range is refused before anything runs).  The constant and
+ * table buffers are copies the fleet keeps until the next upload.  Mode OFF (the default): brov_fleet_step launches the plant kernel it
+ * always launched. */
+int brov_vehicle_wrench_constant_host(brov_fleet* f, const double* w /*[V][6]*/);
+int brov_vehicle_wrench_periodic(brov_fleet* f, uint64_t seed, double scale, double phase0, double dphi, double tz_div);
+int brov_vehicle_wrench_table_host(brov_fleet* f, const double* tab /*[rows][6]*/, int rows, const double* gain /*[V] or NULL*/);
+int brov_vehicle_wrench_off(brov_fleet* f);
+int brov_vehicle_wrench_mode(const brov_fleet* f);             /* BROV_WRENCH_*; OFF for NULL */
+int brov_vehicle_wrench_seek(brov_fleet* f, int64_t tick);     /* tick >= 0 */
+int64_t brov_vehicle_wrench_tick(const brov_fleet* f);
+/* the wrench of every vehicle at `tick`, HOST [V][6]; moves neither the counter nor a state; zeros while OFF */
+int brov_vehicle_wrench_eval_host(brov_fleet* f, int64_t tick, double* w /*[V][6]*/);
+/* The observer's tick behind a fleet step, brov_ekf_batch(e) == V: measurement = xv, thrusts = the reference's allocation of the input every
+ * vehicle was GIVEN in the last step (the winner's u0 or the held input) with the OCP model's rotor constant, acceleration = (v - v_prev) / dt
+ * with v_prev kept in the fleet (zeros after brov_fleet_reset); then brov_ekf_update_device on `stream`.  `dt` is the time between two
+ * measurements, i.e. the loop's plant period; brov_ekf_update_from_solver divides by the observer's own brov_ekf_params::dt instead -- the
+ * two agree when the two are equal. */
+int brov_vehicle_observe(brov_fleet* f, brov_ekf* e, double dt, void* stream);
+/* p[0..3] of every stage of every candidate of vehicle v := brov_ekf_mpc_p_device(e)[v]; p[4..15] are left alone.  Same stream as the
+ * brov_vehicle_observe of the tick.  BROV_ERR_ARG while the fleet's plant parameters are unset (brov_fleet_set_plant_params_host): the
+ * fleet's plant would read the estimate back out of the controller's stage-0 parameters.  The observer is created with compensate_coef =
+ * rotor_constant = 1 (see brov_ekf_apply_to_solver). */
+int brov_vehicle_apply_estimate(brov_fleet* f, brov_ekf* e, void* stream);
+/* brov_closed_loop_fleet under the fleet's wrench mode with the observer closing the loop.  Per tick k, on the solver's last stream:
+ * brov_set_yref_candidates(s, t0 + k*dt_ref, dt_node) -> brov_solve(s) -> brov_fleet_step -> with e: brov_vehicle_observe(f, e, dt) ->
+ * brov_vehicle_apply_estimate(f, e); one host wait at the end.  Logs as brov_closed_loop_fleet, and w_log HOST [ticks][V][6] or NULL: the
+ * wrench every vehicle was under (zeros while OFF), est_log HOST [ticks][V][6] or NULL: the observer's x[12..17] after each tick.
+ * e == NULL: brov_closed_loop_fleet with the wrench log; est_log must then be NULL.  With e the refusals of brov_vehicle_apply_estimate hold. */
+int brov_closed_loop_fleet_dob(brov_fleet* f, brov_ekf* e /*NULL: no observer*/, int ticks, double t0, double dt_ref, double dt_node,
+                               double dt, int substeps, double* u_log, double* x_log, int32_t* st_log, int32_t* win_log,
+                               double* w_log /*[ticks][V][6]*/, double* est_log /*[ticks][V][6]*/);
 
 #ifdef __cplusplus
 }
