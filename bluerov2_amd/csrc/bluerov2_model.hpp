@@ -68,9 +68,9 @@ __device__ __forceinline__ Wrench make_wrench(const double* __restrict__ u) {
 }
 
 // sin and cos together, branch-free: 3-term Cody-Waite reduction by pi/2 (FMA) + the classic degree-13/14 minimax kernels
-// on [-pi/4, pi/4].  Error < 1 ulp for |a| < ~1e6 rad (yaw_sum of the reference grows by 2 pi per lap, i.e. a few
-// hundred rad at most); NaN/Inf propagate.  ocml's sincos() costs ~3x the registers (Payne-Hanek path) and pushed the
-// linearisation kernel into scratch.
+// on [-pi/4, pi/4].  Measured for |a| <= 1e6 rad (yaw_sum of the reference grows by 2 pi per lap, i.e. a few hundred rad at most): at most
+// 1.53 ulp (sin, at a = -547.42; cos 1.45), no quadrant error, also at the doubles next to k pi/2 (profiles/model_exact.txt; held to 2 ulp
+// by tests/test_gpu_model_exact.py); sin(-0.0) = +0; NaN/Inf give NaN.  ocml's sincos() costs ~3x the registers and pushed the linearisation kernel into scratch.
 __device__ __forceinline__ void sincos_pio2(double a, double* sn, double* cs) {
     const double n = rint(a * 6.36619772367581382433e-01);
     double r = fma(-n, 1.57079632679489655800e+00, a);

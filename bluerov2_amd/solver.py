@@ -113,6 +113,7 @@ def _protos(L):
         "brov_get_thrusts_host": [vp, dp], "brov_last_solve_seconds": [vp, dp, dp], "brov_enable_timing": [vp, C.c_int],
         "brov_selftest_tile_tn": [dp, dp, dp, dp, C.c_int],
         "brov_selftest_sweep12": [dp, dp, C.POINTER(C.c_int)],
+        "brov_selftest_model": [dp, dp, dp, dp, C.c_int],
         "brov_plant_set_params_host": [vp, dp], "brov_plant_step": [vp, C.c_double, C.c_int, vp], "brov_get_x0_host": [vp, dp],
         "brov_closed_loop": [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, dp, dp, C.POINTER(C.c_int32)],
         "brov_traj_set_host": [vp, dp, C.c_int], "brov_traj_rows": [vp], "brov_set_yref_from_traj": [vp, C.c_int, C.c_int, vp],
@@ -621,3 +622,28 @@ def selftest_tile_tn(xt, y, c, k4):
     if rc != 0:
         raise RuntimeError(f"selftest failed {rc}")
     return out
+
+
+def selftest_model(a=None, d=None, x=None, u=None, p=None, ww=None, rp=None):
+    """the device model's building blocks alone, one lane per item (csrc/model_selftest.hip): sincos_pio2(a[n]), rcp_nr(d[n]) and
+    model_f of x[n,12], u[n,4], p[n,16] without and with the world wrench ww[n,6], both with the roll / pitch moments rp[n,2].
+    Arguments left out are filled with harmless values.  Returns dict(sin, cos, rcp [n], f, f_ww [n,12])."""
+    L = _load()
+    given = [v for v in (a, d, x, u, p, ww, rp) if v is not None]
+    if not given:
+        raise ValueError("selftest_model needs at least one input array")
+    n = len(given[0])
+
+    def arg(v, cols, fill):
+        if v is None:
+            return np.full((n, cols) if cols else (n,), fill, dtype=np.float64)
+        return _arr(v, (n, cols) if cols else (n,))
+    a, d = arg(a, 0, 0.0), arg(d, 0, 1.0)
+    rows = np.ascontiguousarray(np.concatenate([arg(x, NX, 0.0), arg(u, NU, 0.0), arg(p, NP, 0.0), arg(ww, 6, 0.0), arg(rp, 2, 0.0)], axis=1))
+    out = np.empty((n, 27))
+    rc = L.brov_selftest_model(_dp(a), _dp(d), _dp(rows), _dp(out), n)
+    if rc == -2:
+        raise NoDeviceError("no HIP device")
+    if rc != 0:
+        raise RuntimeError(f"selftest failed {rc}")
+    return dict(sin=out[:, 0].copy(), cos=out[:, 1].copy(), rcp=out[:, 2].copy(), f=out[:, 3:15].copy(), f_ww=out[:, 15:27].copy())

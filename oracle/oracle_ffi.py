@@ -74,6 +74,7 @@ class Oracle:
         L.orc_f.argtypes = [_dp] * 4
         L.orc_jac.argtypes = [_dp] * 5
         L.orc_rk4_sens.argtypes = [_dp, _dp, _dp, C.c_double, _dp, _dp, _dp]
+        L.orc_rk4_sens6.argtypes = [_dp, _dp, _dp, _dp, C.c_double, _dp, _dp, _dp]
         L.orc_rk4.argtypes = [_dp, _dp, _dp, C.c_double, _dp]
         L.orc_qp_solve.argtypes = [C.POINTER(OrcOpts)] + [_dp] * 15
         L.orc_qp_solve.restype = C.c_int
@@ -121,10 +122,14 @@ class Oracle:
         self.lib.orc_jac(_p(x), _p(u), _p(p), _p(A), _p(B))
         return A, B
 
-    def rk4_sens(self, x, u, p, h):
+    def rk4_sens(self, x, u, p, h, drp=None):
+        """drp: the two roll / pitch moments of the 6-disturbance variant (None = the shipped model)"""
         x, u, p = _c(x, (NX,)), _c(u, (NU,)), _c(p, (NP,))
         xn, A, B = np.empty(NX), np.empty((NX, NX)), np.empty((NX, NU))
-        self.lib.orc_rk4_sens(_p(x), _p(u), _p(p), float(h), _p(xn), _p(A), _p(B))
+        if drp is None:
+            self.lib.orc_rk4_sens(_p(x), _p(u), _p(p), float(h), _p(xn), _p(A), _p(B))
+        else:
+            self.lib.orc_rk4_sens6(_p(x), _p(u), _p(p), _p(_c(drp, (2,))), float(h), _p(xn), _p(A), _p(B))
         return xn, A, B
 
     def init_iterate(self, o, nb=None):
