@@ -26,6 +26,58 @@ extern "C" const char* brov_last_error(void) { return g_err.c_str(); }
 
 #define HIPCHK(call) BROV_HIPCHK(g_err, call)
 
+// What ONE launch reads and writes in place of the solver's own arrays (null: those): a local of brov_tick_host, handed down to solve_phase /
+// make_params.  A zero-copy tick's kernel reads the inputs passed with it straight from the pinned staging buffer (no copy command ahead of
+// it); the records go to the host mailbox of that tick (device-visible pinned memory).
+struct LaunchInputs {
+    const double *x0 = nullptr, *yref = nullptr, *par = nullptr;
+    brov_result* mail = nullptr;
+    int32_t* mail_flag = nullptr;    // sequence words the host polls (null with `mail` set: a large batch, the host waits for the launch)
+    int32_t mail_seq = 0;
+    bool reads_pinned = false;       // the kernel reads the pinned inputs: no need to order it behind the refresh copies of an earlier tick
+};
+// The pinned staging buffer of brov_tick_host, offsets in doubles: input set 0 (x0 | shared window | stage parameters) | records | sequence
+// words | input set 1.  Ticks that copy their arguments in alternate between the two input sets; set 0 is the one brov_tick_buffers hands out.
+struct TickLayout {
+    size_t n_x0, n_y, n_p, n_r, n_f;
+    TickLayout(size_t B, size_t N)
+        : n_x0(B * 12), n_y((N + 1) * 16), n_p(B * (N + 1) * 16), n_r((B * sizeof(brov_result) + 7) / 8), n_f((B * sizeof(int32_t) + 7) / 8) {}
+    size_t inputs() const { return n_x0 + n_y + n_p; }
+    size_t x0(int set) const { return set ? inputs() + n_r + n_f : 0; }
+    size_t window(int set) const { return x0(set) + n_x0; }
+    size_t params(int set) const { return window(set) + n_y; }
+    size_t records() const { return inputs(); }
+    size_t seq_words() const { return inputs() + n_r; }
+    size_t total() const { return 2 * inputs() + n_r + n_f; }
+};
+// Everything that belongs to brov_tick_host's transport alone, all of it created on first use
+struct TickChannel {
+    hipStream_t stream = nullptr;        // the solver's own non-blocking stream
+    double* pin = nullptr;               // pinned staging buffer (TickLayout)
+    size_t pin_doubles = 0;
+    hipEvent_t ev_up = nullptr;          // a preparation tick (rti_phase 1): its uploads have left the pinned staging buffer
+    hipEvent_t ev_tick = nullptr;        // ticks with inputs read in place: the kernel's end (neither the host nor the next tick's kernel waits for the copies behind it)
+    hipEvent_t ev_pre = nullptr;         // large batches: recorded AHEAD of the tick's kernel -- its refresh copies run next to the kernel, not behind it
+    hipStream_t copy_stream = nullptr;   // ... those copies (pinned staging buffer -> the device arrays every other entry point works on) run here, behind ev_tick
+    hipEvent_t ev_copy = nullptr;        // ... and end here (alias of the ev_set[] recorded last)
+    hipEvent_t ev_set[2] = {nullptr, nullptr};   // the refresh copies out of input set 0 / 1 of the pinned staging buffer (see stage_inputs)
+    bool set_pending[2] = {false, false};
+    int pin_sel = 0;                     // input set the last copying tick used
+    bool buffers_out = false;            // brov_tick_buffers has handed set 0 out
+    bool copies_pending = false;         // ev_copy recorded and not yet waited for by the host
+    int copy_mask = 0;                   // ... which device arrays those copies write: 1 x0, 2 shared window, 4 stage parameters
+    int32_t mail_seq = 0;                // sequence number of the last mailbox tick
+    double tick_us[5] = {0, 0, 0, 0, 0};   // BROV_TICK_BREAKDOWN=1: host time of the last brov_tick_host by part (brov_dev_tick_breakdown)
+    // nothing of a tick may still be in flight when the solver's memory goes: the tail of its kernel, the input copies behind it
+    void drain() { for (hipStream_t q : {stream, copy_stream}) if (q) hipStreamSynchronize(q); }
+    void destroy() {
+        if (pin) hipHostFree(pin);
+        if (copy_stream) hipStreamDestroy(copy_stream);
+        for (hipEvent_t e : {ev_tick, ev_pre, ev_up, ev_set[0], ev_set[1]}) if (e) hipEventDestroy(e);
+        if (stream) hipStreamDestroy(stream);
+    }
+};
+
 struct brov_solver {
     int device = 0, B = 0, N = 0;
     brov_opts opts{};
@@ -66,7 +118,7 @@ struct brov_solver {
     int cus = 256;                   // compute units of the device, queried once in brov_create
     double* ws = nullptr;        // windowed kernel: per-block parking images
     int32_t* counter = nullptr;
-    unsigned win_tick = 0;           // windowed launches so far: which of the two hand-out counters the next one uses
+    unsigned win_count = 0;           // windowed launches so far: which of the two hand-out counters the next one uses
     int win_blocks = 0, win_L = 0;
     double* ws_split = nullptr;      // fused-kernel horizons, at most one instance per CU: per-instance workspace of the resident kernel's split launches (rti_phase 1 / 2)
     int alt_blocks = 0, alt_L = 0;   // parallel-in-time rounds (pit_rounds_stages): the resident configuration a solve may use instead
@@ -80,31 +132,10 @@ struct brov_solver {
     double* wst = nullptr;           // device [N+1][16] scaled weights per stage
     int32_t* sched = nullptr;        // work ordering: 3 rotating buffers of 64 class counters | lists | pos[B] (qp_kernel.hip, sched_map)
     unsigned sched_tick = 0;
-    hipStream_t tick_stream = nullptr;   // brov_tick_host: the solver's own stream and pinned staging buffer
-    double* pin = nullptr;
-    size_t pin_doubles = 0;
-    // brov_tick_host, mailbox path: inputs passed with the tick are read by THIS launch straight from the pinned staging buffer (no copy
-    // command ahead of the kernel); their device copies are refreshed behind the kernel.  Non-null only while that launch is built.
-    const double *tick_x0 = nullptr, *tick_yref = nullptr, *tick_par = nullptr;
-    hipEvent_t ev_up = nullptr;          // a preparation tick (rti_phase 1): its uploads have left the pinned staging buffer
-    hipEvent_t ev_tick = nullptr;        // ticks with inputs read in place: the kernel's end (neither the host nor the next tick's kernel waits for the copies behind it)
-    hipEvent_t ev_pre = nullptr;         // large batches: recorded AHEAD of the tick's kernel -- its refresh copies run next to the kernel, not behind it
-    hipStream_t copy_stream = nullptr;   // ... those copies (pinned staging buffer -> the device arrays every other entry point works on) run here, behind ev_tick
-    hipEvent_t ev_copy = nullptr;        // ... and end here (alias of the ev_set[] recorded last)
-    hipEvent_t ev_set[2] = {nullptr, nullptr};   // the refresh copies out of input set 0 / 1 of the pinned staging buffer (see brov_tick_host)
-    bool set_pending[2] = {false, false};
-    int pin_sel = 0;                     // input set the last copying tick used
-    bool buffers_out = false;            // brov_tick_buffers has handed set 0 out
-    bool copies_pending = false;         // ev_copy recorded and not yet waited for by the host
-    int copy_mask = 0;                   // ... which device arrays those copies write: 1 x0, 2 shared window, 4 stage parameters
-    bool in_tick = false;                // brov_tick_host is calling brov_solve_phase (whose kernel reads the pinned inputs: no need to order it behind the copies)
-    brov_result* mail = nullptr;     // host mailbox of the tick in flight (device-visible pinned memory), else nullptr
-    int32_t* mail_flag = nullptr;
+    TickChannel tick;                // brov_tick_host's transport; sync_last / order_behind_last wait for the refresh copies it leaves running
     bool pit_ran = false;            // the last solve launched rti_pit_kernel
     int32_t* pit_done = nullptr;     // [B]: written by rti_pit_kernel (parallel-in-time step-0 solve), read by the resident kernel launched behind it
-    int32_t mail_seq = 0;
-    double tick_us[5] = {0, 0, 0, 0, 0};   // BROV_TICK_BREAKDOWN=1: host time of the last brov_tick_host by part (brov_dev_tick_breakdown)
-    DevKnobs k;                      // development knobs (BROV_* environment), read once in brov_create: no getenv on the path of a solve
+    DevKnobs k;                     // development knobs (BROV_* environment), read once in brov_create: no getenv on the path of a solve
 };
 
 // The solver's development knobs: A/B switches and test hooks, all of them BROV_* environment variables.  Read ONCE per solver (brov_create;
@@ -360,21 +391,13 @@ extern "C" int brov_create(brov_solver** out, int device, int B, const brov_opts
 extern "C" void brov_destroy(brov_solver* s) {
     if (!s) return;
     hipSetDevice(s->device);
-    // nothing of this solver may still be in flight when its memory goes: the tail of a tick's kernel, the input copies behind it
-    if (s->tick_stream) hipStreamSynchronize(s->tick_stream);
-    if (s->copy_stream) hipStreamSynchronize(s->copy_stream);
+    s->tick.drain();
     // (a caller's own stream is the caller's to drain -- it may not exist any more; hipFree below waits for the device in any case)
     s->mem.free_all();
     if (s->traj) hipFree(s->traj);
     if (s->wr_tab) hipFree(s->wr_tab);
     if (s->dbg) hipFree(s->dbg);
-    if (s->pin) hipHostFree(s->pin);
-    if (s->copy_stream) hipStreamDestroy(s->copy_stream);
-    if (s->ev_tick) hipEventDestroy(s->ev_tick);
-    if (s->ev_pre) hipEventDestroy(s->ev_pre);
-    if (s->ev_up) hipEventDestroy(s->ev_up);
-    for (int k = 0; k < 2; k++) if (s->ev_set[k]) hipEventDestroy(s->ev_set[k]);
-    if (s->tick_stream) hipStreamDestroy(s->tick_stream);
+    s->tick.destroy();
     for (int k = 0; k < 3; k++)
         if (s->ev[k]) hipEventDestroy(s->ev[k]);
     delete s;
@@ -399,13 +422,14 @@ extern "C" size_t brov_device_bytes(const brov_solver* s) { return s ? s->mem.by
 // host-side wait for everything the solver has in flight: the last stream, and the input copies a tick left running on the copy stream
 static hipError_t sync_last(brov_solver* s) {
     hipError_t e = hipStreamSynchronize(s->last_stream);
-    if (e == hipSuccess && s->copies_pending) { e = hipEventSynchronize(s->ev_copy); s->copies_pending = false; }
+    if (e == hipSuccess && s->tick.copies_pending) { e = hipEventSynchronize(s->tick.ev_copy); s->tick.copies_pending = false; }
     return e;
 }
-static int order_behind_last(brov_solver* s, hipStream_t st) {
+static int order_behind_last(brov_solver* s, hipStream_t st, bool reads_pinned = false) {
     if (s->last_stream != st) HIPCHK(hipStreamSynchronize(s->last_stream));
-    // a tick's input copies (copy stream) write the device arrays this stream's next command may read or overwrite
-    if (s->copies_pending && !s->in_tick) HIPCHK(hipStreamWaitEvent(st, s->ev_copy, 0));
+    // a tick's input copies (copy stream) write the device arrays this stream's next command may read or overwrite (reads_pinned: the launch
+    // of a tick that reads its inputs in the pinned staging buffer instead, LaunchInputs)
+    if (s->tick.copies_pending && !reads_pinned) HIPCHK(hipStreamWaitEvent(st, s->tick.ev_copy, 0));
     return BROV_OK;
 }
 extern "C" int brov_order_stream(brov_solver* s, void* stream) {
@@ -874,7 +898,9 @@ static SolvePlan plan_solve(const brov_solver* s, int rti_phase) {
     return p;
 }
 
-static DevParams make_params(const brov_solver* s, const SolvePlan& plan) {
+static DevParams make_params(const brov_solver* s, const SolvePlan& plan, const LaunchInputs* in = nullptr) {
+    static const LaunchInputs none;
+    if (!in) in = &none;
     DevParams P;
     std::memset(&P, 0, sizeof P);
     P.B = s->B; P.N = s->N;
@@ -887,10 +913,10 @@ static DevParams make_params(const brov_solver* s, const SolvePlan& plan) {
     for (int j = 0; j < 16; j++) P.W[j] = s->opts.W[j];
     for (int j = 0; j < 12; j++) P.We[j] = s->opts.We[j];
     for (int j = 0; j < 4; j++) { P.lbu[j] = s->opts.lbu[j]; P.ubu[j] = s->opts.ubu[j]; }
-    P.x0 = s->tick_x0 ? s->tick_x0 : s->x0;
-    P.yref = s->tick_yref ? s->tick_yref : (s->yref_shared ? shared_window(s) : s->yref);
+    P.x0 = in->x0 ? in->x0 : s->x0;
+    P.yref = in->yref ? in->yref : (s->yref_shared ? shared_window(s) : s->yref);
     P.yref_stride = s->yref_shared ? 0 : (int64_t)(s->N + 1) * 16;
-    P.par = s->tick_par ? s->tick_par : s->par;
+    P.par = in->par ? in->par : s->par;
     P.par_rp = s->dist6 ? s->par_rp : nullptr;
     P.tsv = general_grid(s) ? s->tsv : nullptr;
     P.sched = s->k.sched ? s->sched : nullptr;   // development knob: BROV_SCHED=0 hands the instances out in index order (A/B of the work ordering)
@@ -901,10 +927,10 @@ static DevParams make_params(const brov_solver* s, const SolvePlan& plan) {
     P.BA = s->BA; P.bvec = s->bvec; P.kktp = s->kktp;
     P.Ks = s->Ks; P.Kt = s->Kt; P.Mt = s->Mt; P.Pb = s->Pb; P.kff = s->kff; P.vhat = s->vhat; P.ipm = s->ipm;
     P.dxb = s->dxb; P.cst = s->cst; P.res = s->res;
-    P.mail = s->mail; P.mail_flag = s->mail_flag; P.mail_seq = s->mail_seq;
+    P.mail = in->mail; P.mail_flag = in->mail_flag; P.mail_seq = in->mail_seq;
     P.mail_early = s->k.mail_early;   // development knob (A/B)
-    P.counter = s->counter + 32 * (s->win_tick & 1u);
-    P.counter_next = s->counter + 32 * ((s->win_tick + 1u) & 1u);
+    P.counter = s->counter + 32 * (s->win_count & 1u);
+    P.counter_next = s->counter + 32 * ((s->win_count + 1u) & 1u);
     P.ws = plan.ws; P.ws_stride = plan.ws_stride; P.win_L = plan.win_L; P.win_blocks = plan.win_blocks;
     P.rti_split = plan.rti_split; P.pit_blocks = plan.pit_blocks;
     if (plan.pit) { P.pit = plan.pit; P.pit_done = s->pit_done; P.pit_try = s->k.pit_try; P.pit_light = s->k.pit_light; }
@@ -914,10 +940,38 @@ static DevParams make_params(const brov_solver* s, const SolvePlan& plan) {
 // the launch(es) of an LDS-resident family and what the solver remembers of them
 static void launch_lds(brov_solver* s, const DevParams& P, int family, hipStream_t st) {
     if (family == FAM_FUSED) launch_fused(P, st, s->k);
-    else { launch_windowed(P, st, s->k); s->win_tick++; }   // persistent blocks; the two hand-out counters alternate
+    else { launch_windowed(P, st, s->k); s->win_count++; }   // persistent blocks; the two hand-out counters alternate
     s->pit_ran = P.pit != 0;
     s->last_family = family;
     s->last_stream = st;
+}
+// brov_enable_timing: event k of the three around a solve's launches (0 start, 1 linearisation done / the one launch starts, 2 end), which
+// brov_last_solve_seconds reads
+static void time_mark(brov_solver* s, int k, hipStream_t st) {
+    if (s->timing) { hipEventRecord(s->ev[k], st); s->ev_valid = s->ev_valid || k == 2; }
+}
+// the plant update a closed loop's launch of many steps does behind every step, with its DEVICE logs
+struct PlantInLaunch { double dt; int substeps; double *xlog, *ulog; };
+// `n` steps of every instance in ONE launch of the family's *_ticks kernel on `st`, the shared window moving on row_stride_doubles per step;
+// the window in force afterwards is the last step's.  brov_last_solve_seconds then reports THIS launch.
+static int launch_ticks(brov_solver* s, int family, int n, int64_t row_stride_doubles, int32_t* status_log, const PlantInLaunch* plant,
+                        hipStream_t st) {
+    if (int rc = order_behind_last(s, st)) return rc;
+    DevParams P = make_params(s, plan_solve(s, 0));
+    P.sched = nullptr;                 // a launch of many steps neither reads nor writes the work ordering: every instance follows its own history
+    P.ticks = n; P.tick_yref = row_stride_doubles; P.tick_status = status_log;
+    if (plant) {
+        P.plant_pp = s->pplant; P.plant_rp = plant_rp(s); P.plant_rp_stride = plant_rp_stride(s); P.plant_substeps = plant->substeps; P.plant_dt = plant->dt;
+        P.x0_rw = s->x0; P.plant_xlog = plant->xlog; P.plant_ulog = plant->ulog;
+    }
+    time_mark(s, 0, st); time_mark(s, 1, st);
+    launch_lds(s, P, family, st); s->prep_path = 0;
+    time_mark(s, 2, st);
+    if (row_stride_doubles > 0) {
+        s->traj_line += (n - 1) * (int)(row_stride_doubles / 16);
+        s->yref_view = s->traj + (size_t)s->traj_line * 16;
+    }
+    return BROV_OK;
 }
 
 static int ticks_kernel(const brov_solver* s);
@@ -1022,19 +1076,9 @@ static int run_loop_ticks(brov_solver* s, int n, int line, int ncols, double dt,
     int rc = BROV_OK;
     if (one_launch) {
         rc = brov_set_yref_from_traj(s, line, 16, st);
-        if (rc == BROV_OK) rc = order_behind_last(s, st);
-        if (rc == BROV_OK) {
-            DevParams P = make_params(s, plan_solve(s, 0));
-            P.sched = nullptr;
-            P.ticks = n; P.tick_yref = 16; P.tick_status = T.status(0);
-            P.plant_pp = s->pplant; P.plant_rp = plant_rp(s); P.plant_rp_stride = plant_rp_stride(s); P.plant_substeps = substeps; P.plant_dt = dt;
-            P.x0_rw = s->x0; P.plant_xlog = T.x(0); P.plant_ulog = T.u(0);
-            if (s->timing) { hipEventRecord(s->ev[0], st); hipEventRecord(s->ev[1], st); }   // (as brov_solve_ticks: brov_last_solve_seconds then reports THIS launch)
-            launch_lds(s, P, which, st); s->prep_path = 0;
-            if (s->timing) { hipEventRecord(s->ev[2], st); s->ev_valid = true; }
-            s->traj_line = line + n - 1; s->yref_view = s->traj + (size_t)s->traj_line * 16;
-            s->wr_tick += n;
-        }
+        const PlantInLaunch plant{dt, substeps, T.x(0), T.u(0)};
+        if (rc == BROV_OK) rc = launch_ticks(s, which, n, 16, T.status(0), &plant, st);
+        if (rc == BROV_OK) s->wr_tick += n;
     }
     for (int k = 0; k < n && rc == BROV_OK && !one_launch; k++) {
         forget_traj_window(s);
@@ -1173,11 +1217,10 @@ extern "C" int brov_reset(brov_solver* s) {  // acados_solver_bluerov2.c:797-830
     return BROV_OK;
 }
 
-extern "C" int brov_solve_phase(brov_solver* s, void* stream, int rti_phase) {
-    if (!s || rti_phase < 0 || rti_phase > 2) return BROV_ERR_ARG;
+// one RTI step (or half of one) on `st`; `in`: what brov_tick_host has its launch read and write in place of the solver's arrays (null: nothing)
+static int solve_phase(brov_solver* s, hipStream_t st, int rti_phase, const LaunchInputs* in) {
     HIPCHK(hipSetDevice(s->device));
-    hipStream_t st = (hipStream_t)stream;
-    if (int rc = order_behind_last(s, st)) return rc;   // e.g. a brov_tick_host whose kernel is still finishing on the solver's own stream
+    if (int rc = order_behind_last(s, st, in && in->reads_pinned)) return rc;   // e.g. a brov_tick_host whose kernel is still finishing on the solver's own stream
     const SolvePlan plan = plan_solve(s, rti_phase);
     if (rti_phase == 2 && s->prep_path == 0) {   // no preparation, or one that a later step (rti_phase 0, an earlier feedback) has used up: the iterate it linearised is gone
         g_err = "brov_solve: rti_phase 2 needs a preparation (rti_phase 1) of the CURRENT iterate: none since the last step";
@@ -1188,22 +1231,26 @@ extern "C" int brov_solve_phase(brov_solver* s, void* stream, int rti_phase) {
         return BROV_ERR_ARG;
     }
     if (rti_phase == 1) s->prep_path = plan.prep_path;
-    const DevParams P = make_params(s, plan);
-    if (s->timing) hipEventRecord(s->ev[0], st);
+    const DevParams P = make_params(s, plan, in);
+    time_mark(s, 0, st);
     if (plan.family != FAM_STREAMING) {
-        if (s->timing) hipEventRecord(s->ev[1], st);
+        time_mark(s, 1, st);
         launch_lds(s, P, plan.family, st);
     } else {
         if (rti_phase != 2) launch_linearise(P, st);
-        if (s->timing) hipEventRecord(s->ev[1], st);
+        time_mark(s, 1, st);
         if (rti_phase != 1) launch_qp(P, st);
         s->pit_ran = false; s->last_family = FAM_STREAMING; s->last_stream = st;
     }
-    if (s->timing) { hipEventRecord(s->ev[2], st); s->ev_valid = true; }
+    time_mark(s, 2, st);
     if (rti_phase != 1) s->sched_tick++;   // a QP kernel ran: it wrote the next ordering
     if (rti_phase != 1) s->prep_path = 0;  // ... and the iterate moved (and the per-block workspace was rewritten): whatever preparation there was is used up
     HIPCHK(hipGetLastError());
     return BROV_OK;
+}
+extern "C" int brov_solve_phase(brov_solver* s, void* stream, int rti_phase) {
+    if (!s || rti_phase < 0 || rti_phase > 2) return BROV_ERR_ARG;
+    return solve_phase(s, (hipStream_t)stream, rti_phase, nullptr);
 }
 extern "C" int brov_solve(brov_solver* s, void* stream) { return brov_solve_phase(s, stream, 0); }
 
@@ -1239,17 +1286,7 @@ extern "C" int brov_solve_ticks(brov_solver* s, void* stream, int ticks, int row
         HIPCHK(hipGetLastError());
         return BROV_OK;
     }
-    if (int rc = order_behind_last(s, st)) return rc;
-    DevParams P = make_params(s, plan_solve(s, 0));
-    P.sched = nullptr;                 // a launch of many steps neither reads nor writes the work ordering: every instance follows its own history
-    P.ticks = ticks; P.tick_yref = (int64_t)row_stride * 16; P.tick_status = status_log;
-    if (s->timing) { hipEventRecord(s->ev[0], st); hipEventRecord(s->ev[1], st); }
-    launch_lds(s, P, which, st); s->prep_path = 0;
-    if (s->timing) { hipEventRecord(s->ev[2], st); s->ev_valid = true; }
-    if (row_stride > 0) {              // the window in force is the last step's
-        s->traj_line = line0 + (ticks - 1) * row_stride;
-        s->yref_view = s->traj + (size_t)s->traj_line * 16;
-    }
+    if (int rc = launch_ticks(s, which, ticks, (int64_t)row_stride * 16, status_log, nullptr, st)) return rc;
     HIPCHK(hipGetLastError());
     return BROV_OK;
 }
@@ -1258,19 +1295,16 @@ extern "C" int brov_solve_ticks(brov_solver* s, void* stream, int ticks, int row
 // changed go through ONE pinned staging buffer and asynchronous copies on the solver's own stream, the step is enqueued behind them,
 // the result records come back the same way, and the host waits once.  The separate setters + brov_solve + brov_get_results_host
 // cost five blocking pageable copies and three synchronisations per tick -- 0.2 .. 0.4 ms at batch 1, more than the kernels.
-// the pinned staging buffer of brov_tick_host (x0 | shared window | stage parameters | records | sequence words), (re)allocated on demand
+// the pinned staging buffer of brov_tick_host (TickLayout), (re)allocated on demand
 static int tick_pin(brov_solver* s) {
-    const size_t B = s->B, N1 = s->N + 1;
-    const size_t n_x0 = B * 12, n_y = N1 * 16, n_p = B * N1 * 16, n_r = (B * sizeof(brov_result) + 7) / 8, n_f = (B * sizeof(int32_t) + 7) / 8;
-    // (x0 | window | parameters) | records | sequence words | a second (x0 | window | parameters): ticks that copy their arguments in alternate
-    // between the two input sets
-    const size_t n_all = 2 * (n_x0 + n_y + n_p) + n_r + n_f;
-    if (s->pin_doubles < n_all) {
-        if (s->pin) hipHostFree(s->pin);
-        s->pin = nullptr; s->pin_doubles = 0;
-        HIPCHK(hipHostMalloc((void**)&s->pin, n_all * sizeof(double), hipHostMallocDefault));
-        s->pin_doubles = n_all;
-        std::memset(s->pin, 0, s->pin_doubles * sizeof(double));
+    TickChannel& ch = s->tick;
+    const size_t n_all = TickLayout(s->B, s->N).total();
+    if (ch.pin_doubles < n_all) {
+        if (ch.pin) hipHostFree(ch.pin);
+        ch.pin = nullptr; ch.pin_doubles = 0;
+        HIPCHK(hipHostMalloc((void**)&ch.pin, n_all * sizeof(double), hipHostMallocDefault));
+        ch.pin_doubles = n_all;
+        std::memset(ch.pin, 0, ch.pin_doubles * sizeof(double));
     }
     return BROV_OK;
 }
@@ -1280,145 +1314,152 @@ extern "C" int brov_tick_buffers(brov_solver* s, double** x0, double** yref_shar
     if (!s) return BROV_ERR_ARG;
     HIPCHK(hipSetDevice(s->device));
     if (int rc = tick_pin(s)) return rc;
-    const size_t B = s->B, N1 = s->N + 1;
+    TickChannel& ch = s->tick;
+    const TickLayout L(s->B, s->N);
     // input set 0 is the caller's from here on and "may be rewritten freely" (header): refresh copies an EARLIER copying tick left running out
     // of set 0 (copy_stream; they read it) must be over before the pointers go out -- the wait at the top of the next brov_tick_host comes
     // after the caller's writes (round-5 advisor)
-    if (s->set_pending[0]) { HIPCHK(hipEventSynchronize(s->ev_set[0])); s->set_pending[0] = false; }
-    s->buffers_out = true;
-    if (x0) *x0 = s->pin;
-    if (yref_shared) *yref_shared = s->pin + B * 12;
-    if (par_stage) *par_stage = s->pin + B * 12 + N1 * 16;
-    if (res) *res = (const brov_result*)(s->pin + B * 12 + N1 * 16 + B * N1 * 16);
+    if (ch.set_pending[0]) { HIPCHK(hipEventSynchronize(ch.ev_set[0])); ch.set_pending[0] = false; }
+    ch.buffers_out = true;
+    if (x0) *x0 = ch.pin + L.x0(0);
+    if (yref_shared) *yref_shared = ch.pin + L.window(0);
+    if (par_stage) *par_stage = ch.pin + L.params(0);
+    if (res) *res = (const brov_result*)(ch.pin + L.records());
     return BROV_OK;
 }
 
-extern "C" int brov_tick_host(brov_solver* s, const double* x0, const double* yref_shared, const double* par_stage, int rti_phase,
-                              brov_result* res) {
-    if (!s || rti_phase < 0 || rti_phase > 2) return BROV_ERR_ARG;
-    using clk = std::chrono::steady_clock;
-    const bool brk = s->k.tick_breakdown != 0;
-    clk::time_point tb0, tb1, tb2, tb3, tb4;
-    if (brk) tb0 = clk::now();
-    HIPCHK(hipSetDevice(s->device));
-    const size_t B = s->B, N1 = s->N + 1;
-    const size_t n_x0 = B * 12, n_y = N1 * 16, n_p = B * N1 * 16, n_r = (B * sizeof(brov_result) + 7) / 8;
-    if (!s->tick_stream) HIPCHK(hipStreamCreateWithFlags(&s->tick_stream, hipStreamNonBlocking));
-    if (int rc = tick_pin(s)) return rc;
-    hipStream_t st = s->tick_stream;
-    if (s->last_stream != st) HIPCHK(sync_last(s));   // an earlier solve on the caller's stream
-    double* pr = s->pin + n_x0 + n_y + n_p;
-    volatile int32_t* pf = (volatile int32_t*)(pr + n_r);
-    // The refresh copies a zero-copy tick leaves running behind its kernel (pinned staging buffer -> device arrays, copy_stream) still READ the
-    // input set they were enqueued for (round-4 advisor: rewriting it under them leaves a torn or already-next-tick x0 in the device array).
-    // Waiting for them at the top of the next tick costs a back-to-back control loop 30 us (the kernel's tail and the copies behind it; measured,
-    // round 5) -- so the staging buffer holds TWO input sets and ticks that copy their arguments in alternate: a set is rewritten two ticks
-    // after its copies were enqueued, and the check below almost always finds them done.  Set 0 is the one brov_tick_buffers hands out.
-    const bool in_place = (x0 && x0 == s->pin) || (yref_shared && yref_shared == s->pin + n_x0) || (par_stage && par_stage == s->pin + n_x0 + n_y);
+// How one tick moves its inputs and records: decided here, once per tick, from the call's arguments and the channel's state (no HIP call, no
+// side effect).  `passed`: 1 x0, 2 shared window, 4 stage parameters came with the tick.
+struct TickPlan {
+    int set = 0;                 // input set of the staging buffer the tick uses
+    bool mailbox = false, bulk = false;   // records: written by the kernel into the pinned buffer, with / without sequence words
+    bool zerocopy = false, behind_copies = false, copies_beside = false;   // inputs: read by the kernel in the pinned buffer; refresh copies
+};
+static TickPlan plan_tick(int B, int rti_phase, int passed, bool in_place, const DevKnobs& k, bool buffers_out, bool copies_pending, int copy_mask,
+                          int pin_sel) {
+    TickPlan t;
     // (a caller that holds set 0 through brov_tick_buffers keeps it to itself: its copying ticks, if any, all use set 1)
-    const int sel = in_place ? 0 : (s->buffers_out ? 1 : (s->pin_sel ^= 1));
-    double* px = sel ? pr + n_r + (B * sizeof(int32_t) + 7) / 8 : s->pin; double* py = px + n_x0; double* pp = py + n_y;
-    if (s->set_pending[sel] && hipEventQuery(s->ev_set[sel]) != hipSuccess) {
-        (void)hipGetLastError();
-        HIPCHK(hipEventSynchronize(s->ev_set[sel]));
-    }
-    s->set_pending[sel] = false;
-    if (x0 && x0 != px) std::memcpy(px, x0, n_x0 * sizeof(double));   // (equal: the caller wrote into the staging buffer, brov_tick_buffers)
-    if (yref_shared) {
-        if (yref_shared != py) std::memcpy(py, yref_shared, n_y * sizeof(double));
-        forget_traj_window(s);
-        s->yref_shared = true;
-    }
-    if (par_stage) { if (par_stage != pp) std::memcpy(pp, par_stage, n_p * sizeof(double)); s->pplant_stale = true; }
-    // Small batches with the mailbox: the kernel reads the inputs of this tick where the host has just put them (pinned, device-visible
-    // memory: 21 KB over PCIe inside the linearisation's staging loads) instead of waiting for a copy command ahead of it; the device
-    // copies every other entry point works on are refreshed by the same copies, enqueued BEHIND the launch (BROV_TICK_ZEROCOPY=0: ahead).
-    const bool mailbox = rti_phase != 1 && B <= kTickMailboxMaxBatch && s->k.tick_mailbox;
-    // Larger batches whose records the kernel writes into the pinned buffer itself (bulk, below): the same for x0 and a shared window (96 bytes
-    // per instance over PCIe inside the linearisation's staging loads) -- not for per-stage parameters passed with the tick (2.7 KB per instance
-    // at N = 20: those go through the copy engine ahead of the launch, and the other inputs with them).
-    const bool bulk = !mailbox && rti_phase != 1 && B > kTickMailboxMaxBatch && s->k.tick_mailbox && s->k.tick_bulk;
-    // (a feedback call, rti_phase 2, too: its kernel reads the new measurement where the host has just put it)
-    const bool zerocopy = (mailbox || (bulk && !par_stage)) && rti_phase != 1 && s->k.tick_zerocopy;
-    auto upload = [&](hipStream_t cs) -> int {
-        if (x0 && yref_shared && par_stage) {   // device side: one allocation in the same order (brov_create)
-            HIPCHK(hipMemcpyAsync(s->x0, px, (n_x0 + n_y + n_p) * sizeof(double), hipMemcpyHostToDevice, cs));
-        } else {
-            if (x0) HIPCHK(hipMemcpyAsync(s->x0, px, n_x0 * sizeof(double), hipMemcpyHostToDevice, cs));
-            if (yref_shared) HIPCHK(hipMemcpyAsync(s->yref_sh, py, n_y * sizeof(double), hipMemcpyHostToDevice, cs));
-            if (par_stage) HIPCHK(hipMemcpyAsync(s->par, pp, n_p * sizeof(double), hipMemcpyHostToDevice, cs));
-        }
-        return BROV_OK;
-    };
-    if (!zerocopy) {
-        if (s->copies_pending) HIPCHK(hipStreamWaitEvent(st, s->ev_copy, 0));   // (an earlier tick's copies into the same device arrays)
-        if (int rc = upload(st)) return rc;
-        if (rti_phase == 1) {   // a preparation delivers nothing: the call returns when the staging buffer is free again (below), not when the kernel ends
-            if (!s->ev_up) HIPCHK(hipEventCreateWithFlags(&s->ev_up, hipEventDisableTiming));
-            HIPCHK(hipEventRecord(s->ev_up, st));
-        }
-    } else {
-        s->tick_x0 = x0 ? px : nullptr; s->tick_yref = yref_shared ? py : nullptr; s->tick_par = par_stage ? pp : nullptr;
-        if (!s->copy_stream) {
-            HIPCHK(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
-            HIPCHK(hipEventCreateWithFlags(&s->ev_tick, hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&s->ev_pre, hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&s->ev_set[0], hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&s->ev_set[1], hipEventDisableTiming));
-            s->ev_copy = s->ev_set[0];
-        }
-    }
+    t.set = in_place ? 0 : (buffers_out ? 1 : pin_sel ^ 1);
     // Results.  Small batches (the ROS node's batch of one): the kernel writes every record into the pinned buffer itself and then the
     // instance's sequence word; the host polls those words -- no copy command, no stream synchronisation on the way back.  The stream
     // is queried now and then: a launch that ended without delivering (a device fault) falls back to the synchronous path's error.
     // Larger batches: the kernel still writes the records into the pinned buffer itself (no copy command behind it), without the
     // per-instance sequence words -- the host waits for the stream once.
-    if (mailbox) {
-        s->mail_seq = s->mail_seq == 0x7fffffff ? 1 : s->mail_seq + 1;
-        s->mail = (brov_result*)pr; s->mail_flag = (int32_t*)pf;
-    } else if (bulk) {
-        s->mail = (brov_result*)pr; s->mail_flag = nullptr;
-    }
+    t.mailbox = rti_phase != 1 && B <= kTickMailboxMaxBatch && k.tick_mailbox;
+    t.bulk = !t.mailbox && rti_phase != 1 && B > kTickMailboxMaxBatch && k.tick_mailbox && k.tick_bulk;
+    // Inputs.  Small batches with the mailbox: the kernel reads the inputs of this tick where the host has just put them (pinned, device-visible
+    // memory: 21 KB over PCIe inside the linearisation's staging loads) instead of waiting for a copy command ahead of it; the device
+    // copies every other entry point works on are refreshed by the same copies, enqueued BEHIND the launch (BROV_TICK_ZEROCOPY=0: ahead).
+    // Larger batches whose records the kernel writes into the pinned buffer itself (bulk): the same for x0 and a shared window (96 bytes
+    // per instance over PCIe inside the linearisation's staging loads) -- not for per-stage parameters passed with the tick (2.7 KB per instance
+    // at N = 20: those go through the copy engine ahead of the launch, and the other inputs with them).
+    // (a feedback call, rti_phase 2, too: its kernel reads the new measurement where the host has just put it; a preparation never)
+    t.zerocopy = (t.mailbox || (t.bulk && !(passed & 4))) && rti_phase != 1 && k.tick_zerocopy;
     // (inputs NOT passed with this tick are read from their device arrays: if the copies an earlier tick left running write one of those, the
     // kernel is ordered behind them after all -- a loop that passes the same inputs every tick never is)
-    const int passed = (x0 ? 1 : 0) | (yref_shared ? 2 : 0) | (par_stage ? 4 : 0);
-    const bool behind_copies = s->copies_pending && (s->copy_mask & ~passed) != 0;
-    s->in_tick = zerocopy && !behind_copies;
-    if (brk) tb1 = clk::now();
+    t.behind_copies = copies_pending && (copy_mask & ~passed) != 0;
     // Large batches (records written by the kernel, the host waits for the launch once): the refresh copies of the tick's inputs run NEXT TO the
     // kernel -- it reads the pinned copies, they write the device arrays, which nothing of this launch reads -- ordered only behind what was
     // enqueued ahead of it.  They are over long before the kernel is (0.4 MB against 0.16 ms), so a caller that owns the staging buffers
     // (brov_tick_buffers) does not pay for them at the end of the call.  Small batches keep them BEHIND the kernel: next to it they would share
     // the PCIe reads of a 50 us launch whose latency is the point.
-    const bool copies_beside = zerocopy && bulk && !behind_copies;
-    if (copies_beside) HIPCHK(hipEventRecord(s->ev_pre, st));
-    const int rc = brov_solve_phase(s, st, rti_phase);
-    if (brk) tb2 = clk::now();
-    s->in_tick = false;
-    const int32_t seq = s->mail_seq;
-    s->mail = nullptr; s->mail_flag = nullptr;
-    s->tick_x0 = s->tick_yref = s->tick_par = nullptr;
-    if (rc) return rc;
-    if (zerocopy) {
-        // the device copies every other entry point works on: refreshed BEHIND the kernel that has read the pinned ones, on the copy stream --
-        // neither the host (which waits for the kernel's end / the mailbox) nor the next tick's kernel waits for them; whatever else touches
-        // those arrays is ordered behind ev_copy (order_behind_last, sync_last)
-        HIPCHK(hipEventRecord(s->ev_tick, st));
-        HIPCHK(hipStreamWaitEvent(s->copy_stream, copies_beside ? s->ev_pre : s->ev_tick, 0));
-        if (int rc2 = upload(s->copy_stream)) return rc2;
-        s->ev_copy = s->ev_set[sel];
-        HIPCHK(hipEventRecord(s->ev_copy, s->copy_stream));
-        s->set_pending[sel] = true;
-        s->copy_mask = (s->copies_pending && !behind_copies) ? (s->copy_mask | passed) : passed;   // (arrays written by copies no kernel on st is ordered behind yet)
-        s->copies_pending = true;
+    t.copies_beside = t.zerocopy && t.bulk && !t.behind_copies;
+    return t;
+}
+// The inputs passed with the tick into input set `set` of the staging buffer, and what the solver remembers of them.
+// The refresh copies a zero-copy tick leaves running behind its kernel (pinned staging buffer -> device arrays, copy_stream) still READ the
+// input set they were enqueued for (round-4 advisor: rewriting it under them leaves a torn or already-next-tick x0 in the device array).
+// Waiting for them at the top of the next tick costs a back-to-back control loop 30 us (the kernel's tail and the copies behind it; measured,
+// round 5) -- so the staging buffer holds TWO input sets and ticks that copy their arguments in alternate: a set is rewritten two ticks
+// after its copies were enqueued, and the check below almost always finds them done.
+static int stage_inputs(brov_solver* s, const TickLayout& L, int set, const double* x0, const double* yref_shared, const double* par_stage) {
+    TickChannel& ch = s->tick;
+    if (ch.set_pending[set] && hipEventQuery(ch.ev_set[set]) != hipSuccess) {
+        (void)hipGetLastError();
+        HIPCHK(hipEventSynchronize(ch.ev_set[set]));
     }
-    if (brk) tb3 = clk::now();
-    if (mailbox) {
+    ch.set_pending[set] = false;
+    double *px = ch.pin + L.x0(set), *py = ch.pin + L.window(set), *pp = ch.pin + L.params(set);
+    if (x0 && x0 != px) std::memcpy(px, x0, L.n_x0 * sizeof(double));   // (equal: the caller wrote into the staging buffer, brov_tick_buffers)
+    if (yref_shared) {
+        if (yref_shared != py) std::memcpy(py, yref_shared, L.n_y * sizeof(double));
+        forget_traj_window(s);
+        s->yref_shared = true;
+    }
+    if (par_stage) { if (par_stage != pp) std::memcpy(pp, par_stage, L.n_p * sizeof(double)); s->pplant_stale = true; }
+    return BROV_OK;
+}
+// the inputs `passed` with a tick from input set `set` to the device arrays every other entry point works on, on `cs`
+static int upload_inputs(brov_solver* s, const TickLayout& L, int set, int passed, hipStream_t cs) {
+    const double* pin = s->tick.pin;
+    if (passed == 7) {   // device side: one allocation in the same order (brov_create)
+        HIPCHK(hipMemcpyAsync(s->x0, pin + L.x0(set), L.inputs() * sizeof(double), hipMemcpyHostToDevice, cs));
+    } else {
+        if (passed & 1) HIPCHK(hipMemcpyAsync(s->x0, pin + L.x0(set), L.n_x0 * sizeof(double), hipMemcpyHostToDevice, cs));
+        if (passed & 2) HIPCHK(hipMemcpyAsync(s->yref_sh, pin + L.window(set), L.n_y * sizeof(double), hipMemcpyHostToDevice, cs));
+        if (passed & 4) HIPCHK(hipMemcpyAsync(s->par, pin + L.params(set), L.n_p * sizeof(double), hipMemcpyHostToDevice, cs));
+    }
+    return BROV_OK;
+}
+// Ahead of the launch: the uploads of a tick whose kernel reads the device arrays; what a zero-copy tick needs behind it, on first use.
+static int enqueue_ahead(brov_solver* s, const TickLayout& L, const TickPlan& t, int passed, int rti_phase) {
+    TickChannel& ch = s->tick;
+    if (!t.zerocopy) {
+        if (ch.copies_pending) HIPCHK(hipStreamWaitEvent(ch.stream, ch.ev_copy, 0));   // (an earlier tick's copies into the same device arrays)
+        if (int rc = upload_inputs(s, L, t.set, passed, ch.stream)) return rc;
+        if (rti_phase == 1) {   // a preparation delivers nothing: the call returns when the staging buffer is free again (wait_records), not when the kernel ends
+            if (!ch.ev_up) HIPCHK(hipEventCreateWithFlags(&ch.ev_up, hipEventDisableTiming));
+            HIPCHK(hipEventRecord(ch.ev_up, ch.stream));
+        }
+    } else if (!ch.copy_stream) {
+        HIPCHK(hipStreamCreateWithFlags(&ch.copy_stream, hipStreamNonBlocking));
+        for (hipEvent_t* e : {&ch.ev_tick, &ch.ev_pre, &ch.ev_set[0], &ch.ev_set[1]}) HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+        ch.ev_copy = ch.ev_set[0];
+    }
+    return BROV_OK;
+}
+// what the tick's launch reads and writes in the staging buffer
+static LaunchInputs tick_launch_inputs(const TickChannel& ch, const TickLayout& L, const TickPlan& t, int passed) {
+    LaunchInputs in;
+    if (t.zerocopy) {
+        if (passed & 1) in.x0 = ch.pin + L.x0(t.set);
+        if (passed & 2) in.yref = ch.pin + L.window(t.set);
+        if (passed & 4) in.par = ch.pin + L.params(t.set);
+    }
+    if (t.mailbox || t.bulk) in.mail = (brov_result*)(ch.pin + L.records());
+    if (t.mailbox) in.mail_flag = (int32_t*)(ch.pin + L.seq_words());
+    in.mail_seq = ch.mail_seq;
+    in.reads_pinned = t.zerocopy && !t.behind_copies;
+    return in;
+}
+// Behind the launch of a zero-copy tick: the device copies every other entry point works on are refreshed BEHIND the kernel that has read the
+// pinned ones (copies_beside: next to it), on the copy stream -- neither the host (which waits for the kernel's end / the mailbox) nor the next
+// tick's kernel waits for them; whatever else touches those arrays is ordered behind ev_copy (order_behind_last, sync_last)
+static int enqueue_behind(brov_solver* s, const TickLayout& L, const TickPlan& t, int passed) {
+    TickChannel& ch = s->tick;
+    HIPCHK(hipEventRecord(ch.ev_tick, ch.stream));
+    HIPCHK(hipStreamWaitEvent(ch.copy_stream, t.copies_beside ? ch.ev_pre : ch.ev_tick, 0));
+    if (int rc = upload_inputs(s, L, t.set, passed, ch.copy_stream)) return rc;
+    ch.ev_copy = ch.ev_set[t.set];
+    HIPCHK(hipEventRecord(ch.ev_copy, ch.copy_stream));
+    ch.set_pending[t.set] = true;
+    ch.copy_mask = (ch.copies_pending && !t.behind_copies) ? (ch.copy_mask | passed) : passed;   // (arrays written by copies no kernel on the tick's stream is ordered behind yet)
+    ch.copies_pending = true;
+    return BROV_OK;
+}
+// The host's one wait: for the records in the pinned buffer (mailbox poll / the kernel's end / the stream with the copy back behind the
+// kernel), or, a preparation, for the inputs to have left it -- the preparation itself runs on, stream-ordered ahead of whatever follows
+static int wait_records(brov_solver* s, const TickLayout& L, const TickPlan& t, int rti_phase) {
+    TickChannel& ch = s->tick;
+    const size_t B = s->B;
+    if (t.mailbox) {
+        const volatile int32_t* pf = (const volatile int32_t*)(ch.pin + L.seq_words());
+        const int32_t seq = ch.mail_seq;
         size_t done = 0;
         for (unsigned long spin = 1; done < B; spin++) {
             while (done < B && pf[done] == seq) done++;
             if (done < B && (spin & 0x3ff) == 0) {
-                const hipError_t q = hipStreamQuery(st);
+                const hipError_t q = hipStreamQuery(ch.stream);
                 if (q == hipSuccess) {   // the launch is over: everything it wrote is visible
                     while (done < B && pf[done] == seq) done++;
                     if (done < B) { g_err = "brov_tick_host: the solve ended without delivering its records"; return BROV_ERR_HIP; }
@@ -1430,22 +1471,56 @@ extern "C" int brov_tick_host(brov_solver* s, const double* x0, const double* yr
         }
         std::atomic_thread_fence(std::memory_order_acquire);
     } else if (rti_phase == 1) {
-        HIPCHK(hipEventSynchronize(s->ev_up));   // the inputs have left the pinned buffer; the preparation itself runs on (stream-ordered ahead of
-        return BROV_OK;                          // whatever follows; no record: `res` is left alone)
+        HIPCHK(hipEventSynchronize(ch.ev_up));
     } else {
-        if (!bulk) HIPCHK(hipMemcpyAsync(pr, s->res, B * sizeof(brov_result), hipMemcpyDeviceToHost, st));
-        if (zerocopy) HIPCHK(hipEventSynchronize(s->ev_tick));
-        else HIPCHK(hipStreamSynchronize(st));
+        if (!t.bulk) HIPCHK(hipMemcpyAsync(ch.pin + L.records(), s->res, B * sizeof(brov_result), hipMemcpyDeviceToHost, ch.stream));
+        if (t.zerocopy) HIPCHK(hipEventSynchronize(ch.ev_tick));
+        else HIPCHK(hipStreamSynchronize(ch.stream));
     }
+    return BROV_OK;
+}
+
+extern "C" int brov_tick_host(brov_solver* s, const double* x0, const double* yref_shared, const double* par_stage, int rti_phase,
+                              brov_result* res) {
+    if (!s || rti_phase < 0 || rti_phase > 2) return BROV_ERR_ARG;
+    using clk = std::chrono::steady_clock;
+    const bool brk = s->k.tick_breakdown != 0;
+    clk::time_point tb0, tb1, tb2, tb3, tb4;
+    if (brk) tb0 = clk::now();
+    HIPCHK(hipSetDevice(s->device));
+    TickChannel& ch = s->tick;
+    const TickLayout L(s->B, s->N);
+    if (!ch.stream) HIPCHK(hipStreamCreateWithFlags(&ch.stream, hipStreamNonBlocking));
+    if (int rc = tick_pin(s)) return rc;
+    hipStream_t st = ch.stream;
+    if (s->last_stream != st) HIPCHK(sync_last(s));   // an earlier solve on the caller's stream
+    const int passed = (x0 ? 1 : 0) | (yref_shared ? 2 : 0) | (par_stage ? 4 : 0);
+    const bool in_place = (x0 && x0 == ch.pin + L.x0(0)) || (yref_shared && yref_shared == ch.pin + L.window(0)) || (par_stage && par_stage == ch.pin + L.params(0));
+    const TickPlan t = plan_tick(s->B, rti_phase, passed, in_place, s->k, ch.buffers_out, ch.copies_pending, ch.copy_mask, ch.pin_sel);
+    if (!in_place && !ch.buffers_out) ch.pin_sel = t.set;   // copying ticks alternate between the two input sets
+    if (int rc = stage_inputs(s, L, t.set, x0, yref_shared, par_stage)) return rc;
+    if (int rc = enqueue_ahead(s, L, t, passed, rti_phase)) return rc;
+    if (t.mailbox) ch.mail_seq = ch.mail_seq == 0x7fffffff ? 1 : ch.mail_seq + 1;
+    const LaunchInputs in = tick_launch_inputs(ch, L, t, passed);   // a local: no path out of this call leaves a later solve reading the pinned buffer
+    if (brk) tb1 = clk::now();
+    if (t.copies_beside) HIPCHK(hipEventRecord(ch.ev_pre, st));   // (ahead of the launch like enqueue_ahead, but on the launch's side of the breakdown)
+    const int rc = solve_phase(s, st, rti_phase, &in);
+    if (brk) tb2 = clk::now();
+    if (rc) return rc;
+    if (t.zerocopy) { if (int rc2 = enqueue_behind(s, L, t, passed)) return rc2; }
+    if (brk) tb3 = clk::now();
+    if (int rc2 = wait_records(s, L, t, rti_phase)) return rc2;
+    if (rti_phase == 1) return BROV_OK;   // (no record: `res` is left alone)
     if (brk) {
         tb4 = clk::now();
         auto us = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
-        s->tick_us[0] = us(tb0, tb1); s->tick_us[1] = us(tb1, tb2); s->tick_us[2] = us(tb2, tb3); s->tick_us[3] = us(tb3, tb4); s->tick_us[4] = us(tb0, tb4);
+        ch.tick_us[0] = us(tb0, tb1); ch.tick_us[1] = us(tb1, tb2); ch.tick_us[2] = us(tb2, tb3); ch.tick_us[3] = us(tb3, tb4); ch.tick_us[4] = us(tb0, tb4);
     }
-    if (res && res != (brov_result*)pr) std::memcpy(res, pr, B * sizeof(brov_result));
+    const brov_result* pr = (const brov_result*)(ch.pin + L.records());
+    if (res && res != pr) std::memcpy(res, pr, s->B * sizeof(brov_result));
     // a caller that builds its inputs IN the staging buffers (brov_tick_buffers) is free to write the next tick's as soon as this call is back:
     // the refresh copies out of them are over by then
-    if (zerocopy && in_place) HIPCHK(hipEventSynchronize(s->ev_copy));
+    if (t.zerocopy && in_place) HIPCHK(hipEventSynchronize(ch.ev_copy));
     return BROV_OK;
 }
 
@@ -1481,11 +1556,11 @@ extern "C" int brov_last_kernel_path(const brov_solver* s) {
 // which instances of the LAST solve were completed by the parallel-in-time kernel (rti_pit_kernel, batches the resident windowed mode
 // serves): done[b] = 1, else 0 -- all zero when that kernel did not run.  Test / bench instrumentation.
 // development (BROV_TICK_BREAKDOWN=1 at create): host time of the last brov_tick_host in microseconds -- [0] entry to launch (device selection,
-// staging: copies into the pinned buffer, waits for earlier refresh copies), [1] brov_solve_phase (parameter block, kernel launch(es)), [2] what is
+// staging: copies into the pinned buffer, waits for earlier refresh copies), [1] solve_phase (parameter block, kernel launch(es)), [2] what is
 // enqueued behind the launch (events, refresh copies), [3] the wait for the records (mailbox poll / event / stream), [4] the whole call
 extern "C" int brov_dev_tick_breakdown(brov_solver* s, double us[5]) {
     if (!s || !us) return BROV_ERR_ARG;
-    for (int k = 0; k < 5; k++) us[k] = s->tick_us[k];
+    for (int k = 0; k < 5; k++) us[k] = s->tick.tick_us[k];
     return BROV_OK;
 }
 extern "C" int brov_pit_last(brov_solver* s, int32_t* done) {
