@@ -9,10 +9,9 @@
 //   fleet_apply_kernel           the observer's estimate of vehicle v into p[0..3] of every stage of all its candidates
 //
 // fleet_select_kernel: one wavefront per vehicle, four vehicles per block.  Lane l scans candidates l, l + 64, ... in ascending order, the
-// wave folds (cost, index) pairs with shuffles; at every level the lower cost wins and on equal cost the lower index.  That is a total
-// order on the pairs, so the result does not depend on how the fold is cut: no atomics, no LDS, two calls return the same bytes.  Only
-// `cost` and `status` of a record are read (16 of its 104 bytes), then the winner's record once.  Eligible: status SUCCESS and a finite cost,
-// tested on the exponent bits as track_accumulate_kernel does (an ordering comparison is false for NaN on either side).
+// wave folds (cost, index) pairs with shuffles.  Who is eligible and who wins is the one rule of select_device.hpp (result_eligible,
+// argmin_fold, wave_argmin): no atomics, no LDS, two calls return the same bytes.  Only `cost` and `status` of a record are read (16 of its
+// 104 bytes), then the winner's record once.
 //
 // fleet_plant_kernel / fleet_plant_wrench_kernel: one lane per vehicle; where its input comes from and what it records is its own
 // (fleet_plant_vehicle), the step between is plant_erk4 (bluerov2_model.hpp), the function plant_kernel calls, without / with a WorldWrench.
@@ -21,21 +20,12 @@
 #include "fleet_kernel.hpp"
 #include "nmpc_device.hpp"
 #include "bluerov2_model.hpp"
-
-static_assert(sizeof(brov_result) == 104 && sizeof(brov_result) % 8 == 0, "brov_result is copied as 13 words of 8 bytes");
+#include "select_device.hpp"
 
 namespace brov {
 
 constexpr int kFleetSelectBlock = 256;
 constexpr int kFleetSelectWaves = kFleetSelectBlock / 64;
-constexpr int kResultWords = (int)(sizeof(brov_result) / 8);
-
-__device__ __forceinline__ bool fleet_finite(double v) { return (__double2hiint(v) & 0x7ff00000) != 0x7ff00000; }
-
-// (c, i) := the better of (c, i) and (c2, i2); i < 0: no candidate yet.  The lower cost, on equal cost the lower index.
-__device__ __forceinline__ void fleet_fold(double& c, int& i, double c2, int i2) {
-    if (i2 >= 0 && (i < 0 || c2 < c || (c2 == c && i2 < i))) { c = c2; i = i2; }
-}
 
 __global__ __launch_bounds__(kFleetSelectBlock) void fleet_select_kernel(const brov_result* __restrict__ rec, int V, int C,
                                                                          int32_t* __restrict__ winner, brov_result* __restrict__ winner_rec) {
@@ -48,20 +38,13 @@ __global__ __launch_bounds__(kFleetSelectBlock) void fleet_select_kernel(const b
     for (int c = lane; c < C; c += 64) {   // ascending: within a lane an equal cost never replaces an earlier index
         const double cost = g[c].cost;
         const int st = g[c].status;
-        if (st == BROV_STATUS_SUCCESS && fleet_finite(cost)) fleet_fold(best, bi, cost, c);
+        if (result_eligible(st, cost)) argmin_fold(best, bi, cost, c);
     }
-    // after the step with offset `off` the lanes below `off` hold the fold of their residue class
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const double c2 = __shfl_down(best, off, 64);
-        const int i2 = __shfl_down(bi, off, 64);
-        if (lane + off < 64) fleet_fold(best, bi, c2, i2);
-    }
+    wave_argmin(best, bi);
     bi = __shfl(bi, 0, 64);
     if (lane == 0) winner[v] = bi;
     if (winner_rec && lane < kResultWords) {   // the record as 13 words, one per lane; zeros without a winner
-        const unsigned long long* src = reinterpret_cast<const unsigned long long*>(g + (bi >= 0 ? bi : 0));
-        reinterpret_cast<unsigned long long*>(winner_rec + v)[lane] = bi >= 0 ? src[lane] : 0ULL;
+        result_word(winner_rec + v, lane) = bi >= 0 ? result_word(g + (bi >= 0 ? bi : 0), lane) : 0ULL;
     }
 }
 

@@ -45,6 +45,9 @@ typedef enum { ncclUint8 = 1, ncclDouble = 8 } ncclDataType_t;
 
 #include "../../include/bluerov2_nmpc.h"
 #include "host_common.hpp"
+#include "select_device.hpp"
+
+using namespace brov;
 
 static thread_local std::string g_gerr;
 extern "C" const char* brov_group_last_error(void) { return g_gerr.c_str(); }
@@ -119,26 +122,85 @@ struct DeviceKeeper {
 constexpr int kSelBlocks = 64;   // blocks of group_select_kernel
 struct GroupMail { brov_result rec; int32_t slot; int32_t seq; int32_t owner; int32_t pad; };   // what the select kernels deliver to the host (pinned), seq last
 
+#define HIPCHK(call) BROV_HIPCHK(g_gerr, call)
+#define GNCCL(call)                                                                         \
+    do {                                                                                    \
+        ncclResult_t r_ = (call);                                                           \
+        if (r_ != ncclSuccess) { g_gerr = std::string(#call) + ": " + rccl().GetErrorString(r_); return BROV_ERR_HIP; } \
+    } while (0)
+
+static int pinned_mail(GroupMail** m) {
+    if (hipHostMalloc((void**)m, sizeof(GroupMail), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); *m = nullptr; g_gerr = "brov_group_create: allocation of a pinned mailbox failed"; return BROV_ERR_ALLOC; }
+    std::memset(*m, 0, sizeof(GroupMail));
+    return BROV_OK;
+}
+
+// one rank of the group that lives in this process: a device, its shard of the batch and everything the gather and the select keep there
+struct GroupRank {
+    int dev = -1, rank = -1;              // device ordinal, GLOBAL rank
+    int lo = 0, cnt = 0;                  // its shard: instances [lo, lo + cnt) of the batch
+    brov_solver* sol = nullptr;
+    hipStream_t st = nullptr;
+    ncclComm_t comm = nullptr;
+    brov_result* stage = nullptr;         // [Bmax] (uneven shards only): the shard's records + never-selectable padding
+    brov_result* gathered = nullptr;      // [W * Bmax]
+    double *pair = nullptr, *pairs = nullptr;   // [2] local (cost, global index) and [W * 2] gathered
+    int* best = nullptr;                  // [2]: arg-min scratch (winning slot, ticket of the select kernel)
+    GroupMail* pmail = nullptr;           // pinned: the local winner's record, written by the pack kernel
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // solve start / end = gather start / gather end / select end
+    // local rank 0, where the select runs: partial results of the select kernel's blocks, the winning record, the pinned mailbox they deliver into
+    double* sel_cost = nullptr; int* sel_idx = nullptr; brov_result* sel_rec = nullptr;
+    GroupMail* mail = nullptr;
+    DeviceAllocs mem;
+
+    const brov_result* contribution(bool even) const { return even ? brov_results_device(sol) : stage; }   // what a BROV_GATHER_RECORDS gather takes from this rank: [Bmax] records
+
+    int create(int W, int Bmax, bool even, bool first, const brov_opts* opts) {
+        if (hipSetDevice(dev) != hipSuccess) { (void)hipGetLastError(); g_gerr = "brov_group_create: hipSetDevice failed"; return BROV_ERR_HIP; }
+        if (int rc = brov_create(&sol, dev, cnt, opts)) { g_gerr = std::string("brov_group_create: shard ") + std::to_string(rank) + ": " + brov_last_error(); return rc; }
+        HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        if (int rc = mem.alloc(&gathered, (size_t)W * Bmax, g_gerr)) return rc;
+        if (int rc = mem.alloc(&pair, 2 + 2 * (size_t)W, g_gerr)) return rc;
+        pairs = pair + 2;
+        if (int rc = mem.alloc(&best, 2, g_gerr)) return rc;
+        HIPCHK(hipMemset(best, 0, 2 * sizeof(int)));
+        if (int rc = pinned_mail(&pmail)) return rc;
+        if (first) {
+            if (int rc = mem.alloc(&sel_cost, kSelBlocks, g_gerr)) return rc;
+            if (int rc = mem.alloc(&sel_idx, kSelBlocks, g_gerr)) return rc;
+            if (int rc = mem.alloc(&sel_rec, 1, g_gerr)) return rc;
+            if (int rc = pinned_mail(&mail)) return rc;
+        }
+        if (!even) {
+            if (int rc = mem.alloc(&stage, (size_t)Bmax, g_gerr)) return rc;
+            // padding records: status -1, cost NaN -- never selectable; only the first cnt slots are ever rewritten
+            HIPCHK(hipMemset(stage, 0xFF, (size_t)Bmax * sizeof(brov_result)));
+        }
+        for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
+        return BROV_OK;
+    }
+    // safe on a rank that was built in part, or not at all
+    void destroy() {
+        if (dev >= 0) (void)hipSetDevice(dev);
+        if (comm && rccl().handle) rccl().CommDestroy(comm);
+        brov_destroy(sol);
+        mem.free_all();
+        if (pmail) (void)hipHostFree(pmail);
+        if (mail) (void)hipHostFree(mail);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+        if (st) (void)hipStreamDestroy(st);
+    }
+};
+
 struct brov_group {
-    // n = devices of THIS process; W = ranks of the whole group (= n for the one-process form; one process per GPU: n = 1, W = world),
-    // r0 = global rank of local device 0.  lo / cnt are indexed by GLOBAL rank; everything else by local device.
+    // n = ranks of THIS process, one per local device; W = ranks of the whole group (= n for the one-process form; one process per GPU: n = 1,
+    // W = world), r0 = global rank of local rank 0.  lo / cnt are indexed by GLOBAL rank; a local rank carries its own pair.
     int n = 0, W = 0, r0 = 0, total = 0, Bmax = 0;
     bool even = true;                     // all shards equally large: the records are gathered straight from the solvers' own arrays
-    std::vector<int> dev, lo, cnt;
-    std::vector<brov_solver*> sol;
-    std::vector<hipStream_t> st;
-    std::vector<ncclComm_t> comm;
-    std::vector<brov_result*> stage;      // [Bmax] per device (uneven shards only): the shard's records + never-selectable padding
-    std::vector<brov_result*> gathered;   // [n * Bmax] per device
-    std::vector<double*> pair, pairs;     // [2] local (cost, global index) and [n * 2] gathered, per device
-    std::vector<int*> best;               // [2] per device: arg-min scratch (winning slot, ticket of the select kernel)
-    double* sel_cost = nullptr;           // device 0: partial results of the select kernel's blocks, the winning record
-    int* sel_idx = nullptr;
-    brov_result* sel_rec = nullptr;
-    GroupMail* mail = nullptr;            // pinned host mailbox the select kernels deliver into (device 0)
-    std::vector<GroupMail*> pmail;        // per device (pinned): the local winner's record, written by the pack kernel
+    std::vector<int> lo, cnt;
+    std::vector<GroupRank> ranks;         // the select runs on ranks[0]
     int32_t mail_seq = 0;
-    std::vector<hipEvent_t> ev;           // 4 per device: solve start / end = gather start / gather end / select end
     int last_mode = -1;
     int collective = BROV_COLLECTIVE_RCCL;
     std::shared_ptr<CopyComm> cc;         // BROV_COLLECTIVE_COPY: the meeting point of the group's ranks
@@ -149,57 +211,35 @@ struct brov_group {
     bool ev_solve = false, ev_gather = false;   // ... the solve's pair, the gather's end
 };
 
-#define HIPCHK(call) BROV_HIPCHK(g_gerr, call)
-#define GNCCL(call)                                                                         \
-    do {                                                                                    \
-        ncclResult_t r_ = (call);                                                           \
-        if (r_ != ncclSuccess) { g_gerr = std::string(#call) + ": " + rccl().GetErrorString(r_); return BROV_ERR_HIP; } \
-    } while (0)
-
-// arg-min of cost over the successful records of a (padded) record array: slot -> (rank = slot / Bmax, i = slot % Bmax), valid while
-// i < cnt[rank]; ties go to the lowest slot = lowest global index.  Up to kSelBlocks blocks scan the array (65 536 records of 104 B at
-// BASELINE configs[3]: one block needs ~0.1 ms for them), the block that draws the last ticket reduces the partial results, and -- so
-// that the host needs no copy command and no second round trip for the winner -- writes the winning slot AND its record into a pinned
-// host mailbox, the sequence word last.  out[0] = winning slot or -1, best_dev = the record on the device.
-__device__ __forceinline__ bool sel_better(double c2, int i2, double c1, int i1) { return i2 >= 0 && (i1 < 0 || c2 < c1 || (c2 == c1 && i2 < i1)); }
+// arg-min of cost over the eligible records (select_device.hpp: status SUCCESS and a finite cost) of a (padded) record array: slot ->
+// (rank = slot / Bmax, i = slot % Bmax), valid while i < cnt[rank]; ties go to the lowest slot = lowest global index.  Up to kSelBlocks blocks
+// scan the array (65 536 records of 104 B at BASELINE configs[3]: one block needs ~0.1 ms for them), the block that draws the last ticket
+// reduces the partial results, and -- so that the host needs no copy command and no second round trip for the winner -- writes the winning
+// slot AND its record into a pinned host mailbox, the sequence word last.  out[0] = winning slot or -1, best_dev = the record on the device.
 __global__ __launch_bounds__(256) void group_select_kernel(const brov_result* __restrict__ rec, int slots, int* __restrict__ out, double* pc, int* pi,
                                                              unsigned* ticket, brov_result* best_dev, GroupMail* mail, int seq) {
-    __shared__ double sc[256];
-    __shared__ int si[256];
     __shared__ bool last;
-    double best = 1e300;
+    double best = 0.0;
     int bi = -1;
-    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < slots; k += gridDim.x * blockDim.x) {
-        const double c = rec[k].cost;
-        if (rec[k].status == BROV_STATUS_SUCCESS && c == c && (bi < 0 || c < best)) { best = c; bi = k; }
-    }
-    auto block_reduce = [&]() {
-        sc[threadIdx.x] = best; si[threadIdx.x] = bi;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if ((int)threadIdx.x < o && sel_better(sc[threadIdx.x + o], si[threadIdx.x + o], sc[threadIdx.x], si[threadIdx.x])) {
-                sc[threadIdx.x] = sc[threadIdx.x + o]; si[threadIdx.x] = si[threadIdx.x + o];
-            }
-            __syncthreads();
-        }
-    };
-    block_reduce();
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < slots; k += gridDim.x * blockDim.x)   // ascending within a thread
+        if (result_eligible(rec[k].status, rec[k].cost)) argmin_next(best, bi, rec[k].cost, k);
+    block_argmin<256>(best, bi);
     if (threadIdx.x == 0) {
-        pc[blockIdx.x] = sc[0]; pi[blockIdx.x] = si[0];
+        pc[blockIdx.x] = best; pi[blockIdx.x] = bi;
         __threadfence();
         last = atomicAdd(ticket, 1u) == gridDim.x - 1;
     }
     __syncthreads();
     if (!last) return;
     __threadfence();
-    best = 1e300; bi = -1;
+    bi = -1;
     if (threadIdx.x < gridDim.x) { best = ((volatile double*)pc)[threadIdx.x]; bi = ((volatile int*)pi)[threadIdx.x]; }
-    block_reduce();
-    const int slot = si[0];
-    if (slot >= 0 && threadIdx.x < sizeof(brov_result) / 8) {
-        const double v = ((const double*)(rec + slot))[threadIdx.x];
-        ((double*)best_dev)[threadIdx.x] = v;
-        if (mail) ((double*)&mail->rec)[threadIdx.x] = v;
+    block_argmin<256>(best, bi);
+    const int slot = bi;
+    if (slot >= 0 && threadIdx.x < kResultWords) {
+        const unsigned long long v = result_word(rec + slot, threadIdx.x);
+        result_word(best_dev, threadIdx.x) = v;
+        if (mail) result_word(&mail->rec, threadIdx.x) = v;
     }
     __threadfence_system();
     __syncthreads();
@@ -216,36 +256,25 @@ __global__ __launch_bounds__(256) void group_select_kernel(const brov_result* __
 // the local arg-min as a packed pair: pair[0] = cost (+inf when no record qualifies), pair[1] = global index (exact in a double).  The
 // winner's whole record goes into the device's own pinned mailbox on the way (system-scope fence ahead of the pair: whoever learns the
 // pair through the all-gather finds the record in place).
-__global__ void group_pack_kernel(const brov_result* __restrict__ rec, int n, int lo, double* __restrict__ pair, GroupMail* mail) {
-    __shared__ double sc[256];
-    __shared__ int si[256];
-    double best = 1e300;
-    int bi = -1;
-    for (int k = threadIdx.x; k < n; k += blockDim.x) {
-        const double c = rec[k].cost;
-        if (rec[k].status == BROV_STATUS_SUCCESS && c == c && (bi < 0 || c < best)) { best = c; bi = k; }
-    }
-    sc[threadIdx.x] = best; si[threadIdx.x] = bi;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o && sel_better(sc[threadIdx.x + o], si[threadIdx.x + o], sc[threadIdx.x], si[threadIdx.x])) {
-            sc[threadIdx.x] = sc[threadIdx.x + o]; si[threadIdx.x] = si[threadIdx.x + o];
-        }
-        __syncthreads();
-    }
-    const int w = si[0];
-    if (w >= 0 && threadIdx.x < sizeof(brov_result) / 8) ((double*)&mail->rec)[threadIdx.x] = ((const double*)(rec + w))[threadIdx.x];
+__global__ __launch_bounds__(256) void group_pack_kernel(const brov_result* __restrict__ rec, int n, int lo, double* __restrict__ pair, GroupMail* mail) {
+    double best = 0.0;
+    int w = -1;
+    for (int k = threadIdx.x; k < n; k += blockDim.x)   // ascending within a thread
+        if (result_eligible(rec[k].status, rec[k].cost)) argmin_next(best, w, rec[k].cost, k);
+    block_argmin<256>(best, w);
+    if (w >= 0 && threadIdx.x < kResultWords) result_word(&mail->rec, threadIdx.x) = result_word(rec + w, threadIdx.x);
     __threadfence_system();
     __syncthreads();
     if (threadIdx.x == 0) {
         mail->slot = w >= 0 ? lo + w : -1;
         __threadfence_system();
-        pair[0] = w >= 0 ? sc[0] : __builtin_inf();
+        pair[0] = w >= 0 ? best : __builtin_inf();
         pair[1] = w >= 0 ? (double)(lo + w) : -1.0;
     }
 }
 // the gathered pairs -> owner rank, global index and cost of the global winner, into the host mailbox (one wave; shards hold ascending
-// index ranges, so the first minimal cost in rank order is the lowest index)
+// index ranges, so the first minimal cost in rank order is the lowest index).  A pair is no record: its +inf cost with index -1 says "no
+// winner on that rank", and every other pair carries the finite cost of an eligible record.
 __global__ void group_pairs_kernel(const double* __restrict__ pairs, int W, GroupMail* mail, int seq) {
     if (threadIdx.x != 0) return;
     int owner = -1;
@@ -256,6 +285,39 @@ __global__ void group_pairs_kernel(const double* __restrict__ pairs, int W, Grou
     mail->rec.cost = owner >= 0 ? pairs[2 * owner] : 0.0;
     __threadfence_system();
     *(volatile int32_t*)&mail->seq = seq;
+}
+
+// poll the sequence word of rank 0's mailbox; the stream is queried now and then, so that a launch that ended without delivering (a
+// device fault) turns into an error instead of a hang
+static int mail_wait(GroupRank& r0, int32_t seq) {
+    volatile int32_t* pf = (volatile int32_t*)&r0.mail->seq;
+    for (unsigned long spin = 1; *pf != seq; spin++) {
+        if ((spin & 0x3ff) == 0) {
+            const hipError_t q = hipStreamQuery(r0.st);
+            if (q == hipSuccess) {   // the launch is over: everything it wrote is visible
+                if (*pf != seq) { g_gerr = "brov_group_select_best: the select kernel ended without delivering"; return BROV_ERR_HIP; }
+            } else if (q != hipErrorNotReady) {
+                g_gerr = std::string("brov_group_select_best: ") + hipGetErrorString(q);
+                (void)hipGetLastError();
+                return BROV_ERR_HIP;
+            }
+        }
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    return BROV_OK;
+}
+
+// one delivery through rank 0's pinned mailbox: the next sequence number, `launch(rank 0, number)` enqueues the kernel that writes the mailbox
+// and the number last, the select-end event, and the host polls the sequence word: no copy command, no stream synchronisation on the way back
+template <class Launch>
+static int deliver(brov_group* g, Launch launch) {
+    GroupRank& r0 = g->ranks[0];
+    HIPCHK(hipSetDevice(r0.dev));
+    g->mail_seq = g->mail_seq == 0x7fffffff ? 1 : g->mail_seq + 1;
+    launch(r0, g->mail_seq);
+    HIPCHK(hipGetLastError());
+    if (g->timing) { HIPCHK(hipEventRecord(r0.ev[3], r0.st)); g->ev_sel = true; }
+    return mail_wait(r0, g->mail_seq);
 }
 
 extern "C" {
@@ -272,17 +334,16 @@ int brov_group_rccl_version(int* version) {
 void brov_group_destroy(brov_group* g) {
     if (!g) return;
     DeviceKeeper keep;
-    for (int d = 0; d < g->n; d++) {   // everything this process's ranks have enqueued is over before anything is taken apart
-        if (d < (int)g->dev.size()) hipSetDevice(g->dev[d]);
-        if (d < (int)g->st.size() && g->st[d]) hipStreamSynchronize(g->st[d]);
+    for (GroupRank& r : g->ranks) {   // everything this process's ranks have enqueued is over before anything is taken apart
+        if (r.dev >= 0) hipSetDevice(r.dev);
+        if (r.st) hipStreamSynchronize(r.st);
     }
     if (g->cc) {   // leave the copy collective's table (the other ranks must have finished the gathers they share with this one)
         {
             std::lock_guard<std::mutex> lk(g->cc->m);
-            for (int d = 0; d < g->n; d++) {
-                const int q = g->r0 + d;
-                if (q >= (int)g->cc->peer.size() || !g->cc->peer[q].present || g->cc->peer[q].src_pair != (d < (int)g->pair.size() ? g->pair[d] : nullptr)) continue;
-                CopyPeer& me = g->cc->peer[q];
+            for (GroupRank& r : g->ranks) {
+                if (r.rank >= (int)g->cc->peer.size() || !g->cc->peer[r.rank].present || g->cc->peer[r.rank].src_pair != r.pair) continue;   // not this rank's entry
+                CopyPeer& me = g->cc->peer[r.rank];
                 if (me.ready) hipEventDestroy(me.ready);
                 if (me.pulled) hipEventDestroy(me.pulled);
                 me = CopyPeer();
@@ -294,25 +355,7 @@ void brov_group_destroy(brov_group* g) {
         if (it != g_copy.end() && it->second == g->cc && g->cc->joined <= 0) g_copy.erase(it);
         g->cc.reset();
     }
-    for (int d = 0; d < g->n; d++) {
-        if (d < (int)g->dev.size()) hipSetDevice(g->dev[d]);
-        if (d < (int)g->comm.size() && g->comm[d] && rccl().handle) rccl().CommDestroy(g->comm[d]);
-        if (d < (int)g->sol.size()) brov_destroy(g->sol[d]);
-        if (d < (int)g->stage.size() && g->stage[d]) hipFree(g->stage[d]);
-        if (d < (int)g->gathered.size() && g->gathered[d]) hipFree(g->gathered[d]);
-        if (d < (int)g->pair.size() && g->pair[d]) hipFree(g->pair[d]);
-        if (d < (int)g->best.size() && g->best[d]) hipFree(g->best[d]);
-        if (d < (int)g->pmail.size() && g->pmail[d]) hipHostFree(g->pmail[d]);
-        if (d == 0) {
-            if (g->sel_cost) hipFree(g->sel_cost);
-            if (g->sel_idx) hipFree(g->sel_idx);
-            if (g->sel_rec) hipFree(g->sel_rec);
-            if (g->mail) hipHostFree(g->mail);
-        }
-        for (int k = 0; k < 4; k++)
-            if (4 * d + k < (int)g->ev.size() && g->ev[4 * d + k]) hipEventDestroy(g->ev[4 * d + k]);
-        if (d < (int)g->st.size() && g->st[d]) hipStreamDestroy(g->st[d]);
-    }
+    for (GroupRank& r : g->ranks) r.destroy();
     delete g;
 }
 
@@ -334,45 +377,19 @@ static int group_build(brov_group** out, const int* devices, int n, int W, int r
     if (Rp && !Rp->handle) { g_gerr = "brov_group_create: " + Rp->why; return BROV_ERR_HIP; }
     brov_group* g = new brov_group();
     g->n = n; g->W = W; g->r0 = r0; g->collective = collective;
-    g->dev.assign(devices, devices + n);
     g->cnt = cnt; g->lo.assign(W, 0);
-    g->even = true;
     for (int r = 0; r < W; r++) {
         g->lo[r] = r ? g->lo[r - 1] + g->cnt[r - 1] : 0;
         if (g->cnt[r] > g->Bmax) g->Bmax = g->cnt[r];
         g->even = g->even && g->cnt[r] == g->cnt[0];
     }
     g->total = g->lo[W - 1] + g->cnt[W - 1];
-    g->sol.assign(n, nullptr); g->st.assign(n, nullptr); g->comm.assign(n, nullptr);
-    g->stage.assign(n, nullptr); g->gathered.assign(n, nullptr); g->pair.assign(n, nullptr); g->pairs.assign(n, nullptr);
-    g->best.assign(n, nullptr); g->ev.assign(4 * (size_t)n, nullptr); g->pmail.assign(n, nullptr);
+    g->ranks.resize(n);
     auto fail = [&](int rc) { brov_group_destroy(g); return rc; };
     for (int d = 0; d < n; d++) {
-        if (hipSetDevice(g->dev[d]) != hipSuccess) { g_gerr = "brov_group_create: hipSetDevice failed"; return fail(BROV_ERR_HIP); }
-        const int rc = brov_create(&g->sol[d], g->dev[d], g->cnt[r0 + d], opts);
-        if (rc != BROV_OK) { g_gerr = std::string("brov_group_create: shard ") + std::to_string(r0 + d) + ": " + brov_last_error(); return fail(rc); }
-        bool ok = hipStreamCreateWithFlags(&g->st[d], hipStreamNonBlocking) == hipSuccess;
-        ok = ok && hipMalloc((void**)&g->gathered[d], (size_t)W * g->Bmax * sizeof(brov_result)) == hipSuccess;
-        ok = ok && hipMalloc((void**)&g->pair[d], (2 + 2 * (size_t)W) * sizeof(double)) == hipSuccess;
-        ok = ok && hipMalloc((void**)&g->best[d], 2 * sizeof(int)) == hipSuccess;
-        ok = ok && hipMemset(g->best[d], 0, 2 * sizeof(int)) == hipSuccess;
-        ok = ok && hipHostMalloc((void**)&g->pmail[d], sizeof(GroupMail), hipHostMallocDefault) == hipSuccess;
-        if (ok) std::memset(g->pmail[d], 0, sizeof(GroupMail));
-        if (ok && d == 0) {   // the select runs on local device 0
-            ok = hipMalloc((void**)&g->sel_cost, kSelBlocks * sizeof(double)) == hipSuccess;
-            ok = ok && hipMalloc((void**)&g->sel_idx, kSelBlocks * sizeof(int)) == hipSuccess;
-            ok = ok && hipMalloc((void**)&g->sel_rec, sizeof(brov_result)) == hipSuccess;
-            ok = ok && hipHostMalloc((void**)&g->mail, sizeof(GroupMail), hipHostMallocDefault) == hipSuccess;
-            if (ok) std::memset(g->mail, 0, sizeof(GroupMail));
-        }
-        if (ok && !g->even) {
-            ok = hipMalloc((void**)&g->stage[d], (size_t)g->Bmax * sizeof(brov_result)) == hipSuccess;
-            // padding records: status -1, cost NaN -- never selectable; only the first cnt slots are ever rewritten
-            ok = ok && hipMemset(g->stage[d], 0xFF, (size_t)g->Bmax * sizeof(brov_result)) == hipSuccess;
-        }
-        for (int k = 0; k < 4 && ok; k++) ok = hipEventCreate(&g->ev[4 * d + k]) == hipSuccess;
-        if (!ok) { g_gerr = "brov_group_create: allocation of the gather buffers failed"; return fail(BROV_ERR_ALLOC); }
-        g->pairs[d] = g->pair[d] + 2;
+        GroupRank& r = g->ranks[d];
+        r.dev = devices[d]; r.rank = r0 + d; r.lo = g->lo[r.rank]; r.cnt = g->cnt[r.rank];
+        if (int rc = r.create(W, g->Bmax, g->even, d == 0, opts)) return fail(rc);
     }
     if (copy) {   // join the table entry of this group's id (the one-process form has an id of its own)
         g->cc_key = id ? std::string(id->internal, sizeof(id->internal)) : "one-process group " + std::to_string((unsigned long long)(uintptr_t)g);
@@ -384,14 +401,14 @@ static int group_build(brov_group** out, const int* devices, int n, int W, int r
         }
         std::unique_lock<std::mutex> lk(g->cc->m);
         if ((int)g->cc->peer.size() != W) { lk.unlock(); g_gerr = "brov_group_create_rank: the ranks of this id disagree about the world size"; return fail(BROV_ERR_ARG); }
-        for (int d = 0; d < n; d++)
-            if (g->cc->peer[r0 + d].present) { lk.unlock(); g_gerr = "brov_group_create_rank: rank " + std::to_string(r0 + d) + " of this id exists already"; return fail(BROV_ERR_ARG); }
-        for (int d = 0; d < n; d++) {
-            CopyPeer& me = g->cc->peer[r0 + d];
-            me.dev = g->dev[d];
-            me.src_rec = g->even ? brov_results_device(g->sol[d]) : g->stage[d];
-            me.src_pair = g->pair[d];
-            bool ok = hipSetDevice(g->dev[d]) == hipSuccess;
+        for (GroupRank& r : g->ranks)
+            if (g->cc->peer[r.rank].present) { lk.unlock(); g_gerr = "brov_group_create_rank: rank " + std::to_string(r.rank) + " of this id exists already"; return fail(BROV_ERR_ARG); }
+        for (GroupRank& r : g->ranks) {
+            CopyPeer& me = g->cc->peer[r.rank];
+            me.dev = r.dev;
+            me.src_rec = r.contribution(g->even);
+            me.src_pair = r.pair;
+            bool ok = hipSetDevice(r.dev) == hipSuccess;
             ok = ok && hipEventCreateWithFlags(&me.ready, hipEventDisableTiming) == hipSuccess;
             ok = ok && hipEventCreateWithFlags(&me.pulled, hipEventDisableTiming) == hipSuccess;
             if (!ok) { lk.unlock(); g_gerr = "brov_group_create: events of the copy collective"; return fail(BROV_ERR_HIP); }
@@ -403,10 +420,12 @@ static int group_build(brov_group** out, const int* devices, int n, int W, int r
         Rccl& R = *Rp;
         ncclResult_t nr;
         if (id) {   // one process per GPU: this process is rank r0 of W
-            if (hipSetDevice(g->dev[0]) != hipSuccess) { g_gerr = "brov_group_create_rank: hipSetDevice failed"; return fail(BROV_ERR_HIP); }
-            nr = R.CommInitRank(&g->comm[0], W, *id, r0);
+            if (hipSetDevice(g->ranks[0].dev) != hipSuccess) { g_gerr = "brov_group_create_rank: hipSetDevice failed"; return fail(BROV_ERR_HIP); }
+            nr = R.CommInitRank(&g->ranks[0].comm, W, *id, r0);
         } else {
-            nr = R.CommInitAll(g->comm.data(), n, g->dev.data());
+            std::vector<ncclComm_t> comm(n, nullptr);
+            nr = R.CommInitAll(comm.data(), n, devices);
+            for (int d = 0; d < n; d++) g->ranks[d].comm = comm[d];
         }
         if (nr != ncclSuccess) { g_gerr = std::string("brov_group_create: RCCL communicator set-up: ") + R.GetErrorString(nr); return fail(BROV_ERR_HIP); }
     }
@@ -453,8 +472,8 @@ int brov_group_size(const brov_group* g) { return g ? g->n : 0; }          /* de
 int brov_group_world(const brov_group* g) { return g ? g->W : 0; }         /* ranks of the whole group */
 int brov_group_first_rank(const brov_group* g) { return g ? g->r0 : 0; }
 int brov_group_total(const brov_group* g) { return g ? g->total : 0; }
-brov_solver* brov_group_solver(brov_group* g, int rank) { return (g && rank >= 0 && rank < g->n) ? g->sol[rank] : nullptr; }
-void* brov_group_stream(brov_group* g, int rank) { return (g && rank >= 0 && rank < g->n) ? (void*)g->st[rank] : nullptr; }
+brov_solver* brov_group_solver(brov_group* g, int rank) { return (g && rank >= 0 && rank < g->n) ? g->ranks[rank].sol : nullptr; }
+void* brov_group_stream(brov_group* g, int rank) { return (g && rank >= 0 && rank < g->n) ? (void*)g->ranks[rank].st : nullptr; }
 int brov_group_shard(const brov_group* g, int rank, int* lo, int* hi) {
     if (!g || rank < 0 || rank >= g->W) return BROV_ERR_ARG;   /* GLOBAL rank */
     if (lo) *lo = g->lo[rank];
@@ -466,42 +485,55 @@ int brov_group_shard(const brov_group* g, int rank, int* lo, int* hi) {
 int brov_group_set_x0_host(brov_group* g, const double* x0) {
     if (!g || !x0) return BROV_ERR_ARG;
     DeviceKeeper keep;
-    for (int d = 0; d < g->n; d++)
-        if (int rc = brov_set_x0_host(g->sol[d], x0 + (size_t)g->lo[g->r0 + d] * 12)) { g_gerr = brov_last_error(); return rc; }
+    for (GroupRank& r : g->ranks)
+        if (int rc = brov_set_x0_host(r.sol, x0 + (size_t)r.lo * 12)) { g_gerr = brov_last_error(); return rc; }
     return BROV_OK;
 }
 int brov_group_set_params_host(brov_group* g, const double* p, int per_stage) {
     if (!g || !p) return BROV_ERR_ARG;
     DeviceKeeper keep;
-    const size_t row = per_stage ? (size_t)(brov_horizon(g->sol[0]) + 1) * 16 : 16;
-    for (int d = 0; d < g->n; d++)
-        if (int rc = brov_set_params_host(g->sol[d], p + (size_t)g->lo[g->r0 + d] * row, per_stage)) { g_gerr = brov_last_error(); return rc; }
+    const size_t row = per_stage ? (size_t)(brov_horizon(g->ranks[0].sol) + 1) * 16 : 16;
+    for (GroupRank& r : g->ranks)
+        if (int rc = brov_set_params_host(r.sol, p + (size_t)r.lo * row, per_stage)) { g_gerr = brov_last_error(); return rc; }
     return BROV_OK;
 }
 int brov_group_set_yref_host(brov_group* g, const double* yref, int shared) {
     if (!g || !yref) return BROV_ERR_ARG;
     DeviceKeeper keep;
-    const size_t row = (size_t)(brov_horizon(g->sol[0]) + 1) * 16;
-    for (int d = 0; d < g->n; d++)
-        if (int rc = brov_set_yref_host(g->sol[d], shared ? yref : yref + (size_t)g->lo[g->r0 + d] * row, shared)) { g_gerr = brov_last_error(); return rc; }
+    const size_t row = (size_t)(brov_horizon(g->ranks[0].sol) + 1) * 16;
+    for (GroupRank& r : g->ranks)
+        if (int rc = brov_set_yref_host(r.sol, shared ? yref : yref + (size_t)r.lo * row, shared)) { g_gerr = brov_last_error(); return rc; }
     return BROV_OK;
 }
 int brov_group_set_candidate_params_host(brov_group* g, int kind, const double* p0, const double* p1, const double* phase) {
     if (!g || !p0 || !p1 || !phase) return BROV_ERR_ARG;
     DeviceKeeper keep;
-    for (int d = 0; d < g->n; d++)
-        if (int rc = brov_set_candidate_params_host(g->sol[d], kind, p0 + g->lo[g->r0 + d], p1 + g->lo[g->r0 + d], phase + g->lo[g->r0 + d])) { g_gerr = brov_last_error(); return rc; }
+    for (GroupRank& r : g->ranks)
+        if (int rc = brov_set_candidate_params_host(r.sol, kind, p0 + r.lo, p1 + r.lo, phase + r.lo)) { g_gerr = brov_last_error(); return rc; }
     return BROV_OK;
 }
 int brov_group_set_yref_candidates(brov_group* g, double t0, double dt) {   // one window kernel per device, on the device's stream
     if (!g) return BROV_ERR_ARG;
     DeviceKeeper keep;
-    for (int d = 0; d < g->n; d++)
-        if (int rc = brov_set_yref_candidates(g->sol[d], t0, dt, g->st[d])) { g_gerr = brov_last_error(); return rc; }
+    for (GroupRank& r : g->ranks)
+        if (int rc = brov_set_yref_candidates(r.sol, t0, dt, r.st)) { g_gerr = brov_last_error(); return rc; }
     return BROV_OK;
 }
 
 int brov_group_enable_timing(brov_group* g, int on) { if (!g) return BROV_ERR_ARG; g->timing = on != 0; return BROV_OK; }
+
+// BROV_COLLECTIVE_COPY, with c.m held: wait until every rank of the group is present and its counter `member` (entered / done) has reached
+// `round`.  A rank that does not get there within the collective's time limit is named in the error, not waited for forever.
+static int wait_for_ranks(CopyComm& c, std::unique_lock<std::mutex>& lk, long round, long CopyPeer::*member, const char* what) {
+    int missing = -1;
+    const bool ok = c.cv.wait_for(lk, std::chrono::seconds(kCopyWaitSeconds.load()), [&] {
+        for (int r = 0; r < (int)c.peer.size(); r++)
+            if (!c.peer[r].present || c.peer[r].*member < round) { missing = r; return false; }
+        return true;
+    });
+    if (!ok) { g_gerr = "copy collective: rank " + std::to_string(missing) + what + std::to_string(round); return BROV_ERR_HIP; }
+    return BROV_OK;
+}
 
 // BROV_COLLECTIVE_COPY: before a rank rewrites what it contributed to the last gather (its records: the next solve; its staging copy /
 // its pair: the next gather), every rank has pulled it -- waited for on the host until the pulls are enqueued, on the streams until
@@ -511,18 +543,12 @@ static int copy_fence(brov_group* g) {
     CopyComm& c = *g->cc;
     {
         std::unique_lock<std::mutex> lk(c.m);
-        int missing = -1;
-        const bool ok = c.cv.wait_for(lk, std::chrono::seconds(kCopyWaitSeconds.load()), [&] {
-            for (int r = 0; r < g->W; r++)
-                if (!c.peer[r].present || c.peer[r].done < g->round) { missing = r; return false; }
-            return true;
-        });
-        if (!ok) { g_gerr = "copy collective: rank " + std::to_string(missing) + " has not finished gather " + std::to_string(g->round); return BROV_ERR_HIP; }
+        if (int rc = wait_for_ranks(c, lk, g->round, &CopyPeer::done, " has not finished gather ")) return rc;
     }
-    for (int d = 0; d < g->n; d++) {
-        HIPCHK(hipSetDevice(g->dev[d]));
+    for (GroupRank& me : g->ranks) {
+        HIPCHK(hipSetDevice(me.dev));
         for (int r = 0; r < g->W; r++)
-            if (r != g->r0 + d) HIPCHK(hipStreamWaitEvent(g->st[d], c.peer[r].pulled, 0));
+            if (r != me.rank) HIPCHK(hipStreamWaitEvent(me.st, c.peer[r].pulled, 0));
     }
     return BROV_OK;
 }
@@ -532,39 +558,33 @@ static int copy_gather(brov_group* g, int mode) {
     CopyComm& c = *g->cc;
     const size_t rec = sizeof(brov_result);
     const long round = ++g->round;
-    for (int d = 0; d < g->n; d++) {
-        HIPCHK(hipSetDevice(g->dev[d]));
-        HIPCHK(hipEventRecord(c.peer[g->r0 + d].ready, g->st[d]));
+    for (GroupRank& me : g->ranks) {
+        HIPCHK(hipSetDevice(me.dev));
+        HIPCHK(hipEventRecord(c.peer[me.rank].ready, me.st));
     }
     {
         std::unique_lock<std::mutex> lk(c.m);
-        for (int d = 0; d < g->n; d++) { c.peer[g->r0 + d].entered = round; c.peer[g->r0 + d].mode = mode; }
+        for (GroupRank& me : g->ranks) { c.peer[me.rank].entered = round; c.peer[me.rank].mode = mode; }
         c.cv.notify_all();
         // every rank has entered this gather: what a collective waits for on the device is waited for on the host here
-        int missing = -1;
-        const bool ok = c.cv.wait_for(lk, std::chrono::seconds(kCopyWaitSeconds.load()), [&] {
-            for (int r = 0; r < g->W; r++)
-                if (!c.peer[r].present || c.peer[r].entered < round) { missing = r; return false; }
-            return true;
-        });
-        if (!ok) { g_gerr = "copy collective: rank " + std::to_string(missing) + " did not enter gather " + std::to_string(round); return BROV_ERR_HIP; }
+        if (int rc = wait_for_ranks(c, lk, round, &CopyPeer::entered, " did not enter gather ")) return rc;
         for (int r = 0; r < g->W; r++)
             if (c.peer[r].entered == round && c.peer[r].mode != mode) { g_gerr = "copy collective: the ranks disagree about the gather mode"; return BROV_ERR_ARG; }
     }
-    for (int d = 0; d < g->n; d++) {
-        HIPCHK(hipSetDevice(g->dev[d]));
+    for (GroupRank& me : g->ranks) {
+        HIPCHK(hipSetDevice(me.dev));
         for (int r = 0; r < g->W; r++) {
-            if (r != g->r0 + d) HIPCHK(hipStreamWaitEvent(g->st[d], c.peer[r].ready, 0));
+            if (r != me.rank) HIPCHK(hipStreamWaitEvent(me.st, c.peer[r].ready, 0));
             if (mode == BROV_GATHER_RECORDS)
-                HIPCHK(hipMemcpyAsync(g->gathered[d] + (size_t)r * g->Bmax, c.peer[r].src_rec, (size_t)g->Bmax * rec, hipMemcpyDefault, g->st[d]));
+                HIPCHK(hipMemcpyAsync(me.gathered + (size_t)r * g->Bmax, c.peer[r].src_rec, (size_t)g->Bmax * rec, hipMemcpyDefault, me.st));
             else
-                HIPCHK(hipMemcpyAsync(g->pairs[d] + 2 * r, c.peer[r].src_pair, 2 * sizeof(double), hipMemcpyDefault, g->st[d]));
+                HIPCHK(hipMemcpyAsync(me.pairs + 2 * r, c.peer[r].src_pair, 2 * sizeof(double), hipMemcpyDefault, me.st));
         }
-        HIPCHK(hipEventRecord(c.peer[g->r0 + d].pulled, g->st[d]));
+        HIPCHK(hipEventRecord(c.peer[me.rank].pulled, me.st));
     }
     {
         std::lock_guard<std::mutex> lk(c.m);
-        for (int d = 0; d < g->n; d++) c.peer[g->r0 + d].done = round;
+        for (GroupRank& me : g->ranks) c.peer[me.rank].done = round;
         c.cv.notify_all();
     }
     return BROV_OK;
@@ -574,11 +594,11 @@ int brov_group_solve(brov_group* g) {
     if (!g) return BROV_ERR_ARG;
     DeviceKeeper keep;
     if (int rc = copy_fence(g)) return rc;
-    for (int d = 0; d < g->n; d++) {
-        HIPCHK(hipSetDevice(g->dev[d]));
-        if (g->timing) HIPCHK(hipEventRecord(g->ev[4 * d + 0], g->st[d]));
-        if (int rc = brov_solve(g->sol[d], g->st[d])) { g_gerr = brov_last_error(); return rc; }
-        if (g->timing) HIPCHK(hipEventRecord(g->ev[4 * d + 1], g->st[d]));
+    for (GroupRank& r : g->ranks) {
+        HIPCHK(hipSetDevice(r.dev));
+        if (g->timing) HIPCHK(hipEventRecord(r.ev[0], r.st));
+        if (int rc = brov_solve(r.sol, r.st)) { g_gerr = brov_last_error(); return rc; }
+        if (g->timing) HIPCHK(hipEventRecord(r.ev[1], r.st));
     }
     g->last_mode = -1;
     g->ev_sel = false; g->ev_gather = false; g->ev_solve = g->timing;
@@ -590,14 +610,14 @@ int brov_group_gather(brov_group* g, int mode) {
     DeviceKeeper keep;
     const size_t rec = sizeof(brov_result);
     if (int rc = copy_fence(g)) return rc;
-    // what each device contributes, produced on its own stream behind the solve
-    for (int d = 0; d < g->n; d++) {
-        HIPCHK(hipSetDevice(g->dev[d]));
+    // what each rank contributes, produced on its own stream behind the solve
+    for (GroupRank& r : g->ranks) {
+        HIPCHK(hipSetDevice(r.dev));
         // (timing: the solve's end event doubles as the gather's start)
         if (mode == BROV_GATHER_RECORDS) {
-            if (!g->even) HIPCHK(hipMemcpyAsync(g->stage[d], brov_results_device(g->sol[d]), (size_t)g->cnt[g->r0 + d] * rec, hipMemcpyDeviceToDevice, g->st[d]));
+            if (!g->even) HIPCHK(hipMemcpyAsync(r.stage, brov_results_device(r.sol), (size_t)r.cnt * rec, hipMemcpyDeviceToDevice, r.st));
         } else {
-            hipLaunchKernelGGL(group_pack_kernel, dim3(1), dim3(256), 0, g->st[d], brov_results_device(g->sol[d]), g->cnt[g->r0 + d], g->lo[g->r0 + d], g->pair[d], g->pmail[d]);
+            hipLaunchKernelGGL(group_pack_kernel, dim3(1), dim3(256), 0, r.st, brov_results_device(r.sol), r.cnt, r.lo, r.pair, r.pmail);
             HIPCHK(hipGetLastError());
         }
     }
@@ -606,20 +626,15 @@ int brov_group_gather(brov_group* g, int mode) {
     } else {
         Rccl& R = rccl();
         GNCCL(R.GroupStart());
-        for (int d = 0; d < g->n; d++) {
-            ncclResult_t r;
-            if (mode == BROV_GATHER_RECORDS) {
-                const void* src = g->even ? (const void*)brov_results_device(g->sol[d]) : (const void*)g->stage[d];
-                r = R.AllGather(src, g->gathered[d], (size_t)g->Bmax * rec, ncclUint8, g->comm[d], g->st[d]);
-            } else {
-                r = R.AllGather(g->pair[d], g->pairs[d], 2, ncclDouble, g->comm[d], g->st[d]);
-            }
-            if (r != ncclSuccess) { R.GroupEnd(); g_gerr = std::string("ncclAllGather: ") + R.GetErrorString(r); return BROV_ERR_HIP; }
+        for (GroupRank& r : g->ranks) {
+            const ncclResult_t nr = mode == BROV_GATHER_RECORDS ? R.AllGather(r.contribution(g->even), r.gathered, (size_t)g->Bmax * rec, ncclUint8, r.comm, r.st)
+                                                                : R.AllGather(r.pair, r.pairs, 2, ncclDouble, r.comm, r.st);
+            if (nr != ncclSuccess) { R.GroupEnd(); g_gerr = std::string("ncclAllGather: ") + R.GetErrorString(nr); return BROV_ERR_HIP; }
         }
         GNCCL(R.GroupEnd());
     }
     if (g->timing)
-        for (int d = 0; d < g->n; d++) { HIPCHK(hipSetDevice(g->dev[d])); HIPCHK(hipEventRecord(g->ev[4 * d + 2], g->st[d])); }
+        for (GroupRank& r : g->ranks) { HIPCHK(hipSetDevice(r.dev)); HIPCHK(hipEventRecord(r.ev[2], r.st)); }
     g->ev_gather = g->timing && g->ev_solve;
     g->last_mode = mode;
     return BROV_OK;
@@ -628,7 +643,7 @@ int brov_group_gather(brov_group* g, int mode) {
 int brov_group_synchronize(brov_group* g) {
     if (!g) return BROV_ERR_ARG;
     DeviceKeeper keep;
-    for (int d = 0; d < g->n; d++) { HIPCHK(hipSetDevice(g->dev[d])); HIPCHK(hipStreamSynchronize(g->st[d])); }
+    for (GroupRank& r : g->ranks) { HIPCHK(hipSetDevice(r.dev)); HIPCHK(hipStreamSynchronize(r.st)); }
     return BROV_OK;
 }
 
@@ -638,69 +653,38 @@ static int slot_to_global(const brov_group* g, int slot) {
     return (r < g->W && i < g->cnt[r]) ? g->lo[r] + i : -1;
 }
 
-// poll the sequence word of device 0's mailbox; the stream is queried now and then, so that a launch that ended without delivering (a
-// device fault) turns into an error instead of a hang
-static int mail_wait(brov_group* g, int32_t seq) {
-    volatile int32_t* pf = (volatile int32_t*)&g->mail->seq;
-    for (unsigned long spin = 1; *pf != seq; spin++) {
-        if ((spin & 0x3ff) == 0) {
-            const hipError_t q = hipStreamQuery(g->st[0]);
-            if (q == hipSuccess) {   // the launch is over: everything it wrote is visible
-                if (*pf != seq) { g_gerr = "brov_group_select_best: the select kernel ended without delivering"; return BROV_ERR_HIP; }
-            } else if (q != hipErrorNotReady) {
-                g_gerr = std::string("brov_group_select_best: ") + hipGetErrorString(q);
-                (void)hipGetLastError();
-                return BROV_ERR_HIP;
-            }
-        }
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    return BROV_OK;
-}
-
 int brov_group_select_best(brov_group* g, int* best_index, brov_result* best) {
     if (!g || !best_index) return BROV_ERR_ARG;
     if (g->last_mode < 0) { g_gerr = "brov_group_select_best: call brov_group_gather first"; return BROV_ERR_ARG; }
     DeviceKeeper keep;
     *best_index = -1;
+    const GroupMail* mail = g->ranks[0].mail;
     if (g->last_mode == BROV_GATHER_RECORDS) {
-        // every device holds all records: device 0 selects (any would do).  The kernel delivers the winning slot and its record into
-        // the pinned mailbox and the host polls the sequence word: no copy command, no stream synchronisation on the way back (the
-        // other devices only finish their gather -- their streams order whatever is enqueued next behind it).
-        HIPCHK(hipSetDevice(g->dev[0]));
+        // every rank holds all records: rank 0 selects (any would do; the others only finish their gather -- their streams order whatever is
+        // enqueued next behind it).  The kernel delivers the winning slot and its record.
         const int slots = g->W * g->Bmax;
         int nb = (slots + 1023) / 1024;
         nb = nb < 1 ? 1 : (nb > kSelBlocks ? kSelBlocks : nb);
-        g->mail_seq = g->mail_seq == 0x7fffffff ? 1 : g->mail_seq + 1;
-        const int32_t seq = g->mail_seq;
-        hipLaunchKernelGGL(group_select_kernel, dim3(nb), dim3(256), 0, g->st[0], g->gathered[0], slots, g->best[0], g->sel_cost, g->sel_idx,
-                           (unsigned*)(g->best[0] + 1), g->sel_rec, g->mail, seq);
-        HIPCHK(hipGetLastError());
-        if (g->timing) { HIPCHK(hipEventRecord(g->ev[3], g->st[0])); g->ev_sel = true; }
-        if (int rc = mail_wait(g, seq)) return rc;
-        const int slot = g->mail->slot;
-        *best_index = slot_to_global(g, slot);
-        if (best && slot >= 0) std::memcpy(best, &g->mail->rec, sizeof(brov_result));
+        if (int rc = deliver(g, [&](GroupRank& r, int32_t seq) {
+                hipLaunchKernelGGL(group_select_kernel, dim3(nb), dim3(256), 0, r.st, r.gathered, slots, r.best, r.sel_cost, r.sel_idx, (unsigned*)(r.best + 1),
+                                   r.sel_rec, r.mail, seq);
+            })) return rc;
+        *best_index = slot_to_global(g, mail->slot);
+        if (best && mail->slot >= 0) std::memcpy(best, &mail->rec, sizeof(brov_result));
     } else {
-        // the gathered pairs are reduced on device 0 and the winner's (owner rank, global index, cost) comes back through the mailbox;
-        // its whole record is already in the owner's own mailbox (group_pack_kernel) when the owner is a device of this process
-        HIPCHK(hipSetDevice(g->dev[0]));
-        g->mail_seq = g->mail_seq == 0x7fffffff ? 1 : g->mail_seq + 1;
-        const int32_t seq = g->mail_seq;
-        hipLaunchKernelGGL(group_pairs_kernel, dim3(1), dim3(64), 0, g->st[0], g->pairs[0], g->W, g->mail, seq);
-        HIPCHK(hipGetLastError());
-        if (g->timing) { HIPCHK(hipEventRecord(g->ev[3], g->st[0])); g->ev_sel = true; }
-        if (int rc = mail_wait(g, seq)) return rc;
-        const int owner = g->mail->owner;
-        if (owner >= 0) {
-            *best_index = g->mail->slot;
+        // the gathered pairs are reduced on rank 0 and the winner's (owner rank, global index, cost) comes back through the mailbox; its
+        // whole record is already in the owner's own mailbox (group_pack_kernel) when the owner is a rank of this process
+        if (int rc = deliver(g, [&](GroupRank& r, int32_t seq) { hipLaunchKernelGGL(group_pairs_kernel, dim3(1), dim3(64), 0, r.st, r.pairs, g->W, r.mail, seq); }))
+            return rc;
+        if (mail->owner >= 0) {
+            *best_index = mail->slot;
             if (best) {
                 std::memset(best, 0, sizeof(*best));
-                const int d = owner - g->r0;
+                const int d = mail->owner - g->r0;
                 if (d >= 0 && d < g->n) {   // the winner lives in this process: its whole record
-                    std::memcpy(best, &g->pmail[d]->rec, sizeof(brov_result));
+                    std::memcpy(best, &g->ranks[d].pmail->rec, sizeof(brov_result));
                 } else {                    // ... in another process (one process per GPU): the pair carries its cost only
-                    best->cost = g->mail->rec.cost; best->status = BROV_STATUS_SUCCESS;
+                    best->cost = mail->rec.cost; best->status = BROV_STATUS_SUCCESS;
                 }
             }
         }
@@ -713,32 +697,33 @@ int brov_group_get_results_host(brov_group* g, brov_result* res) {
     if (g->last_mode != BROV_GATHER_RECORDS) { g_gerr = "brov_group_get_results_host: needs a BROV_GATHER_RECORDS gather"; return BROV_ERR_ARG; }
     if (int rc = brov_group_synchronize(g)) return rc;
     DeviceKeeper keep;
-    HIPCHK(hipSetDevice(g->dev[0]));
+    HIPCHK(hipSetDevice(g->ranks[0].dev));
     for (int r = 0; r < g->W; r++)   // strip the padding slots of uneven shards
-        HIPCHK(hipMemcpy(res + g->lo[r], g->gathered[0] + (size_t)r * g->Bmax, (size_t)g->cnt[r] * sizeof(brov_result), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(res + g->lo[r], g->ranks[0].gathered + (size_t)r * g->Bmax, (size_t)g->cnt[r] * sizeof(brov_result), hipMemcpyDeviceToHost));
     return BROV_OK;
 }
-const brov_result* brov_group_gathered_device(const brov_group* g, int rank) { return (g && rank >= 0 && rank < g->n) ? g->gathered[rank] : nullptr; }
+const brov_result* brov_group_gathered_device(const brov_group* g, int rank) { return (g && rank >= 0 && rank < g->n) ? g->ranks[rank].gathered : nullptr; }
 int brov_group_slots_per_rank(const brov_group* g) { return g ? g->Bmax : 0; }
 
 int brov_group_last_seconds(brov_group* g, double* solve, double* gather, double* select) {
     if (!g || !g->timing || !g->ev_solve) { g_gerr = "brov_group_last_seconds: no timed solve yet (timing must be on before brov_group_solve)"; return BROV_ERR_ARG; }
     double ts = 0, tg = 0, tsel = 0;
     DeviceKeeper keep;
-    for (int d = 0; d < g->n; d++) {
-        HIPCHK(hipSetDevice(g->dev[d]));
+    for (GroupRank& r : g->ranks) {
+        HIPCHK(hipSetDevice(r.dev));
         float a = 0, b = 0;
-        HIPCHK(hipEventSynchronize(g->ev[4 * d + 1]));
-        HIPCHK(hipEventElapsedTime(&a, g->ev[4 * d + 0], g->ev[4 * d + 1]));
-        if (g->last_mode >= 0 && g->ev_gather) { HIPCHK(hipEventSynchronize(g->ev[4 * d + 2])); HIPCHK(hipEventElapsedTime(&b, g->ev[4 * d + 1], g->ev[4 * d + 2])); }
+        HIPCHK(hipEventSynchronize(r.ev[1]));
+        HIPCHK(hipEventElapsedTime(&a, r.ev[0], r.ev[1]));
+        if (g->last_mode >= 0 && g->ev_gather) { HIPCHK(hipEventSynchronize(r.ev[2])); HIPCHK(hipEventElapsedTime(&b, r.ev[1], r.ev[2])); }
         if (a * 1e-3 > ts) ts = a * 1e-3;
         if (b * 1e-3 > tg) tg = b * 1e-3;
     }
     if (g->last_mode >= 0 && g->ev_sel && g->ev_gather) {   // (an event that was never recorded makes hipEventElapsedTime fail, and the failure would stay
         float c = 0;                        // behind as the thread's "last error" for the next hipGetLastError of an unrelated call)
-        HIPCHK(hipSetDevice(g->dev[0]));
-        HIPCHK(hipEventSynchronize(g->ev[3]));
-        HIPCHK(hipEventElapsedTime(&c, g->ev[2], g->ev[3]));
+        GroupRank& r0 = g->ranks[0];
+        HIPCHK(hipSetDevice(r0.dev));
+        HIPCHK(hipEventSynchronize(r0.ev[3]));
+        HIPCHK(hipEventElapsedTime(&c, r0.ev[2], r0.ev[3]));
         tsel = c * 1e-3;
     }
     if (solve) *solve = ts;

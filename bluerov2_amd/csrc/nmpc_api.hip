@@ -16,6 +16,7 @@
 
 #include "host_common.hpp"
 #include "nmpc_device.hpp"
+#include "select_device.hpp"
 
 using namespace brov;
 
@@ -1639,29 +1640,14 @@ extern "C" int brov_get_linearisation_host(brov_solver* s, double* AB, double* b
     return BROV_OK;
 }
 
-// arg-min of cost over successful instances: one block, strided scan + LDS tree
-__global__ void select_best_kernel(const brov_result* __restrict__ res, int B, int* __restrict__ out) {
-    __shared__ double sc[256];
-    __shared__ int si[256];
-    double best = 1e300;
+// arg-min of cost over the eligible instances (select_device.hpp: status SUCCESS and a finite cost): one block, strided scan + block_argmin
+__global__ __launch_bounds__(256) void select_best_kernel(const brov_result* __restrict__ res, int B, int* __restrict__ out) {
+    double best = 0.0;
     int bi = -1;
-    for (int k = threadIdx.x; k < B; k += blockDim.x) {
-        const double c = res[k].cost;
-        if (res[k].status == BROV_STATUS_SUCCESS && c == c && (c < best || (c == best && k < bi))) { best = c; bi = k; }
-    }
-    sc[threadIdx.x] = best; si[threadIdx.x] = bi;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            const double c2 = sc[threadIdx.x + o];
-            const int i2 = si[threadIdx.x + o];
-            if (i2 >= 0 && (si[threadIdx.x] < 0 || c2 < sc[threadIdx.x] || (c2 == sc[threadIdx.x] && i2 < si[threadIdx.x]))) {
-                sc[threadIdx.x] = c2; si[threadIdx.x] = i2;
-            }
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = si[0];
+    for (int k = threadIdx.x; k < B; k += blockDim.x)   // ascending: within a thread an equal cost never replaces an earlier index
+        if (result_eligible(res[k].status, res[k].cost)) argmin_next(best, bi, res[k].cost, k);
+    block_argmin<256>(best, bi);
+    if (threadIdx.x == 0) out[0] = bi;
 }
 
 extern "C" int brov_select_best_host(brov_solver* s, int* best_index, brov_result* best) {

@@ -77,13 +77,13 @@ def records_to_numpy(rec_bytes):
 
 
 def select_best_device(rec_bytes):
-    """arg-min of cost over the successful records with torch ops on the device holding them, no host synchronisation:
-    returns (index tensor, cost tensor); the cost is +inf when no record qualifies"""
+    """arg-min of cost over the eligible records -- status SUCCESS and a finite cost, the rule of csrc/select_device.hpp -- with torch ops
+    on the device holding them, no host synchronisation: returns (index tensor, cost tensor); the cost is +inf when no record qualifies"""
     n = rec_bytes.numel() // RECORD_BYTES
     rows = rec_bytes.view(n, RECORD_BYTES)
     cost = rows[:, 32:40].contiguous().view(torch.float64).view(n)
     status = rows[:, 48:52].contiguous().view(torch.int32).view(n)
-    ok = (status == 0) & ~torch.isnan(cost)
+    ok = (status == 0) & torch.isfinite(cost)
     masked = torch.where(ok, cost, torch.full_like(cost, float("inf")))
     idx = torch.argmin(masked)
     return idx, masked[idx]

@@ -328,8 +328,9 @@ double* brov_rp_disturbance_device(brov_solver* s);   /* [B][N+1][2]; NULL while
 int brov_get_rp_disturbance_host(brov_solver* s, double* d /*[B][N+1][2]*/);
 int brov_plant_set_rp_disturbance_host(brov_solver* s, const double* d /*[B][2]; NULL: back to the controller's stage 0*/);
 
-/* argmin of cost over instances with status SUCCESS (config 4 "best-trajectory select"); writes the winning index
- * and its record; runs on the GPU, result copied to HOST */
+/* argmin of cost over the eligible instances -- status SUCCESS and a finite cost: NaN, +Inf and -Inf never win; ties: lowest index; the
+ * one rule of bluerov2_amd/csrc/select_device.hpp -- (config 4 "best-trajectory select"); writes the winning index (-1: no instance
+ * qualifies) and its record; runs on the GPU, result copied to HOST */
 int brov_select_best_host(brov_solver* s, int* best_index, brov_result* best);
 
 /* ---- several GPUs in ONE process (BASELINE.json configs[3]: 65 536 candidates over 8 GPUs, all-gather of the
@@ -339,7 +340,8 @@ int brov_select_best_host(brov_solver* s, int* best_index, brov_result* best);
  * ncclAllGather per device (inside ncclGroupStart / ncclGroupEnd, on the devices' own streams, behind the solve) of
  *     BROV_GATHER_RECORDS  every instance's 104-byte result record, to every device (uneven shards: padded with never-selectable slots)
  *     BROV_GATHER_PACKED   one (cost, global index) pair per device (16 B): the local arg-min -- when only the winner is wanted
- * and brov_group_select_best returns the global arg-min of cost over the instances with status SUCCESS (ties: lowest index) and waits
+ * and brov_group_select_best returns the global arg-min of cost over the instances with status SUCCESS and a finite cost (NaN, +Inf and
+ * -Inf never win; ties: lowest index; the rule of bluerov2_amd/csrc/select_device.hpp, as brov_select_best_host) and waits
  * for it -- the only host wait of a step.  With BROV_GATHER_RECORDS the winner comes back through a pinned host mailbox the select kernel
  * (up to 64 blocks over the gathered records) writes itself: no copy command and no stream synchronisation on the way back; the call
  * returns when local device 0 has delivered, the other devices may still be finishing their gather (their streams order whatever is

@@ -101,6 +101,25 @@ def test_select_best_skips_failed_instances():
     assert D.select_best(torch.from_numpy(np.frombuffer(rec.tobytes(), dtype=np.uint8).copy()))[0] == -1
 
 
+def test_select_best_never_takes_a_cost_that_is_not_finite():
+    """status 0 with a NaN, +Inf or -Inf cost is not eligible (bluerov2_amd/csrc/select_device.hpp): no winner, and the packed pair says
+    so with a cost of +Inf; one finite record among them wins"""
+    from bluerov2_amd import distributed as D
+    from bluerov2_amd.solver import RESULT_DTYPE
+    rec = np.zeros(6, dtype=RESULT_DTYPE)
+    rec["cost"] = [np.inf, -np.inf, np.nan, -np.inf, np.inf, -np.inf]
+    as_bytes = lambda r: torch.from_numpy(np.frombuffer(r.tobytes(), dtype=np.uint8).copy())   # noqa: E731
+    idx, best = D.select_best(as_bytes(rec))
+    assert idx == -1 and best is None
+    pidx, pcost, powner = D.select_best_packed(as_bytes(rec), 100)
+    assert float(pcost) == np.inf
+    rec["cost"][4] = 7.0
+    idx, best = D.select_best(as_bytes(rec))
+    assert idx == 4 and best["cost"] == 7.0
+    pidx, pcost, powner = D.select_best_packed(as_bytes(rec), 100)
+    assert int(pidx) == 104 and float(pcost) == 7.0
+
+
 def _run_bench(args, env_extra=None, launcher=None):
     import json
     import subprocess
