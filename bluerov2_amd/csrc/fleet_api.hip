@@ -13,6 +13,7 @@
 #include "fleet_kernel.hpp"
 #include "host_common.hpp"
 #include "nmpc_device.hpp"
+#include "wrench_source.hpp"
 
 using namespace brov;
 
@@ -30,12 +31,9 @@ struct brov_fleet {
     int32_t* status = nullptr;         // [V] of the last step
     brov_result* winner_rec = nullptr; // [V] brov_fleet_select_host
     brov_result* stage_rec = nullptr;  // [B] brov_fleet_select_host: the caller's records on the device
-    long long ticks = 0;               // steps since the last reset (brov_vehicle_wrench_seek sets it): the tick the wrench is evaluated at
-    WrenchGen wr;                      // world-frame wrench of the vehicles (brov_vehicle_wrench_*); mode OFF: fleet_plant_kernel as it always was
-    double* wr_const = nullptr;        // [V][6] constant mode
-    double* wr_gain = nullptr;         // [V] table mode
-    double* wr_tab = nullptr;          // [rows][6] table mode; replaced by the next upload, not in `mem`
-    double* wv = nullptr;              // [V][6] the wrench of the tick in flight where no log row takes it; brov_vehicle_wrench_eval_host
+    // world-frame wrench of the vehicles (brov_vehicle_wrench_*) at batch V, its buffers reserved at create.  Its counter: steps since the last
+    // reset.  Its eval buffer also holds the wrench of the tick in flight where no log row takes it
+    WrenchSource wr;
     double* vprev = nullptr;           // [V][6] velocities at the last brov_vehicle_observe (zeros after reset)
     double *y12 = nullptr, *thrust = nullptr, *acc = nullptr;   // [V][12], [V][6], [V][6] the observer's inputs
     hipStream_t last_stream = nullptr;
@@ -52,7 +50,7 @@ extern "C" void brov_fleet_destroy(brov_fleet* f) {
     (void)hipSetDevice(f->device);
     (void)hipStreamSynchronize(f->last_stream);
     f->mem.free_all();
-    if (f->wr_tab) (void)hipFree(f->wr_tab);
+    f->wr.destroy();
     f->timer.destroy();
     if (f->ev_done) (void)hipEventDestroy(f->ev_done);
     delete f;
@@ -99,7 +97,7 @@ extern "C" int brov_fleet_reset(brov_fleet* f) {
     // xv[v] := x0 of candidate 0 of group v
     HIPCHK(hipMemcpy2D(f->xv, 12 * sizeof(double), brov_x0_device(f->s), (size_t)f->C * 12 * sizeof(double), 12 * sizeof(double), (size_t)f->V,
                        hipMemcpyDeviceToDevice));
-    f->ticks = 0;
+    f->wr.tick = 0;
     return BROV_OK;
 }
 
@@ -124,18 +122,13 @@ extern "C" int brov_fleet_create(brov_fleet** out, brov_solver* s, int candidate
     if (rc == BROV_OK) rc = f->mem.alloc(&f->status, V, g_fleet_err);
     if (rc == BROV_OK) rc = f->mem.alloc(&f->winner_rec, V, g_fleet_err);
     if (rc == BROV_OK) rc = f->mem.alloc(&f->stage_rec, (size_t)B, g_fleet_err);
-    if (rc == BROV_OK) rc = f->mem.alloc(&f->wr_const, V * 6, g_fleet_err);
-    if (rc == BROV_OK) rc = f->mem.alloc(&f->wr_gain, V, g_fleet_err);
-    if (rc == BROV_OK) rc = f->mem.alloc(&f->wv, V * 6, g_fleet_err);
     if (rc == BROV_OK) rc = f->mem.alloc(&f->vprev, V * 6, g_fleet_err);
     if (rc == BROV_OK) rc = f->mem.alloc(&f->y12, V * 12, g_fleet_err);
     if (rc == BROV_OK) rc = f->mem.alloc(&f->thrust, V * 6, g_fleet_err);
     if (rc == BROV_OK) rc = f->mem.alloc(&f->acc, V * 6, g_fleet_err);
-    if (rc != BROV_OK) {
-        g_fleet_err = "brov_fleet_create: " + g_fleet_err;
-        brov_fleet_destroy(f);
-        return rc;
-    }
+    f->wr.B = V;
+    if (rc == BROV_OK) rc = f->wr.reserve(f->mem, g_fleet_err);   // eager: a step reads the eval buffer without a host wait
+    if (rc != BROV_OK) { g_fleet_err = "brov_fleet_create: " + g_fleet_err; brov_fleet_destroy(f); return rc; }
     if (f->timer.create() != hipSuccess || hipEventCreateWithFlags(&f->ev_done, hipEventDisableTiming) != hipSuccess) {
         g_fleet_err = "brov_fleet_create: device initialisation failed";
         brov_fleet_destroy(f);
@@ -205,81 +198,36 @@ extern "C" int brov_fleet_select_host(brov_fleet* f, const brov_result* rec_host
     return BROV_OK;
 }
 
-// ---- the world-frame wrench of the vehicles: the solver's generator (plant_wrench.hip) at batch V -------------------------------------
-static const double kWrenchMaxHalfPeriods = 4194304.0;   // 2^22: the half-period index has 22 bits of the amplitude counter
-// the periodic generator's half-period index at `tick` must fit its counter field (the check of brov_plant_wrench_*)
-static int wrench_tick_ok(const WrenchGen& g, long long tick, const char* who) {
-    if (tick < 0) { g_fleet_err = std::string(who) + ": negative wrench tick"; return BROV_ERR_ARG; }
-    if (g.mode == BROV_WRENCH_PERIODIC) {
-        const double j = std::floor((g.phase0 + (double)tick * g.dphi) / 3.14159265358979323846);
-        if (!(j < kWrenchMaxHalfPeriods)) {
-            g_fleet_err = std::string(who) + ": the periodic wrench's half-period index floor(t / pi) must stay below 2^22";
-            return BROV_ERR_ARG;
-        }
-    }
-    return BROV_OK;
-}
-// the last of `n` steps from the counter on (the phase does not decrease with the tick: dphi >= 0)
-static int wrench_steps_ok(const brov_fleet* f, long long n, const char* who) {
-    return n > 0 ? wrench_tick_ok(f->wr, f->ticks + n - 1, who) : BROV_OK;
-}
-
-extern "C" int brov_vehicle_wrench_constant_host(brov_fleet* f, const double* w) {
-    if (!f || !w) { g_fleet_err = "brov_vehicle_wrench_constant_host: null argument"; return BROV_ERR_ARG; }
+// ---- the world-frame wrench of the vehicles: the solver's generator (plant_wrench.hip) at batch V, thin forwards to the one host side,
+// wrench_source.hpp -------------------------------------------------------------------------------------------------------------------------
+static int no_fleet(const char* who) { g_fleet_err = std::string(who) + ": null argument"; return BROV_ERR_ARG; }
+// the device, and the host wait for a step in flight that may still read the generator's buffers
+static int wrench_wait(brov_fleet* f) {
     HIPCHK(hipSetDevice(f->device));
-    HIPCHK(hipStreamSynchronize(f->last_stream));   // a plant step in flight may still read the buffer
-    HIPCHK(hipMemcpy(f->wr_const, w, (size_t)f->V * 6 * sizeof(double), hipMemcpyHostToDevice));
-    f->wr.mode = BROV_WRENCH_CONSTANT; f->wr.w = f->wr_const;
+    HIPCHK(hipStreamSynchronize(f->last_stream));
     return BROV_OK;
+}
+extern "C" int brov_vehicle_wrench_constant_host(brov_fleet* f, const double* w) {
+    if (!f) return no_fleet("brov_vehicle_wrench_constant_host");
+    return f->wr.constant_host(w, [f] { return wrench_wait(f); }, f->mem, g_fleet_err, "brov_vehicle_wrench_constant_host");
 }
 extern "C" int brov_vehicle_wrench_periodic(brov_fleet* f, uint64_t seed, double scale, double phase0, double dphi, double tz_div) {
-    if (!f || !std::isfinite(scale) || !(phase0 >= 0.0) || !(dphi >= 0.0) || !std::isfinite(phase0) || !std::isfinite(dphi) || !std::isfinite(tz_div) ||
-        tz_div == 0.0) {
-        g_fleet_err = "brov_vehicle_wrench_periodic: needs a fleet and finite scale, phase0 >= 0, dphi >= 0 and tz_div != 0";
-        return BROV_ERR_ARG;
-    }
-    WrenchGen g = f->wr;
-    g.mode = BROV_WRENCH_PERIODIC; g.seed = seed; g.scale = scale; g.phase0 = phase0; g.dphi = dphi; g.tz_div = tz_div;
-    if (int rc = wrench_tick_ok(g, f->ticks, "brov_vehicle_wrench_periodic")) return rc;
-    f->wr = g;
-    return BROV_OK;
+    if (!f) return no_fleet("brov_vehicle_wrench_periodic");
+    return f->wr.periodic(seed, scale, phase0, dphi, tz_div, g_fleet_err, "brov_vehicle_wrench_periodic");
 }
 extern "C" int brov_vehicle_wrench_table_host(brov_fleet* f, const double* tab, int rows, const double* gain) {
-    if (!f || !tab || rows < 1) { g_fleet_err = "brov_vehicle_wrench_table_host: needs a fleet, a table and rows >= 1"; return BROV_ERR_ARG; }
-    HIPCHK(hipSetDevice(f->device));
-    HIPCHK(hipStreamSynchronize(f->last_stream));
-    ScopedDeviceBuffer<double> nt;   // the table in force stays until the new one is complete
-    HIPCHK(nt.init((size_t)rows * 6));
-    HIPCHK(hipMemcpy(nt.p, tab, (size_t)rows * 6 * sizeof(double), hipMemcpyHostToDevice));
-    if (gain) HIPCHK(hipMemcpy(f->wr_gain, gain, (size_t)f->V * sizeof(double), hipMemcpyHostToDevice));
-    if (f->wr_tab) (void)hipFree(f->wr_tab);
-    f->wr_tab = nt.release();
-    f->wr.mode = BROV_WRENCH_TABLE; f->wr.tab = f->wr_tab; f->wr.rows = rows; f->wr.gain = gain ? f->wr_gain : nullptr;
-    return BROV_OK;
+    if (!f) return no_fleet("brov_vehicle_wrench_table_host");
+    return f->wr.table_host(tab, rows, gain, [f] { return wrench_wait(f); }, f->mem, g_fleet_err, "brov_vehicle_wrench_table_host");
 }
-extern "C" int brov_vehicle_wrench_off(brov_fleet* f) {
-    if (!f) { g_fleet_err = "brov_vehicle_wrench_off: null argument"; return BROV_ERR_ARG; }
-    f->wr.mode = BROV_WRENCH_OFF;
-    return BROV_OK;
-}
-extern "C" int brov_vehicle_wrench_mode(const brov_fleet* f) { return f ? f->wr.mode : BROV_WRENCH_OFF; }
+extern "C" int brov_vehicle_wrench_off(brov_fleet* f) { return f ? f->wr.set_off() : no_fleet("brov_vehicle_wrench_off"); }
+extern "C" int brov_vehicle_wrench_mode(const brov_fleet* f) { return f ? f->wr.mode() : BROV_WRENCH_OFF; }
 extern "C" int brov_vehicle_wrench_seek(brov_fleet* f, int64_t tick) {
-    if (!f) { g_fleet_err = "brov_vehicle_wrench_seek: null argument"; return BROV_ERR_ARG; }
-    if (int rc = wrench_tick_ok(f->wr, (long long)tick, "brov_vehicle_wrench_seek")) return rc;
-    f->ticks = (long long)tick;
-    return BROV_OK;
+    return f ? f->wr.seek(tick, g_fleet_err, "brov_vehicle_wrench_seek") : no_fleet("brov_vehicle_wrench_seek");
 }
-extern "C" int64_t brov_vehicle_wrench_tick(const brov_fleet* f) { return f ? (int64_t)f->ticks : 0; }
+extern "C" int64_t brov_vehicle_wrench_tick(const brov_fleet* f) { return f ? (int64_t)f->wr.tick : 0; }
 extern "C" int brov_vehicle_wrench_eval_host(brov_fleet* f, int64_t tick, double* w) {
-    if (!f || !w) { g_fleet_err = "brov_vehicle_wrench_eval_host: null argument"; return BROV_ERR_ARG; }
-    if (int rc = wrench_tick_ok(f->wr, (long long)tick, "brov_vehicle_wrench_eval_host")) return rc;
-    HIPCHK(hipSetDevice(f->device));
-    HIPCHK(hipStreamSynchronize(f->last_stream));   // a step in flight may still read the buffer
-    launch_wrench_eval(f->wr, f->V, (long long)tick, f->wv, f->last_stream);   // mode OFF: zeros
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(f->last_stream));
-    HIPCHK(hipMemcpy(w, f->wv, (size_t)f->V * 6 * sizeof(double), hipMemcpyDeviceToHost));
-    return BROV_OK;
+    if (!f) return no_fleet("brov_vehicle_wrench_eval_host");
+    return f->wr.eval_host(tick, w, f->last_stream, [f] { return wrench_wait(f); }, f->mem, g_fleet_err, "brov_vehicle_wrench_eval_host");
 }
 
 // what the plant of the fleet does not model: the vehicles' wrench is the fleet's (brov_vehicle_wrench_*), indexed
@@ -298,7 +246,7 @@ static int plant_modes_ok(const brov_fleet* f, const char* who) {
 }
 
 // select + plant + broadcast on `st` (ordered by the caller, who has checked the wrench tick), with optional DEVICE log rows of this tick.
-// Under a wrench mode the wrench of the tick is evaluated into wlog's row (or the fleet's buffer): the plant's input and the log row are one.
+// Under a wrench mode the wrench of the tick is evaluated into wlog's row (or the source's eval buffer): the plant's input and the log row are one.
 static int step_on(brov_fleet* f, const brov_result* rec, double dt, int substeps, double* xlog, double* ulog, int32_t* stlog, int32_t* winlog,
                    double* wlog, hipStream_t st) {
     if (!rec) rec = brov_results_device(f->s);
@@ -309,18 +257,18 @@ static int step_on(brov_fleet* f, const brov_result* rec, double dt, int substep
     else { a.pp = solver_view(f->s).par; a.pp_stride = (long long)f->C * (f->N + 1) * 16; }   // stage 0 of candidate 0, as it stands now
     a.dt = dt; a.substeps = substeps; a.u_hold = f->u_hold; a.status = f->status;
     a.xlog = xlog; a.ulog = ulog; a.stlog = stlog; a.winlog = winlog;
-    if (f->wr.mode == BROV_WRENCH_OFF) {
+    if (f->wr.off()) {
         launch_fleet_plant(a, st);
     } else {
-        double* wv = wlog ? wlog : f->wv;
-        launch_wrench_eval(f->wr, f->V, f->ticks, wv, st);
+        double* wv = wlog ? wlog : f->wr.eval;
+        launch_wrench_eval(f->wr.gen, f->V, f->wr.tick, wv, st);
         HIPCHK(hipGetLastError());
         launch_fleet_plant_wrench(a, wv, st);
     }
     HIPCHK(hipGetLastError());
     launch_fleet_bcast(f->xv, f->V, f->C, brov_x0_device(f->s), st);
     HIPCHK(hipGetLastError());
-    f->ticks++;
+    f->wr.tick++;
     return enqueued_on(f, st);
 }
 
@@ -330,7 +278,7 @@ extern "C" int brov_fleet_step(brov_fleet* f, const brov_result* rec, double dt,
         return BROV_ERR_ARG;
     }
     if (int rc = plant_modes_ok(f, "brov_fleet_step")) return rc;
-    if (int rc = wrench_steps_ok(f, 1, "brov_fleet_step")) return rc;
+    if (int rc = f->wr.steps_ok(1, g_fleet_err, "brov_fleet_step")) return rc;
     HIPCHK(hipSetDevice(f->device));
     hipStream_t st = (hipStream_t)stream;
     if (int rc = order_both(f, st, "brov_fleet_step")) return rc;
@@ -422,7 +370,7 @@ static int fleet_loop(brov_fleet* f, brov_ekf* e, const char* who, int ticks, do
         if (int rc = observer_ok(f, e, who)) return rc;
         if (int rc = apply_ok(f, who)) return rc;
     }
-    if (int rc = wrench_steps_ok(f, ticks, who)) return rc;
+    if (int rc = f->wr.steps_ok(ticks, g_fleet_err, who)) return rc;
     const SolverView sv = solver_view(f->s);
     if (!sv.cand_set) {
         g_fleet_err = pre + "no candidate parameters (brov_set_candidate_params_host)";
@@ -430,54 +378,28 @@ static int fleet_loop(brov_fleet* f, brov_ekf* e, const char* who, int ticks, do
     }
     HIPCHK(hipSetDevice(f->device));
     hipStream_t st = sv.last_stream;
-    const size_t V = (size_t)f->V, n = (size_t)ticks;
-    // DEVICE logs for the whole run, a block per HOST log asked for; the states behind the start state
-    DeviceAllocs logs;
-    double *dx = nullptr, *du = nullptr, *dw = nullptr, *dest = nullptr;
-    int32_t *dst = nullptr, *dwin = nullptr;
-    int rc = BROV_OK;
-    if (x_log) rc = logs.alloc(&dx, (n + 1) * V * 12, g_fleet_err);
-    if (u_log && n && rc == BROV_OK) rc = logs.alloc(&du, n * V * 4, g_fleet_err);
-    if (st_log && n && rc == BROV_OK) rc = logs.alloc(&dst, n * V, g_fleet_err);
-    if (win_log && n && rc == BROV_OK) rc = logs.alloc(&dwin, n * V, g_fleet_err);
-    if (w_log && n && rc == BROV_OK) rc = logs.alloc(&dw, n * V * 6, g_fleet_err);
-    if (est_log && n && rc == BROV_OK) rc = logs.alloc(&dest, n * V * 6, g_fleet_err);
-    if (rc != BROV_OK) g_fleet_err = pre + g_fleet_err;
+    // DEVICE logs for the whole run (LoopLog, host_common.hpp), a column per HOST log asked for; the states behind the start state
+    LoopLog L;
+    const int X = L.column(12, x_log, 1), U = L.column(4, u_log), ST = L.column(1, st_log), WIN = L.column(1, win_log), W = L.column(6, w_log),
+              EST = L.column(6, est_log);
+    int rc = L.alloc((size_t)f->V, (size_t)ticks, g_fleet_err, pre);
     if (rc == BROV_OK) rc = order_both(f, st, who);
-    if (rc == BROV_OK && ((dx && hipMemcpyAsync(dx, f->xv, V * 12 * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess) ||
-                          (dw && f->wr.mode == BROV_WRENCH_OFF && hipMemsetAsync(dw, 0, n * V * 6 * sizeof(double), st) != hipSuccess))) {
-        (void)hipGetLastError();
-        g_fleet_err = pre + "log initialisation failed";
-        rc = BROV_ERR_HIP;
-    }
+    if (rc == BROV_OK) rc = L.init(f->xv, f->wr.off() ? W : -1, st, g_fleet_err, pre);   // (mode OFF: no wrench, nothing writes its log)
     for (int k = 0; k < ticks && rc == BROV_OK; k++) {
         rc = brov_set_yref_candidates(f->s, t0 + k * dt_ref, dt_node, st);
         if (rc == BROV_OK) rc = brov_solve(f->s, st);
         if (rc != BROV_OK) { g_fleet_err = pre + brov_last_error(); break; }
-        rc = step_on(f, nullptr, dt, substeps, dx ? dx + (size_t)(k + 1) * V * 12 : nullptr, du ? du + (size_t)k * V * 4 : nullptr,
-                     dst ? dst + (size_t)k * V : nullptr, dwin ? dwin + (size_t)k * V : nullptr, dw ? dw + (size_t)k * V * 6 : nullptr, st);
+        rc = step_on(f, nullptr, dt, substeps, L.row<double>(X, k), L.row<double>(U, k), L.row<int32_t>(ST, k), L.row<int32_t>(WIN, k),
+                     L.row<double>(W, k), st);
         if (e && rc == BROV_OK) rc = observe_on(f, e, dt, who, st);
         if (e && rc == BROV_OK) rc = apply_on(f, e, st);
-        if (rc == BROV_OK && dest) {
-            launch_gather_cols(brov_ekf_x_device(e), (int)V, 18, 12, 6, dest + (size_t)k * V * 6, st);
+        double* est = L.row<double>(EST, k);
+        if (rc == BROV_OK && est) {
+            launch_gather_cols(brov_ekf_x_device(e), f->V, 18, 12, 6, est, st);
             if (hipGetLastError() != hipSuccess) { g_fleet_err = pre + "gathering the estimate failed"; rc = BROV_ERR_HIP; }
         }
     }
-    // the one host wait, then a launch error nobody has picked up
-    hipError_t err = hipStreamSynchronize(st);
-    if (rc == BROV_OK && err == hipSuccess) err = hipGetLastError();
-    if (rc == BROV_OK && err != hipSuccess) { g_fleet_err = pre + hipGetErrorString(err); rc = BROV_ERR_HIP; }
-    if (rc == BROV_OK) {   // logs only from a loop that completed
-        if (dx && hipMemcpy(x_log, dx, (n + 1) * V * 12 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = BROV_ERR_HIP;
-        if (du && hipMemcpy(u_log, du, n * V * 4 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = BROV_ERR_HIP;
-        if (dst && hipMemcpy(st_log, dst, n * V * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) rc = BROV_ERR_HIP;
-        if (dwin && hipMemcpy(win_log, dwin, n * V * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) rc = BROV_ERR_HIP;
-        if (dw && hipMemcpy(w_log, dw, n * V * 6 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = BROV_ERR_HIP;
-        if (dest && hipMemcpy(est_log, dest, n * V * 6 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = BROV_ERR_HIP;
-        if (rc != BROV_OK) { (void)hipGetLastError(); g_fleet_err = pre + "copying the logs back failed"; }
-    }
-    logs.free_all();
-    return rc;
+    return L.deliver(finish_loop(st, rc, g_fleet_err, pre), g_fleet_err, pre);
 }
 
 extern "C" int brov_closed_loop_fleet(brov_fleet* f, int ticks, double t0, double dt_ref, double dt_node, double dt, int substeps, double* u_log,

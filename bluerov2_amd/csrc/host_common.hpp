@@ -1,7 +1,7 @@
 // host_common.hpp -- the host-side scaffolding every device object of the C ABI is built from (brov_solver, brov_ekf, brov_rls, brov_track,
 // brov_group): the HIP error check, the "is this device usable" test of the create calls, an owner of device allocations, a two-event kernel
-// timer and a scoped temporary device buffer.  Host code only, header only.  Each component keeps its OWN thread-local error string and its own
-// brov_*_last_error(): a failing observer call must not overwrite brov_last_error(), so everything here that reports takes the string to write.
+// timer, a scoped temporary device buffer, the logs of a closed loop.  Host code only, header only.  Each component keeps its OWN thread-local
+// error string and brov_*_last_error(): a failing observer call must not overwrite brov_last_error(), so what reports here takes the string to write.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -116,5 +116,72 @@ struct ScopedDeviceBuffer {
     hipError_t init(size_t n) { return hipMalloc((void**)&p, n * sizeof(T)); }
     T* release() { T* q = p; p = nullptr; return q; }
 };
+
+// ---- the logs of a closed loop: DEVICE blocks of one row per tick that the loop's kernels write, copied to the host after the loop's one host
+// wait.  The whole-loop logs of brov_closed_loop_ex / _dob, the one-chunk device logs of brov_closed_loop_track and the six logs of the fleet's
+// loops are all declared, allocated, initialised, delivered and freed here -------------------------------------------------------------------
+struct LoopLog {
+    struct Column {
+        size_t elem, width, lead;   // bytes per element (double or int32_t), elements per instance per tick, rows ahead of tick 0
+        void* host;                 // where deliver() copies the column; null: a device-only column
+        bool wanted;                // a host destination was given, or the column is device-only: alloc() gives it a block
+        char* dev;
+    };
+    std::vector<Column> cols;
+    size_t B = 0, n = 0;
+    DeviceAllocs mem;
+    LoopLog() { cols.reserve(6); }   // one host allocation for the columns of any loop
+    LoopLog(const LoopLog&) = delete;
+    ~LoopLog() { mem.free_all(); }   // on every way out
+    // declares a column of T and returns its index; without a host destination it exists only as a device-only column.  The state column of
+    // a whole loop has lead = 1: the start state ahead of the states after every tick
+    template <typename T>
+    int column(size_t width, T* host, size_t lead = 0, bool device_only = false) {
+        static_assert(sizeof(T) == sizeof(double) || sizeof(T) == sizeof(int32_t), "a log column holds double or int32_t");
+        cols.push_back(Column{sizeof(T), width, lead, host, host != nullptr || device_only, nullptr});
+        return (int)cols.size() - 1;
+    }
+    size_t row_bytes(const Column& c) const { return B * c.width * c.elem; }
+    // the wanted columns for `n_` ticks of `B_` instances (a column without a row gets no block)
+    int alloc(size_t B_, size_t n_, std::string& err, const std::string& pre) {
+        B = B_; n = n_;
+        for (Column& c : cols) {
+            if (!c.wanted || n + c.lead == 0) continue;
+            if (int rc = mem.alloc(&c.dev, (n + c.lead) * row_bytes(c), err)) { err = pre + err; return rc; }
+        }
+        return BROV_OK;
+    }
+    // row `j` (tick j of the run) of column `c`, whose element type is T; null when the column was not asked for
+    template <typename T>
+    T* row(int c, size_t j) const { return cols[c].dev ? (T*)(cols[c].dev + (j + cols[c].lead) * row_bytes(cols[c])) : nullptr; }
+    // enqueues the initialisation on `st`: zeros into column `zero_col` (-1: none; the caller names it only where nothing will write its rows)
+    // and `start` into the lead rows
+    int init(const void* start, int zero_col, hipStream_t st, std::string& err, const std::string& pre) {
+        hipError_t e = hipSuccess;
+        if (zero_col >= 0 && cols[zero_col].dev) e = hipMemsetAsync(cols[zero_col].dev, 0, (n + cols[zero_col].lead) * row_bytes(cols[zero_col]), st);
+        for (const Column& c : cols)
+            if (c.dev && c.lead && e == hipSuccess) e = hipMemcpyAsync(c.dev, start, c.lead * row_bytes(c), hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess) return BROV_OK;
+        (void)hipGetLastError();
+        err = pre + "log initialisation failed";
+        return BROV_ERR_HIP;
+    }
+    // after the loop's host wait: the columns to their host destinations, from a loop that completed alone (rc, which is handed on) -- a
+    // failing call leaves the caller's arrays as they were
+    int deliver(int rc, std::string& err, const std::string& pre) {
+        if (rc != BROV_OK) return rc;
+        for (const Column& c : cols)
+            if (c.dev && c.host && hipMemcpy(c.host, c.dev, (n + c.lead) * row_bytes(c), hipMemcpyDeviceToHost) != hipSuccess) rc = BROV_ERR_HIP;
+        if (rc != BROV_OK) { (void)hipGetLastError(); err = pre + "copying the logs back failed"; }
+        return rc;
+    }
+};
+// the end of a closed loop: its one host wait, then a launch error nobody has picked up (its text behind `pre`), then the code
+inline int finish_loop(hipStream_t st, int rc, std::string& err, const std::string& pre) {
+    hipError_t e = hipStreamSynchronize(st);
+    if (rc == BROV_OK && e == hipSuccess) e = hipGetLastError();
+    if (rc == BROV_OK && e != hipSuccess) { err = pre + hipGetErrorString(e); rc = BROV_ERR_HIP; }
+    return rc;
+}
 
 }  // namespace brov

@@ -17,6 +17,7 @@
 #include "host_common.hpp"
 #include "nmpc_device.hpp"
 #include "select_device.hpp"
+#include "wrench_source.hpp"
 
 using namespace brov;
 
@@ -102,10 +103,7 @@ struct brov_solver {
     bool dist6 = false, prp_plant_set = false;
     bool pplant_set = false;     // explicit plant parameters given (brov_plant_set_params_host)
     bool pplant_stale = true;    // controller parameters changed since the plant's copy of them was taken
-    WrenchGen wr;                // world-frame wrench of the plant (brov_plant_wrench_*): mode OFF = the plant kernel as it always was
-    double *wr_const = nullptr, *wr_gain = nullptr, *wr_eval = nullptr;   // [B][6], [B], [B][6] (brov_plant_wrench_eval_host): allocated on first use
-    double* wr_tab = nullptr;    // [rows][6], replaced by every brov_plant_wrench_table_host
-    long long wr_tick = 0;       // plant steps so far (brov_plant_wrench_seek sets it)
+    WrenchSource wr;             // world-frame wrench of the plant (brov_plant_wrench_*), its buffers allocated on first use; its counter: plant steps so far
     bool cand_set = false;       // candidate shape parameters resident in scratch3
     int cand_kind = 0;
     bool dump_lin = false;
@@ -328,6 +326,7 @@ extern "C" int brov_create(brov_solver** out, int device, int B, const brov_opts
     s->B = B;
     s->N = opts->N;
     s->opts = *opts;
+    s->wr.B = (size_t)B;
     const size_t N = opts->N, Bz = B;
     int rc = BROV_OK;
 #define AL(ptr, n) if (rc == BROV_OK) rc = s->mem.alloc(&s->ptr, (n), g_err)
@@ -396,7 +395,7 @@ extern "C" void brov_destroy(brov_solver* s) {
     // (a caller's own stream is the caller's to drain -- it may not exist any more; hipFree below waits for the device in any case)
     s->mem.free_all();
     if (s->traj) hipFree(s->traj);
-    if (s->wr_tab) hipFree(s->wr_tab);
+    s->wr.destroy();
     if (s->dbg) hipFree(s->dbg);
     s->tick.destroy();
     for (int k = 0; k < 3; k++)
@@ -750,87 +749,47 @@ static int ensure_plant_params(brov_solver* s, hipStream_t st) {
     }
     return BROV_OK;
 }
-// ---- time-varying world-frame wrench of the plant (plant_wrench.hip) ----------------------------------------------------------------
-static const double kWrenchMaxHalfPeriods = 4194304.0;   // 2^22: the half-period index has 22 bits of the amplitude counter
-// the periodic generator's half-period index at `tick` must fit its counter field
-static int wrench_tick_ok(const brov_solver* s, long long tick, const char* who) {
-    if (tick < 0) { g_err = std::string(who) + ": negative wrench tick"; return BROV_ERR_ARG; }
-    if (s->wr.mode == BROV_WRENCH_PERIODIC) {
-        const double j = std::floor((s->wr.phase0 + (double)tick * s->wr.dphi) / 3.14159265358979323846);
-        if (!(j < kWrenchMaxHalfPeriods)) { g_err = std::string(who) + ": the periodic wrench's half-period index floor(t / pi) must stay below 2^22"; return BROV_ERR_ARG; }
-    }
+// ---- time-varying world-frame wrench of the plant (plant_wrench.hip): thin forwards to the one host side, wrench_source.hpp -------------------
+static int no_solver(const char* who) { g_err = std::string(who) + ": null argument"; return BROV_ERR_ARG; }
+// the device, and the host wait for a plant step in flight that may still read the generator's buffers
+static int wrench_wait(brov_solver* s) {
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(sync_last(s));
     return BROV_OK;
 }
 extern "C" int brov_plant_wrench_constant_host(brov_solver* s, const double* w) {
-    if (!s || !w) return BROV_ERR_ARG;
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(sync_last(s));   // a plant step in flight may still read the buffer
-    if (!s->wr_const) { if (int rc = s->mem.alloc(&s->wr_const, (size_t)s->B * 6, g_err)) return rc; }
-    HIPCHK(hipMemcpy(s->wr_const, w, (size_t)s->B * 6 * sizeof(double), hipMemcpyHostToDevice));
-    s->wr.mode = BROV_WRENCH_CONSTANT; s->wr.w = s->wr_const;
-    return BROV_OK;
+    if (!s) return no_solver("brov_plant_wrench_constant_host");
+    return s->wr.constant_host(w, [s] { return wrench_wait(s); }, s->mem, g_err, "brov_plant_wrench_constant_host");
 }
 extern "C" int brov_plant_wrench_periodic(brov_solver* s, uint64_t seed, double scale, double phase0, double dphi, double tz_div) {
-    if (!s || !std::isfinite(scale) || !(phase0 >= 0.0) || !(dphi >= 0.0) || !std::isfinite(phase0) || !std::isfinite(dphi) || !std::isfinite(tz_div) ||
-        tz_div == 0.0) {
-        g_err = "brov_plant_wrench_periodic: scale, phase0 >= 0, dphi >= 0 and tz_div != 0 must be finite";
-        return BROV_ERR_ARG;
-    }
-    const WrenchGen keep = s->wr;
-    s->wr.mode = BROV_WRENCH_PERIODIC; s->wr.seed = seed; s->wr.scale = scale; s->wr.phase0 = phase0; s->wr.dphi = dphi; s->wr.tz_div = tz_div;
-    if (int rc = wrench_tick_ok(s, s->wr_tick, "brov_plant_wrench_periodic")) { s->wr = keep; return rc; }
-    return BROV_OK;
+    if (!s) return no_solver("brov_plant_wrench_periodic");
+    return s->wr.periodic(seed, scale, phase0, dphi, tz_div, g_err, "brov_plant_wrench_periodic");
 }
 extern "C" int brov_plant_wrench_table_host(brov_solver* s, const double* tab, int rows, const double* gain) {
-    if (!s || !tab || rows < 1) return BROV_ERR_ARG;
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(sync_last(s));
-    if (gain && !s->wr_gain) { if (int rc = s->mem.alloc(&s->wr_gain, (size_t)s->B, g_err)) return rc; }
-    ScopedDeviceBuffer<double> nt;   // the table in force stays until the new one is complete
-    HIPCHK(nt.init((size_t)rows * 6));
-    HIPCHK(hipMemcpy(nt.p, tab, (size_t)rows * 6 * sizeof(double), hipMemcpyHostToDevice));
-    if (gain) HIPCHK(hipMemcpy(s->wr_gain, gain, (size_t)s->B * sizeof(double), hipMemcpyHostToDevice));
-    if (s->wr_tab) hipFree(s->wr_tab);
-    s->wr_tab = nt.release();
-    s->wr.mode = BROV_WRENCH_TABLE; s->wr.tab = s->wr_tab; s->wr.rows = rows; s->wr.gain = gain ? s->wr_gain : nullptr;
-    return BROV_OK;
+    if (!s) return no_solver("brov_plant_wrench_table_host");
+    return s->wr.table_host(tab, rows, gain, [s] { return wrench_wait(s); }, s->mem, g_err, "brov_plant_wrench_table_host");
 }
-extern "C" int brov_plant_wrench_off(brov_solver* s) {
-    if (!s) return BROV_ERR_ARG;
-    s->wr.mode = BROV_WRENCH_OFF;
-    return BROV_OK;
-}
-extern "C" int brov_plant_wrench_mode(const brov_solver* s) { return s ? s->wr.mode : BROV_WRENCH_OFF; }
+extern "C" int brov_plant_wrench_off(brov_solver* s) { return s ? s->wr.set_off() : no_solver("brov_plant_wrench_off"); }
+extern "C" int brov_plant_wrench_mode(const brov_solver* s) { return s ? s->wr.mode() : BROV_WRENCH_OFF; }
 extern "C" int brov_plant_wrench_seek(brov_solver* s, int64_t tick) {
-    if (!s) return BROV_ERR_ARG;
-    if (int rc = wrench_tick_ok(s, (long long)tick, "brov_plant_wrench_seek")) return rc;
-    s->wr_tick = (long long)tick;
-    return BROV_OK;
+    return s ? s->wr.seek(tick, g_err, "brov_plant_wrench_seek") : no_solver("brov_plant_wrench_seek");
 }
-extern "C" int64_t brov_plant_wrench_tick(const brov_solver* s) { return s ? (int64_t)s->wr_tick : 0; }
+extern "C" int64_t brov_plant_wrench_tick(const brov_solver* s) { return s ? (int64_t)s->wr.tick : 0; }
 extern "C" int brov_plant_wrench_eval_host(brov_solver* s, int64_t tick, double* w) {
-    if (!s || !w) return BROV_ERR_ARG;
-    if (int rc = wrench_tick_ok(s, (long long)tick, "brov_plant_wrench_eval_host")) return rc;
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(sync_last(s));
-    if (!s->wr_eval) { if (int rc = s->mem.alloc(&s->wr_eval, (size_t)s->B * 6, g_err)) return rc; }
-    launch_wrench_eval(s->wr, s->B, (long long)tick, s->wr_eval, s->last_stream);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s->last_stream));
-    HIPCHK(hipMemcpy(w, s->wr_eval, (size_t)s->B * 6 * sizeof(double), hipMemcpyDeviceToHost));
-    return BROV_OK;
+    if (!s) return no_solver("brov_plant_wrench_eval_host");
+    return s->wr.eval_host(tick, w, s->last_stream, [s] { return wrench_wait(s); }, s->mem, g_err, "brov_plant_wrench_eval_host");
 }
 // one plant step of the tick counter's tick on `st`, with optional DEVICE logs of this tick; mode OFF: the plant kernel as it always was
 static void plant_step_on(brov_solver* s, double dt, int substeps, double* xlog, double* ulog, double* wlog, hipStream_t st) {
-    if (s->wr.mode == BROV_WRENCH_OFF)
+    if (s->wr.off())
         launch_plant(s->x0, s->res, s->pplant, plant_rp(s), plant_rp_stride(s), s->B, dt, substeps, xlog, ulog, st);
     else
-        launch_plant_wrench(s->x0, s->res, s->pplant, plant_rp(s), plant_rp_stride(s), s->B, dt, substeps, xlog, ulog, s->wr, s->wr_tick, wlog, st);
-    s->wr_tick++;
+        launch_plant_wrench(s->x0, s->res, s->pplant, plant_rp(s), plant_rp_stride(s), s->B, dt, substeps, xlog, ulog, s->wr.gen, s->wr.tick, wlog, st);
+    s->wr.tick++;
 }
 extern "C" int brov_plant_step(brov_solver* s, double dt, int substeps, void* stream) {
     if (!s || !(dt > 0.0) || substeps < 1) return BROV_ERR_ARG;
-    if (int rc = wrench_tick_ok(s, s->wr_tick, "brov_plant_step")) return rc;
+    if (int rc = s->wr.steps_ok(1, g_err, "brov_plant_step")) return rc;
     HIPCHK(hipSetDevice(s->device));
     if (int rc = order_behind_last(s, (hipStream_t)stream)) return rc;
     ensure_plant_params(s, (hipStream_t)stream);
@@ -976,66 +935,18 @@ static int launch_ticks(brov_solver* s, int family, int n, int64_t row_stride_do
 }
 
 static int ticks_kernel(const brov_solver* s);
-// DEVICE logs of a run of consecutive ticks, entry j = tick j of the run (x: the plant state AFTER it, behind `lead` rows that belong to the
-// owner); a null block is not logged.  The whole-loop logs of brov_closed_loop_ex / _dob and the one-chunk logs of brov_closed_loop_track are
-// both allocated, handed to the tick runners and freed so.
-struct TickLogs {
-    size_t B = 0, lead = 0;
-    double *dx = nullptr, *du = nullptr, *dw = nullptr, *de = nullptr;
-    int* dst = nullptr;
-    DeviceAllocs mem;
-    double* x(int j) const { return dx ? dx + ((size_t)j + lead) * B * 12 : nullptr; }
-    double* u(int j) const { return du ? du + (size_t)j * B * 4 : nullptr; }
-    double* w(int j) const { return dw ? dw + (size_t)j * B * 6 : nullptr; }
-    double* est(int j) const { return de ? de + (size_t)j * B * 6 : nullptr; }
-    int* status(int j) const { return dst ? dst + (size_t)j * B : nullptr; }
-    // the blocks asked for, for `n` ticks of `B_` instances
-    int alloc(size_t B_, size_t n, size_t lead_, bool x_, bool u_, bool st_, bool w_, bool est_, const char* who) {
-        B = B_; lead = lead_;
-        int rc = BROV_OK;
-        if (x_) rc = mem.alloc(&dx, (n + lead) * B * 12, g_err);
-        if (u_ && rc == BROV_OK) rc = mem.alloc(&du, n * B * 4, g_err);
-        if (st_ && rc == BROV_OK) rc = mem.alloc(&dst, n * B, g_err);
-        if (w_ && rc == BROV_OK) rc = mem.alloc(&dw, n * B * 6, g_err);
-        if (est_ && rc == BROV_OK) rc = mem.alloc(&de, n * B * 6, g_err);
-        if (rc != BROV_OK) g_err = std::string(who) + ": " + g_err;
-        return rc;
-    }
-    void free() { mem.free_all(); }
-};
-// The whole-loop logs of brov_closed_loop_ex / _dob: a device block per HOST log the caller asked for and, ahead of the states, the start
-// state; that and the zeroed wrench log are enqueued on the loop's stream, everything is copied back after the loop's one host wait.  Logs come
-// back only from a loop that completed: a failing call leaves the caller's arrays as they were.
-struct LoopLogs {
-    TickLogs T;
-    size_t ticks = 0;
-    double *hx = nullptr, *hu = nullptr, *hw = nullptr, *he = nullptr;   // HOST
-    int32_t* hst = nullptr;
-    int begin(const brov_solver* s, int ticks_, double* u_log, double* x_log, int32_t* st_log, double* w_log, double* est_log, hipStream_t st,
-              const char* who) {
-        ticks = ticks_; hx = x_log; hu = u_log; hst = st_log; hw = w_log; he = est_log;
-        if (int rc = T.alloc(s->B, ticks, 1, hx, hu, hst, hw, he, who)) return rc;
-        const size_t B = T.B;
-        hipError_t e = hipSuccess;
-        if (T.dw) e = hipMemsetAsync(T.dw, 0, ticks * B * 6 * sizeof(double), st);   // (mode OFF: no wrench, nothing writes it)
-        if (T.dx && e == hipSuccess) e = hipMemcpyAsync(T.dx, s->x0, B * 12 * sizeof(double), hipMemcpyDeviceToDevice, st);
-        if (e != hipSuccess) { g_err = std::string(who) + ": log initialisation failed"; return BROV_ERR_HIP; }
-        return BROV_OK;
-    }
-    // after the host wait: copies back when the loop succeeded, frees in any case; returns rc
-    int end(int rc) {
-        const size_t B = T.B;
-        if (rc == BROV_OK) {
-            if (T.dx) hipMemcpy(hx, T.dx, (ticks + 1) * B * 12 * sizeof(double), hipMemcpyDeviceToHost);
-            if (T.du) hipMemcpy(hu, T.du, ticks * B * 4 * sizeof(double), hipMemcpyDeviceToHost);
-            if (T.dst) hipMemcpy(hst, T.dst, ticks * B * sizeof(int), hipMemcpyDeviceToHost);
-            if (T.dw) hipMemcpy(hw, T.dw, ticks * B * 6 * sizeof(double), hipMemcpyDeviceToHost);
-            if (T.de) hipMemcpy(he, T.de, ticks * B * 6 * sizeof(double), hipMemcpyDeviceToHost);
-        }
-        T.free();
-        return rc;
-    }
-};
+// The columns of the solver's loop logs (LoopLog, host_common.hpp), entry j = tick j of the run: the plant state AFTER the tick, the applied
+// input, the status, the applied wrench, the observer's estimate.  A whole loop (brov_closed_loop_ex / _dob) has a column per HOST log the
+// caller asked for, the states behind the start state; a chunk of brov_closed_loop_track has x, u and status on the device alone.
+enum { LOG_X, LOG_U, LOG_ST, LOG_W, LOG_EST };
+static void declare_logs(LoopLog& L, double* x, double* u, int32_t* st, double* w, double* est, bool chunk) {
+    L.column(12, x, chunk ? 0 : 1, chunk); L.column(4, u, 0, chunk); L.column(1, st, 0, chunk); L.column(6, w); L.column(6, est);
+}
+// a whole loop's logs on `st`: allocated, the start state ahead of the states, and the wrench log zeroed where no wrench kernel writes it
+static int begin_logs(LoopLog& L, const brov_solver* s, int ticks, hipStream_t st, const std::string& pre) {
+    if (int rc = L.alloc(s->B, ticks, g_err, pre)) return rc;
+    return L.init(s->x0, s->wr.off() ? LOG_W : -1, st, g_err, pre);
+}
 // what the closed-loop entry points ask of their arguments alike, reported under the caller's name (an observer and an estimator are optional
 // here; brov_closed_loop_dob asks for its observer itself)
 static int loop_args_ok(const brov_solver* s, const brov_ekf* e, const brov_rls* r, int rls_mode, int ticks, int ncols, double dt, int substeps,
@@ -1047,18 +958,11 @@ static int loop_args_ok(const brov_solver* s, const brov_ekf* e, const brov_rls*
     }
     if ((e && brov_ekf_batch(e) != s->B) || (r && brov_rls_batch(r) != s->B)) { g_err = std::string(who) + ": batch sizes differ"; return BROV_ERR_ARG; }
     if (r && rls_mode != BROV_RLS_APPLY_DISTURBANCE && rls_mode != BROV_RLS_APPLY_MODEL) { g_err = std::string(who) + ": unknown rls_mode"; return BROV_ERR_ARG; }
-    return wrench_tick_ok(s, s->wr_tick + ticks - 1, who);
+    return s->wr.steps_ok(ticks, g_err, who);
 }
 // the statuses of the step just enqueued on `st` into a DEVICE log row (null: not logged)
 static void gather_status(const brov_solver* s, int* out, hipStream_t st) {
     if (out) hipLaunchKernelGGL(gather_status_kernel, dim3((unsigned)((s->B + 255) / 256)), dim3(256), 0, st, s->res, out, (int)s->B);
-}
-// the end of a closed loop: its one host wait, then a launch error nobody has picked up, then the code
-static int finish_loop(hipStream_t st, int rc) {
-    hipError_t err = hipStreamSynchronize(st);
-    if (rc == BROV_OK && err == hipSuccess) err = hipGetLastError();
-    if (rc == BROV_OK && err != hipSuccess) { g_err = hipGetErrorString(err); rc = BROV_ERR_HIP; }
-    return rc;
 }
 // whether brov_closed_loop_ex runs `ticks` ticks from `line0` as one launch, and with which kernel.
 // One launch for the whole loop where the fused kernels serve the solver and every window is rows of the table in place (round 5,
@@ -1069,32 +973,32 @@ static int finish_loop(hipStream_t st, int rc) {
 static bool loop_in_one_launch(const brov_solver* s, int ticks, int line0, int ncols, int* which) {
     *which = ticks_kernel(s);
     return s->k.closed_loop_fused && ncols == 16 && line0 >= 0 && line0 + (ticks - 1) + s->N <= s->traj_rows - 1 && *which != 0 &&
-           s->wr.mode == BROV_WRENCH_OFF;
+           s->wr.off();
 }
-// `n` ticks of the plain loop (window -> RTI step -> plant step) from trajectory row `line` on `st`, logged into T
-static int run_loop_ticks(brov_solver* s, int n, int line, int ncols, double dt, int substeps, bool one_launch, int which, const TickLogs& T,
+// `n` ticks of the plain loop (window -> RTI step -> plant step) from trajectory row `line` on `st`, logged into L
+static int run_loop_ticks(brov_solver* s, int n, int line, int ncols, double dt, int substeps, bool one_launch, int which, const LoopLog& L,
                           hipStream_t st) {
     int rc = BROV_OK;
     if (one_launch) {
         rc = brov_set_yref_from_traj(s, line, 16, st);
-        const PlantInLaunch plant{dt, substeps, T.x(0), T.u(0)};
-        if (rc == BROV_OK) rc = launch_ticks(s, which, n, 16, T.status(0), &plant, st);
-        if (rc == BROV_OK) s->wr_tick += n;
+        const PlantInLaunch plant{dt, substeps, L.row<double>(LOG_X, 0), L.row<double>(LOG_U, 0)};
+        if (rc == BROV_OK) rc = launch_ticks(s, which, n, 16, L.row<int32_t>(LOG_ST, 0), &plant, st);
+        if (rc == BROV_OK) s->wr.tick += n;
     }
     for (int k = 0; k < n && rc == BROV_OK && !one_launch; k++) {
         forget_traj_window(s);
         launch_window(s->traj, s->traj_rows, nullptr, line + k, 1, s->N, ncols, s->yref_sh, st);
         s->yref_shared = true;
         rc = brov_solve_phase(s, st, 0);
-        gather_status(s, T.status(k), st);
-        plant_step_on(s, dt, substeps, T.x(k), T.u(k), T.w(k), st);
+        gather_status(s, L.row<int32_t>(LOG_ST, k), st);
+        plant_step_on(s, dt, substeps, L.row<double>(LOG_X, k), L.row<double>(LOG_U, k), L.row<double>(LOG_W, k), st);
     }
     return rc;
 }
 // `n` ticks of the DOB / AMPC loop from trajectory row `line` on `st`: per tick the five public calls of the header.  The observer's and the
 // estimator's calls report through their own error strings: their code is handed on, their text copied behind `who`
 static int run_dob_ticks(brov_solver* s, brov_ekf* e, brov_rls* r, int rls_mode, int n, int line, int ncols, double dt, int substeps,
-                         const TickLogs& T, hipStream_t st, const char* who) {
+                         const LoopLog& L, hipStream_t st, const char* who) {
     const size_t B = s->B;
     int rc = BROV_OK;
     auto sub = [&](int code, const char* text) {
@@ -1105,11 +1009,11 @@ static int run_dob_ticks(brov_solver* s, brov_ekf* e, brov_rls* r, int rls_mode,
         rc = brov_set_yref_from_traj(s, line + k, ncols, st);
         if (rc == BROV_OK) rc = brov_solve_phase(s, st, 0);
         if (rc != BROV_OK) break;
-        gather_status(s, T.status(k), st);
+        gather_status(s, L.row<int32_t>(LOG_ST, k), st);
         ensure_plant_params(s, st);   // (the hand-off below rewrites the controller's stage 0, which a plant without parameters of its own follows)
-        plant_step_on(s, dt, substeps, T.x(k), T.u(k), T.w(k), st);
+        plant_step_on(s, dt, substeps, L.row<double>(LOG_X, k), L.row<double>(LOG_U, k), L.row<double>(LOG_W, k), st);
         if (!sub(brov_ekf_update_from_solver(e, s, st), brov_ekf_last_error())) break;
-        if (T.est(k)) launch_gather_cols(brov_ekf_x_device(e), (int)B, 18, 12, 6, T.est(k), st);
+        if (double* est = L.row<double>(LOG_EST, k)) launch_gather_cols(brov_ekf_x_device(e), (int)B, 18, 12, 6, est, st);
         if (!r) sub(brov_ekf_apply_to_solver(e, s, st), brov_ekf_last_error());
         else if (sub(brov_rls_update_from_ekf(r, e, s, st), brov_rls_last_error())) sub(brov_rls_apply_to_solver(r, s, rls_mode, st), brov_rls_last_error());
     }
@@ -1125,12 +1029,13 @@ extern "C" int brov_closed_loop_ex(brov_solver* s, int ticks, int line0, int nco
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = s->last_stream;
     ensure_plant_params(s, st);
-    LoopLogs L;
-    int rc = L.begin(s, ticks, u_log, x_log, st_log, w_log, nullptr, st, "brov_closed_loop");
+    LoopLog L;
+    declare_logs(L, x_log, u_log, st_log, w_log, nullptr, false);
+    int rc = begin_logs(L, s, ticks, st, "brov_closed_loop: ");
     int which = 0;
     const bool one_launch = loop_in_one_launch(s, ticks, line0, ncols, &which);
-    if (rc == BROV_OK) rc = run_loop_ticks(s, ticks, line0, ncols, dt, substeps, one_launch, which, L.T, st);
-    return L.end(finish_loop(st, rc));
+    if (rc == BROV_OK) rc = run_loop_ticks(s, ticks, line0, ncols, dt, substeps, one_launch, which, L, st);
+    return L.deliver(finish_loop(st, rc, g_err, ""), g_err, "brov_closed_loop: ");
 }
 
 // The DOB / AMPC loop on the device: per tick the five public calls of the header, on one stream, one host wait at the end.
@@ -1140,10 +1045,11 @@ extern "C" int brov_closed_loop_dob(brov_solver* s, brov_ekf* e, brov_rls* r, in
     if (int rc = loop_args_ok(s, e, r, rls_mode, ticks, ncols, dt, substeps, "brov_closed_loop_dob")) return rc;
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = s->last_stream;
-    LoopLogs L;
-    int rc = L.begin(s, ticks, u_log, x_log, st_log, w_log, est_log, st, "brov_closed_loop_dob");
-    if (rc == BROV_OK) rc = run_dob_ticks(s, e, r, rls_mode, ticks, line0, ncols, dt, substeps, L.T, st, "brov_closed_loop_dob");
-    return L.end(finish_loop(st, rc));
+    LoopLog L;
+    declare_logs(L, x_log, u_log, st_log, w_log, est_log, false);
+    int rc = begin_logs(L, s, ticks, st, "brov_closed_loop_dob: ");
+    if (rc == BROV_OK) rc = run_dob_ticks(s, e, r, rls_mode, ticks, line0, ncols, dt, substeps, L, st, "brov_closed_loop_dob");
+    return L.deliver(finish_loop(st, rc, g_err, ""), g_err, "brov_closed_loop_dob: ");
 }
 
 namespace brov {
@@ -1164,20 +1070,20 @@ extern "C" int brov_closed_loop_track(brov_solver* s, brov_ekf* e, brov_rls* r, 
     int which = 0;
     const bool one_launch = !e && loop_in_one_launch(s, ticks, line0, ncols, &which);   // decided for the whole run, as brov_closed_loop_ex does
     const int C = std::min(chunk == 0 ? 64 : chunk, ticks);
-    TickLogs T;
-    int rc = T.alloc(s->B, C, 0, true, true, true, false, false, "brov_closed_loop_track");
+    LoopLog L;   // one chunk, on the device alone
+    declare_logs(L, nullptr, nullptr, nullptr, nullptr, nullptr, true);
+    int rc = L.alloc(s->B, C, g_err, "brov_closed_loop_track: ");
     for (int k0 = 0; k0 < ticks && rc == BROV_OK; k0 += C) {
         const int n = std::min(C, ticks - k0);
-        rc = e ? run_dob_ticks(s, e, r, rls_mode, n, line0 + k0, ncols, dt, substeps, T, st, "brov_closed_loop_track")
-               : run_loop_ticks(s, n, line0 + k0, ncols, dt, substeps, one_launch, which, T, st);
+        rc = e ? run_dob_ticks(s, e, r, rls_mode, n, line0 + k0, ncols, dt, substeps, L, st, "brov_closed_loop_track")
+               : run_loop_ticks(s, n, line0 + k0, ncols, dt, substeps, one_launch, which, L, st);
         if (rc != BROV_OK) break;
         // the state after tick k against row line0 + k + 1, by the solver's bounds of the moment
-        rc = track_accumulate_on(t, T.dx, T.du, T.dst, n, s->traj, s->traj_rows, line0 + k0 + 1, s->opts.lbu, s->opts.ubu, st);
+        rc = track_accumulate_on(t, L.row<double>(LOG_X, 0), L.row<double>(LOG_U, 0), L.row<int32_t>(LOG_ST, 0), n, s->traj, s->traj_rows,
+                                 line0 + k0 + 1, s->opts.lbu, s->opts.ubu, st);
         if (rc != BROV_OK) g_err = std::string("brov_closed_loop_track: ") + brov_track_last_error();
     }
-    rc = finish_loop(st, rc);
-    T.free();
-    return rc;
+    return finish_loop(st, rc, g_err, "");
 }
 
 extern "C" int brov_set_iterate_host(brov_solver* s, const double* x, const double* u, const double* pi, const double* lam) {

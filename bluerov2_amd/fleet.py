@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from .solver import RESULT_DTYPE, _Handle, _arr, _arr_opt, _bind, _dp, _load
+from .solver import RESULT_DTYPE, _Handle, _Wrench, _arr, _bind, _dp, _load
 
 
 def _protos(L):
@@ -107,52 +107,31 @@ class Fleet(_Handle):
         return (u, x, st, win) if log else None
 
     # ---- the fleet under disturbance (brov_vehicle_*) -------------------------------------------------------------------------------
+    _wrench = property(lambda self: _Wrench(self, "brov_vehicle_wrench_", self.V, "set_wrench"))
+
     def set_wrench(self, constant=None, periodic=None, table=None, gain=None):
         """the vehicles' world-frame wrench, BatchSolver.set_plant_wrench at batch V: exactly one of
             constant=w         [6] or [V, 6], world frame [fx fy fz tx ty tz]
             periodic=dict(seed=0, scale=6.0, phase0=0.0, dphi=0.125, tz_div=3.0)   (any subset)
             table=tab          [rows, 6], row min(tick, rows - 1); gain=[V] scales it per vehicle"""
-        if (constant is not None) + (periodic is not None) + (table is not None) != 1:
-            raise ValueError("set_wrench takes exactly one of constant=, periodic=, table=")
-        if gain is not None and table is None:
-            raise ValueError("gain= goes with table=")
-        if constant is not None:
-            w = np.ascontiguousarray(constant, dtype=np.float64)
-            if w.shape == (6,):
-                w = np.ascontiguousarray(np.broadcast_to(w, (self.V, 6)))
-            self._chk(self._L.brov_vehicle_wrench_constant_host(self._h, _dp(_arr(w, (self.V, 6)))), "wrench_constant")
-        elif periodic is not None:
-            kw = dict(seed=0, scale=6.0, phase0=0.0, dphi=0.125, tz_div=3.0)
-            unknown = set(periodic) - set(kw)
-            if unknown:
-                raise ValueError(f"unknown periodic wrench parameters {sorted(unknown)}")
-            kw.update(periodic)
-            self._chk(self._L.brov_vehicle_wrench_periodic(self._h, int(kw["seed"]) & 0xFFFFFFFFFFFFFFFF, float(kw["scale"]), float(kw["phase0"]),
-                                                           float(kw["dphi"]), float(kw["tz_div"])), "wrench_periodic")
-        else:
-            tab = np.ascontiguousarray(table, dtype=np.float64)
-            if tab.ndim != 2 or tab.shape[1] != 6 or tab.shape[0] < 1:
-                raise ValueError("wrench table must be [rows][6]")
-            self._chk(self._L.brov_vehicle_wrench_table_host(self._h, _dp(tab), tab.shape[0], _dp(_arr_opt(gain, (self.V,)))), "wrench_table")
+        self._wrench.set(constant, periodic, table, gain)
 
     def wrench_off(self):
-        self._chk(self._L.brov_vehicle_wrench_off(self._h), "wrench_off")
+        self._wrench.call("off")
 
     def wrench_mode(self):
-        return int(self._L.brov_vehicle_wrench_mode(self._h))
+        return self._wrench.get("mode")
 
     def wrench(self, tick):
         """[V, 6]: the wrench of every vehicle at `tick`, evaluated by the device generator (moves nothing; zeros while off)"""
-        w = np.empty((self.V, 6))
-        self._chk(self._L.brov_vehicle_wrench_eval_host(self._h, int(tick), _dp(w)), "wrench_eval")
-        return w
+        return self._wrench.eval(tick)
 
     def wrench_seek(self, tick):
-        self._chk(self._L.brov_vehicle_wrench_seek(self._h, int(tick)), "wrench_seek")
+        self._wrench.call("seek", int(tick))
 
     def wrench_tick(self):
         """the tick counter: fleet steps since the last reset or seek (step and every closed-loop tick add one)"""
-        return int(self._L.brov_vehicle_wrench_tick(self._h))
+        return self._wrench.get("tick")
 
     def observe(self, ekf, dt=0.05, stream=0):
         """one tick of the observer `ekf` (BatchEkf of batch V) on the vehicles' states, the inputs they were given and (v - v_prev) / dt"""

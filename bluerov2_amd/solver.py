@@ -225,6 +225,47 @@ def thrust_allocation(u0):
                      -u0[..., 2] / c, -u0[..., 2] / c], axis=-1)
 
 
+class _Wrench:
+    """The world-frame wrench generator of `owner` through the entry points `prefix`* of the C ABI, written once for BatchSolver
+    (brov_plant_wrench_, one wrench per instance) and Fleet (brov_vehicle_wrench_, one per vehicle): `batch` wrenches, `name` the owner's
+    public setter, which the texts of the exceptions cite.  Made per call: it keeps the owner alive no longer than that."""
+
+    def __init__(self, owner, prefix, batch, name):
+        self.o, self.prefix, self.batch, self.name = owner, prefix, batch, name
+
+    def call(self, op, *args):   # a failure is reported as e.g. "plant_wrench_constant failed (-1): ..."
+        self.o._chk(getattr(self.o._L, self.prefix + op)(self.o._h, *args), self.name[4:] + "_" + op.replace("_host", ""))
+
+    def set(self, constant, periodic, table, gain):
+        if (constant is not None) + (periodic is not None) + (table is not None) != 1:
+            raise ValueError(f"{self.name} takes exactly one of constant=, periodic=, table=")
+        if gain is not None and table is None:
+            raise ValueError("gain= goes with table=")
+        if constant is not None:
+            w = np.asarray(constant, dtype=np.float64)   # one wrench [6] for all, or [batch, 6]
+            self.call("constant_host", _dp(_arr(np.broadcast_to(w, (self.batch, 6)) if w.shape == (6,) else w, (self.batch, 6))))
+        elif periodic is not None:
+            kw = dict(seed=0, scale=6.0, phase0=0.0, dphi=0.125, tz_div=3.0)
+            unknown = set(periodic) - set(kw)
+            if unknown:
+                raise ValueError(f"unknown periodic wrench parameters {sorted(unknown)}")
+            kw.update(periodic)
+            self.call("periodic", int(kw["seed"]) & 0xFFFFFFFFFFFFFFFF, float(kw["scale"]), float(kw["phase0"]), float(kw["dphi"]), float(kw["tz_div"]))
+        else:
+            tab = np.ascontiguousarray(table, dtype=np.float64)
+            if tab.ndim != 2 or tab.shape[1] != 6 or tab.shape[0] < 1:
+                raise ValueError("wrench table must be [rows][6]")
+            self.call("table_host", _dp(tab), tab.shape[0], _dp(_arr_opt(gain, (self.batch,))))
+
+    def get(self, what):   # "mode" or "tick"
+        return int(getattr(self.o._L, self.prefix + what)(self.o._h))
+
+    def eval(self, tick):
+        w = np.empty((self.batch, 6))
+        self.call("eval_host", int(tick), _dp(w))
+        return w
+
+
 class BatchSolver(_Handle):
     """B independent BlueROV2 OCP instances resident on one GPU; one solve() = one RTI step of each."""
 
@@ -465,53 +506,31 @@ class BatchSolver(_Handle):
                                                   int(substeps), int(chunk)), "closed_loop_track")
 
     # ---- time-varying world-frame wrench on the plant (bluerov2_dob.cpp:754-892, applyBodyWrench) ------------------------------
+    _wrench = property(lambda self: _Wrench(self, "brov_plant_wrench_", self.B, "set_plant_wrench"))
+
     def set_plant_wrench(self, constant=None, periodic=None, table=None, gain=None):
         """exactly one of
             constant=w         [6] or [B, 6], world frame [fx fy fz tx ty tz]; the reference's mode 1 is (10, 10, 10, 0, 0, 0)
             periodic=dict(seed=0, scale=6.0, phase0=0.0, dphi=0.125, tz_div=3.0)   (any subset; dphi = 0.025 is the AMPC node's)
             table=tab          [rows, 6], row min(tick, rows - 1); gain=[B] scales it per instance"""
-        if (constant is not None) + (periodic is not None) + (table is not None) != 1:
-            raise ValueError("set_plant_wrench takes exactly one of constant=, periodic=, table=")
-        if gain is not None and table is None:
-            raise ValueError("gain= goes with table=")
-        if constant is not None:
-            w = np.ascontiguousarray(constant, dtype=np.float64)
-            if w.shape == (6,):
-                w = np.ascontiguousarray(np.broadcast_to(w, (self.B, 6)))
-            self._chk(self._L.brov_plant_wrench_constant_host(self._h, _dp(_arr(w, (self.B, 6)))), "plant_wrench_constant")
-        elif periodic is not None:
-            kw = dict(seed=0, scale=6.0, phase0=0.0, dphi=0.125, tz_div=3.0)
-            unknown = set(periodic) - set(kw)
-            if unknown:
-                raise ValueError(f"unknown periodic wrench parameters {sorted(unknown)}")
-            kw.update(periodic)
-            self._chk(self._L.brov_plant_wrench_periodic(self._h, int(kw["seed"]) & 0xFFFFFFFFFFFFFFFF, float(kw["scale"]), float(kw["phase0"]),
-                                                         float(kw["dphi"]), float(kw["tz_div"])), "plant_wrench_periodic")
-        else:
-            tab = np.ascontiguousarray(table, dtype=np.float64)
-            if tab.ndim != 2 or tab.shape[1] != 6 or tab.shape[0] < 1:
-                raise ValueError("wrench table must be [rows][6]")
-            g = _arr_opt(gain, (self.B,))
-            self._chk(self._L.brov_plant_wrench_table_host(self._h, _dp(tab), tab.shape[0], _dp(g)), "plant_wrench_table")
+        self._wrench.set(constant, periodic, table, gain)
 
     def plant_wrench_off(self):
-        self._chk(self._L.brov_plant_wrench_off(self._h), "plant_wrench_off")
+        self._wrench.call("off")
 
     def plant_wrench_mode(self):
-        return int(self._L.brov_plant_wrench_mode(self._h))
+        return self._wrench.get("mode")
 
     def plant_wrench(self, tick):
         """[B, 6]: the wrench of every instance at `tick`, evaluated by the device generator (moves nothing)"""
-        w = np.empty((self.B, 6))
-        self._chk(self._L.brov_plant_wrench_eval_host(self._h, int(tick), _dp(w)), "plant_wrench_eval")
-        return w
+        return self._wrench.eval(tick)
 
     def plant_wrench_seek(self, tick):
-        self._chk(self._L.brov_plant_wrench_seek(self._h, int(tick)), "plant_wrench_seek")
+        self._wrench.call("seek", int(tick))
 
     def plant_wrench_tick(self):
         """the tick counter: plant steps so far (plant_step and every closed-loop tick add one)"""
-        return int(self._L.brov_plant_wrench_tick(self._h))
+        return self._wrench.get("tick")
 
     # ---- iterate ----------------------------------------------------------------------------------------------
     def set_iterate(self, x=None, u=None, pi=None, lam=None):

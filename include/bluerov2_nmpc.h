@@ -677,7 +677,8 @@ int  brov_fleet_last_seconds(brov_fleet* f, double* select_seconds);
  * its instance index: vehicle v draws what instance v of a solver of batch V draws under the same settings.  The tick counter counts fleet
  * steps: +1 in every brov_fleet_step and in every tick of the fleet's loops, whatever the mode; brov_fleet_reset sets it to 0,
  * brov_vehicle_wrench_seek to `tick`.  Arguments are checked as the solver's are (tz_div != 0, rows >= 1, the periodic half-period index of
- * every tick a call will touch below 2^22: a step or a loop that would leave that range is refused before anything runs).  The constant and
+ * every tick a call will touch below 2^22: a step or a loop that would leave that range is refused before anything runs) -- both families go
+ * through one function, so a refusal of either has BROV_ERR_ARG and a text that begins with the entry point's name.  The constant and
  * table buffers are copies the fleet keeps until the next upload.  Mode OFF (the default): brov_fleet_step launches the plant kernel it
  * always launched. */
 int brov_vehicle_wrench_constant_host(brov_fleet* f, const double* w /*[V][6]*/);
