@@ -3,13 +3,18 @@
 // given last, the winners of the last select, the vehicles' true parameters, the world-frame wrench every vehicle is under (brov_vehicle_wrench_*:
 // the solver's generator at batch V, instance index v) and what a disturbance observer of batch V is fed from (brov_vehicle_observe).  It
 // reaches the solver through its public calls (brov_order_stream, brov_set_yref_candidates, brov_solve, the DEVICE pointers) and solver_view()
-// of host_common.hpp, the observer through brov_ekf_update_device and brov_ekf_mpc_p_device.
+// of host_common.hpp, the observer through brov_ekf_update_device and brov_ekf_mpc_p_device.  The inter-vehicle clearance term
+// (brov_clearance_*; kernels: clearance_kernel.hip) lives here too: its plan, buffers and statistics are the fleet's, and a step with the term on
+// re-scores the records ahead of the select and publishes the plan behind it.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
+#include <limits>
 #include <string>
+#include <vector>
 
+#include "clearance_kernel.hpp"
 #include "fleet_kernel.hpp"
 #include "host_common.hpp"
 #include "nmpc_device.hpp"
@@ -36,6 +41,19 @@ struct brov_fleet {
     WrenchSource wr;
     double* vprev = nullptr;           // [V][6] velocities at the last brov_vehicle_observe (zeros after reset)
     double *y12 = nullptr, *thrust = nullptr, *acc = nullptr;   // [V][12], [V][6], [V][6] the observer's inputs
+    // the inter-vehicle clearance term (brov_clearance_*), its buffers reserved at create; off by default
+    struct Clearance {
+        bool on = false;
+        double radius = 0.0, weight = 0.0, r2 = 0.0;
+        int shift = 0, slices = 1;
+        double* plan = nullptr;        // [N+1][V][3] stage-major: the positions of the path every vehicle committed to last
+        double* part = nullptr;        // [kClearanceMaxSlices][B], [slices][B] used: the distance kernel's minima per slice of the peer range
+        double* d2min = nullptr;       // [B] of the last step or brov_clearance_eval_host
+        brov_result* rec = nullptr;    // [B] the re-scored records a step selects from
+        double *last_d2 = nullptr, *min_d2 = nullptr;   // [V] statistics
+        int32_t* below = nullptr;      // [V]
+        KernelTimer timer;             // around the last distance kernel
+    } cl;
     hipStream_t last_stream = nullptr;
     KernelTimer timer;                 // around the last select kernel
     hipEvent_t ev_done = nullptr;      // behind the last enqueued work
@@ -52,6 +70,7 @@ extern "C" void brov_fleet_destroy(brov_fleet* f) {
     f->mem.free_all();
     f->wr.destroy();
     f->timer.destroy();
+    f->cl.timer.destroy();
     if (f->ev_done) (void)hipEventDestroy(f->ev_done);
     delete f;
 }
@@ -86,6 +105,22 @@ static int wait_all(brov_fleet* f, const char* who) {
     return BROV_OK;
 }
 
+// the plan of a fleet that has not planned yet: every vehicle stays where it is (every stage := the position of xv[v], HOST [V][12]);
+// the statistics as before the first step.  The caller has waited for everything that may touch the buffers.
+static int clearance_hold(brov_fleet* f, const double* xv) {
+    const size_t V = (size_t)f->V, K = (size_t)f->N + 1;
+    std::vector<double> plan(K * V * 3);
+    for (size_t k = 0; k < K; k++)
+        for (size_t v = 0; v < V; v++)
+            for (size_t j = 0; j < 3; j++) plan[(k * V + v) * 3 + j] = xv[v * 12 + j];
+    HIPCHK(hipMemcpy(f->cl.plan, plan.data(), plan.size() * sizeof(double), hipMemcpyHostToDevice));
+    const std::vector<double> last(V, -1.0), lowest(V, std::numeric_limits<double>::infinity());
+    HIPCHK(hipMemcpy(f->cl.last_d2, last.data(), V * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(f->cl.min_d2, lowest.data(), V * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(f->cl.below, 0, V * sizeof(int32_t)));
+    return BROV_OK;
+}
+
 extern "C" int brov_fleet_reset(brov_fleet* f) {
     if (!f) { g_fleet_err = "brov_fleet_reset: null argument"; return BROV_ERR_ARG; }
     HIPCHK(hipSetDevice(f->device));
@@ -98,7 +133,9 @@ extern "C" int brov_fleet_reset(brov_fleet* f) {
     HIPCHK(hipMemcpy2D(f->xv, 12 * sizeof(double), brov_x0_device(f->s), (size_t)f->C * 12 * sizeof(double), 12 * sizeof(double), (size_t)f->V,
                        hipMemcpyDeviceToDevice));
     f->wr.tick = 0;
-    return BROV_OK;
+    std::vector<double> xv((size_t)f->V * 12);
+    HIPCHK(hipMemcpy(xv.data(), f->xv, xv.size() * sizeof(double), hipMemcpyDeviceToHost));
+    return clearance_hold(f, xv.data());
 }
 
 extern "C" int brov_fleet_create(brov_fleet** out, brov_solver* s, int candidates) {
@@ -126,10 +163,18 @@ extern "C" int brov_fleet_create(brov_fleet** out, brov_solver* s, int candidate
     if (rc == BROV_OK) rc = f->mem.alloc(&f->y12, V * 12, g_fleet_err);
     if (rc == BROV_OK) rc = f->mem.alloc(&f->thrust, V * 6, g_fleet_err);
     if (rc == BROV_OK) rc = f->mem.alloc(&f->acc, V * 6, g_fleet_err);
+    f->cl.slices = clearance_slices(B, f->V);
+    if (rc == BROV_OK) rc = f->mem.alloc(&f->cl.plan, ((size_t)f->N + 1) * V * 3, g_fleet_err);
+    if (rc == BROV_OK) rc = f->mem.alloc(&f->cl.part, (size_t)kClearanceMaxSlices * B, g_fleet_err);   // (brov_clearance_dev_set_slices may raise the count)
+    if (rc == BROV_OK) rc = f->mem.alloc(&f->cl.d2min, (size_t)B, g_fleet_err);
+    if (rc == BROV_OK) rc = f->mem.alloc(&f->cl.rec, (size_t)B, g_fleet_err);
+    if (rc == BROV_OK) rc = f->mem.alloc(&f->cl.last_d2, V, g_fleet_err);
+    if (rc == BROV_OK) rc = f->mem.alloc(&f->cl.min_d2, V, g_fleet_err);
+    if (rc == BROV_OK) rc = f->mem.alloc(&f->cl.below, V, g_fleet_err);
     f->wr.B = V;
     if (rc == BROV_OK) rc = f->wr.reserve(f->mem, g_fleet_err);   // eager: a step reads the eval buffer without a host wait
     if (rc != BROV_OK) { g_fleet_err = "brov_fleet_create: " + g_fleet_err; brov_fleet_destroy(f); return rc; }
-    if (f->timer.create() != hipSuccess || hipEventCreateWithFlags(&f->ev_done, hipEventDisableTiming) != hipSuccess) {
+    if (f->timer.create() != hipSuccess || f->cl.timer.create() != hipSuccess || hipEventCreateWithFlags(&f->ev_done, hipEventDisableTiming) != hipSuccess) {
         g_fleet_err = "brov_fleet_create: device initialisation failed";
         brov_fleet_destroy(f);
         return BROV_ERR_HIP;
@@ -147,7 +192,7 @@ extern "C" int brov_fleet_set_state_host(brov_fleet* f, const double* xv) {
     launch_fleet_bcast(f->xv, f->V, f->C, brov_x0_device(f->s), nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(nullptr));
-    return BROV_OK;
+    return clearance_hold(f, xv);
 }
 
 extern "C" int brov_fleet_get_state_host(brov_fleet* f, double* xv) {
@@ -245,11 +290,27 @@ static int plant_modes_ok(const brov_fleet* f, const char* who) {
     return BROV_OK;
 }
 
+// the two clearance kernels on `st` (ordered by the caller) against the plan as it stands: the distance kernel, timed, then the fold of its
+// slices into d2min and, with `out`, the re-scored records
+static int clearance_on(brov_fleet* f, const double* x, const brov_result* rec, double* d2min, brov_result* out, hipStream_t st) {
+    HIPCHK(f->cl.timer.start(st));
+    launch_clearance_dist(x, f->cl.plan, f->B, f->V, f->C, f->N, f->cl.shift, f->cl.slices, f->cl.part, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(f->cl.timer.stop(st));
+    launch_clearance_rescore(f->cl.part, f->cl.slices, f->B, rec, f->cl.r2, f->cl.weight, d2min, out, st);
+    HIPCHK(hipGetLastError());
+    return BROV_OK;
+}
+
 // select + plant + broadcast on `st` (ordered by the caller, who has checked the wrench tick), with optional DEVICE log rows of this tick.
 // Under a wrench mode the wrench of the tick is evaluated into wlog's row (or the source's eval buffer): the plant's input and the log row are one.
 static int step_on(brov_fleet* f, const brov_result* rec, double dt, int substeps, double* xlog, double* ulog, int32_t* stlog, int32_t* winlog,
                    double* wlog, hipStream_t st) {
     if (!rec) rec = brov_results_device(f->s);
+    if (f->cl.on) {   // the candidates priced by their clearance from the other vehicles' plans: the select, the plant and the logs see these records
+        if (int rc = clearance_on(f, brov_x_device(f->s), rec, f->cl.d2min, f->cl.rec, st)) return rc;
+        rec = f->cl.rec;
+    }
     if (int rc = select_on(f, rec, f->winner, nullptr, st)) return rc;
     FleetPlantArgs a;
     a.V = f->V; a.C = f->C; a.xv = f->xv; a.res = rec; a.winner = f->winner;
@@ -268,6 +329,11 @@ static int step_on(brov_fleet* f, const brov_result* rec, double dt, int substep
     HIPCHK(hipGetLastError());
     launch_fleet_bcast(f->xv, f->V, f->C, brov_x0_device(f->s), st);
     HIPCHK(hipGetLastError());
+    if (f->cl.on) {   // behind the select: the winners' paths are the plans the next tick keeps clear of
+        launch_clearance_publish(brov_x_device(f->s), f->winner, f->cl.d2min, f->V, f->C, f->N, f->cl.shift, f->cl.r2, f->cl.plan, f->cl.last_d2,
+                                 f->cl.min_d2, f->cl.below, st);
+        HIPCHK(hipGetLastError());
+    }
     f->wr.tick++;
     return enqueued_on(f, st);
 }
@@ -416,4 +482,116 @@ extern "C" int brov_fleet_last_seconds(brov_fleet* f, double* select_seconds) {
     if (!f || !select_seconds || !f->timer.valid) { g_fleet_err = "brov_fleet_last_seconds: no select yet"; return BROV_ERR_ARG; }
     HIPCHK(hipSetDevice(f->device));
     return f->timer.seconds(select_seconds, g_fleet_err);
+}
+
+// ---- the inter-vehicle clearance term (kernels: clearance_kernel.hip) ---------------------------------------------
+static int no_clearance(const char* who) { g_fleet_err = std::string(who) + ": null argument"; return BROV_ERR_ARG; }
+
+extern "C" int brov_clearance_set(brov_fleet* f, double radius, double weight, int shift) {
+    if (!f) return no_clearance("brov_clearance_set");
+    const double r2 = radius * radius;   // what the kernels compare against: a radius whose square overflows or underflows is refused
+    if (!(radius > 0.0) || !std::isfinite(radius) || !(r2 > 0.0) || !std::isfinite(r2) || !(weight > 0.0) || shift < 0 || shift > f->N) {
+        g_fleet_err = "brov_clearance_set: bad argument (needs a finite radius > 0 whose square is finite and > 0, a weight > 0 that may be +Inf, "
+                      "and 0 <= shift <= N = " + std::to_string(f->N) + ")";
+        return BROV_ERR_ARG;
+    }
+    f->cl.radius = radius; f->cl.weight = weight; f->cl.shift = shift;
+    f->cl.r2 = r2;
+    f->cl.on = true;
+    return BROV_OK;
+}
+
+extern "C" int brov_clearance_off(brov_fleet* f) {
+    if (!f) return no_clearance("brov_clearance_off");
+    f->cl.on = false;
+    return BROV_OK;
+}
+
+extern "C" int brov_clearance_enabled(const brov_fleet* f) { return f && f->cl.on ? 1 : 0; }
+
+extern "C" int brov_clearance_dev_set_slices(brov_fleet* f, int slices) {
+    if (!f) return no_clearance("brov_clearance_dev_set_slices");
+    if (slices < 0 || slices > kClearanceMaxSlices) {
+        g_fleet_err = "brov_clearance_dev_set_slices: bad argument (needs 0 <= slices <= " + std::to_string(kClearanceMaxSlices) + ", 0: the default)";
+        return BROV_ERR_ARG;
+    }
+    f->cl.slices = slices ? slices : clearance_slices(f->B, f->V);   // a launch takes the count by value: no wait
+    return BROV_OK;
+}
+extern "C" int brov_clearance_dev_slices(const brov_fleet* f) { return f ? f->cl.slices : 0; }
+
+// HOST [V][N+1][3] <-> the device's stage-major [N+1][V][3]
+extern "C" int brov_clearance_set_plan_host(brov_fleet* f, const double* plan) {
+    if (!f || !plan) return no_clearance("brov_clearance_set_plan_host");
+    HIPCHK(hipSetDevice(f->device));
+    HIPCHK(hipStreamSynchronize(f->last_stream));   // a step in flight may still read or write the plan
+    const size_t V = (size_t)f->V, K = (size_t)f->N + 1;
+    std::vector<double> t(K * V * 3);
+    for (size_t v = 0; v < V; v++)
+        for (size_t k = 0; k < K; k++)
+            for (size_t j = 0; j < 3; j++) t[(k * V + v) * 3 + j] = plan[(v * K + k) * 3 + j];
+    HIPCHK(hipMemcpy(f->cl.plan, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice));
+    return BROV_OK;
+}
+
+extern "C" int brov_clearance_get_plan_host(brov_fleet* f, double* plan) {
+    if (!f || !plan) return no_clearance("brov_clearance_get_plan_host");
+    HIPCHK(hipSetDevice(f->device));
+    HIPCHK(hipStreamSynchronize(f->last_stream));
+    const size_t V = (size_t)f->V, K = (size_t)f->N + 1;
+    std::vector<double> t(K * V * 3);
+    HIPCHK(hipMemcpy(t.data(), f->cl.plan, t.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t v = 0; v < V; v++)
+        for (size_t k = 0; k < K; k++)
+            for (size_t j = 0; j < 3; j++) plan[(v * K + k) * 3 + j] = t[(k * V + v) * 3 + j];
+    return BROV_OK;
+}
+
+static int clearance_is_set(const brov_fleet* f, const char* who) {
+    if (f->cl.on) return BROV_OK;
+    g_fleet_err = std::string(who) + ": the clearance term is off (brov_clearance_set gives the radius, the weight and the shift)";
+    return BROV_ERR_ARG;
+}
+
+extern "C" int brov_clearance_eval_device(brov_fleet* f, const double* x, const brov_result* rec, double* d2min, brov_result* out, void* stream) {
+    if (!f || !d2min) return no_clearance("brov_clearance_eval_device");
+    if (int rc = clearance_is_set(f, "brov_clearance_eval_device")) return rc;
+    HIPCHK(hipSetDevice(f->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = order_both(f, st, "brov_clearance_eval_device")) return rc;
+    if (int rc = clearance_on(f, x ? x : brov_x_device(f->s), rec ? rec : brov_results_device(f->s), d2min, out, st)) return rc;
+    return enqueued_on(f, st);
+}
+
+extern "C" int brov_clearance_eval_host(brov_fleet* f, const brov_result* rec_host, double* d2min, brov_result* out) {
+    if (!f || !d2min) return no_clearance("brov_clearance_eval_host");
+    if (int rc = clearance_is_set(f, "brov_clearance_eval_host")) return rc;
+    HIPCHK(hipSetDevice(f->device));
+    if (int rc = wait_all(f, "brov_clearance_eval_host")) return rc;   // the staging buffer and the fleet's own d2min may still be in use
+    if (rec_host) HIPCHK(hipMemcpy(f->stage_rec, rec_host, (size_t)f->B * sizeof(brov_result), hipMemcpyHostToDevice));
+    if (int rc = clearance_on(f, brov_x_device(f->s), rec_host ? f->stage_rec : brov_results_device(f->s), f->cl.d2min, out ? f->cl.rec : nullptr,
+                              nullptr))
+        return rc;
+    if (int rc = enqueued_on(f, nullptr)) return rc;
+    HIPCHK(hipStreamSynchronize(nullptr));
+    HIPCHK(hipMemcpy(d2min, f->cl.d2min, (size_t)f->B * sizeof(double), hipMemcpyDeviceToHost));
+    if (out) HIPCHK(hipMemcpy(out, f->cl.rec, (size_t)f->B * sizeof(brov_result), hipMemcpyDeviceToHost));
+    return BROV_OK;
+}
+
+extern "C" int brov_clearance_get_stats_host(brov_fleet* f, double* last_d2, double* min_d2, int32_t* below) {
+    if (!f) return no_clearance("brov_clearance_get_stats_host");
+    HIPCHK(hipSetDevice(f->device));
+    HIPCHK(hipStreamSynchronize(f->last_stream));
+    const size_t V = (size_t)f->V;
+    if (last_d2) HIPCHK(hipMemcpy(last_d2, f->cl.last_d2, V * sizeof(double), hipMemcpyDeviceToHost));
+    if (min_d2) HIPCHK(hipMemcpy(min_d2, f->cl.min_d2, V * sizeof(double), hipMemcpyDeviceToHost));
+    if (below) HIPCHK(hipMemcpy(below, f->cl.below, V * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return BROV_OK;
+}
+
+extern "C" int brov_clearance_last_seconds(brov_fleet* f, double* seconds) {
+    if (!f || !seconds || !f->cl.timer.valid) { g_fleet_err = "brov_clearance_last_seconds: no distance kernel yet"; return BROV_ERR_ARG; }
+    HIPCHK(hipSetDevice(f->device));
+    return f->cl.timer.seconds(seconds, g_fleet_err);
 }

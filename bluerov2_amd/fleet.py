@@ -27,6 +27,13 @@ def _protos(L):
         "brov_closed_loop_fleet_dob": [vp, vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, dp, dp, ip, ip, dp, dp],
     })
     _bind(L, {"brov_vehicle_wrench_tick": [vp]}, C.c_int64)
+    _bind(L, {
+        "brov_clearance_set": [vp, C.c_double, C.c_double, C.c_int], "brov_clearance_off": [vp], "brov_clearance_enabled": [vp],
+        "brov_clearance_set_plan_host": [vp, dp], "brov_clearance_get_plan_host": [vp, dp],
+        "brov_clearance_eval_device": [vp, vp, vp, vp, vp, vp], "brov_clearance_eval_host": [vp, vp, dp, vp],
+        "brov_clearance_get_stats_host": [vp, dp, dp, ip], "brov_clearance_last_seconds": [vp, dp],
+        "brov_clearance_dev_set_slices": [vp, C.c_int], "brov_clearance_dev_slices": [vp],
+    })
 
 
 def _fleet_lib():
@@ -155,6 +162,62 @@ class Fleet(_Handle):
         self._chk(self._L.brov_closed_loop_fleet_dob(self._h, None if ekf is None else ekf._h, ticks, float(t0), float(dt_ref), float(dt_node),
                                                      float(dt), int(substeps), _dp(u), _dp(x), _ip(st), _ip(win), _dp(w), _dp(est)), "closed_loop_dob")
         return dict(u=u, x=x, status=st, winner=win, wrench=w, est=est) if log else None
+
+    # ---- the inter-vehicle clearance term (brov_clearance_*) ------------------------------------------------------------------------
+    def set_clearance(self, radius, weight=float("inf"), shift=1):
+        """turns the term on: candidates that come closer than `radius` to another vehicle's plan pay weight * (radius^2 - d2min) on their
+        cost ahead of the select (weight=inf: they are ineligible); the plan of a peer is read `shift` stages ahead.  step() and the closed
+        loops then re-score, select and publish the winners' paths as the new plans"""
+        self._chk(self._L.brov_clearance_set(self._h, float(radius), float(weight), int(shift)), "set_clearance")
+
+    def clearance_off(self):
+        """today's step again; plan, statistics and parameters are kept"""
+        self._chk(self._L.brov_clearance_off(self._h), "clearance_off")
+
+    def clearance_enabled(self):
+        return bool(self._L.brov_clearance_enabled(self._h))
+
+    def set_plan(self, plan):
+        """the positions of the path every vehicle committed to, [V, N + 1, 3]"""
+        self._chk(self._L.brov_clearance_set_plan_host(self._h, _dp(_arr(plan, (self.V, self.solver.N + 1, 3)))), "set_plan")
+
+    def plan(self):
+        plan = np.empty((self.V, self.solver.N + 1, 3))
+        self._chk(self._L.brov_clearance_get_plan_host(self._h, _dp(plan)), "plan")
+        return plan
+
+    def clearance_eval(self, records=None):
+        """(d2min [V * C], re-scored records [V * C]) of the solver's iterate against the plan as it stands, from host records (None: the
+        solver's own); moves nothing"""
+        B = self.V * self.C
+        rp = None
+        if records is not None:
+            records = _arr(records, (B,), RESULT_DTYPE)
+            rp = records.ctypes.data_as(C.c_void_p)
+        d2 = np.empty(B)
+        out = np.empty(B, dtype=RESULT_DTYPE)
+        self._chk(self._L.brov_clearance_eval_host(self._h, rp, _dp(d2), out.ctypes.data_as(C.c_void_p)), "clearance_eval")
+        return d2, out
+
+    def clearance_stats(self):
+        """dict(last_d2 [V]: d2min of the last step's winner or -1, min_d2 [V]: its minimum over the steps with a winner, below [V]: steps
+        whose winner was inside the radius)"""
+        last, low, below = np.empty(self.V), np.empty(self.V), np.empty(self.V, dtype=np.int32)
+        self._chk(self._L.brov_clearance_get_stats_host(self._h, _dp(last), _dp(low), _ip(below)), "clearance_stats")
+        return dict(last_d2=last, min_d2=low, below=below)
+
+    def clearance_slices(self, slices=None):
+        """development and tests: the number of grid-level slices the distance kernel cuts the peer range into (set with 1..8, 0: the
+        default); the results do not depend on it"""
+        if slices is not None:
+            self._chk(self._L.brov_clearance_dev_set_slices(self._h, int(slices)), "clearance_slices")
+        return int(self._L.brov_clearance_dev_slices(self._h))
+
+    def clearance_seconds(self):
+        """seconds of the last distance kernel"""
+        s = C.c_double()
+        self._chk(self._L.brov_clearance_last_seconds(self._h, C.byref(s)), "clearance_seconds")
+        return s.value
 
     def last_seconds(self):
         """seconds of the last select kernel"""

@@ -650,7 +650,7 @@ int  brov_fleet_create(brov_fleet** out, brov_solver* s, int candidates);   /* B
 void brov_fleet_destroy(brov_fleet* f);                                      /* does not destroy the solver */
 int  brov_fleet_vehicles(const brov_fleet* f);
 int  brov_fleet_candidates(const brov_fleet* f);
-int  brov_fleet_reset(brov_fleet* f);                    /* u_hold = 0; v_prev = 0; xv := x0 of candidate 0 of every group; tick counter 0 (done by create) */
+int  brov_fleet_reset(brov_fleet* f);                    /* u_hold = 0; v_prev = 0; xv := x0 of candidate 0 of every group; tick counter 0; plan and clearance statistics as new (done by create) */
 int  brov_fleet_set_state_host(brov_fleet* f, const double* xv /*[V][12]*/);   /* also broadcast into the solver's x0 */
 int  brov_fleet_get_state_host(brov_fleet* f, double* xv /*[V][12]*/);
 int  brov_fleet_set_plant_params_host(brov_fleet* f, const double* p /*[V][16]; NULL: stage-0 parameters of candidate 0 of each group, re-read at every step*/);
@@ -659,7 +659,8 @@ int  brov_fleet_set_plant_params_host(brov_fleet* f, const double* p /*[V][16]; 
 int  brov_fleet_select_device(brov_fleet* f, const brov_result* rec, int32_t* winner, brov_result* winner_rec, void* stream);
 int  brov_fleet_select_host(brov_fleet* f, const brov_result* rec_host /*[B] or NULL*/, int32_t* winner /*[V]*/, brov_result* winner_rec /*[V] or NULL*/);
 /* select + plant + broadcast from the given records (DEVICE [B]; NULL = the solver's).  Callers that re-score candidates
- * (e.g. add a penalty to `cost`) pass their own records. */
+ * (e.g. add a penalty to `cost`) pass their own records; the re-scoring that keeps the vehicles apart is done on the device
+ * (brov_clearance_set below): with it on, the step re-scores the records it is given, selects, and publishes the winners' paths. */
 int  brov_fleet_step(brov_fleet* f, const brov_result* rec, double dt, int substeps, void* stream);
 /* of the last step, HOST, any may be NULL: the input every vehicle was given u [V][4], its status [V] and its winner [V] */
 int  brov_fleet_get_last_host(brov_fleet* f, double* u, int32_t* status, int32_t* winner);
@@ -709,6 +710,44 @@ int brov_vehicle_apply_estimate(brov_fleet* f, brov_ekf* e, void* stream);
 int brov_closed_loop_fleet_dob(brov_fleet* f, brov_ekf* e /*NULL: no observer*/, int ticks, double t0, double dt_ref, double dt_node,
                                double dt, int substeps, double* u_log, double* x_log, int32_t* st_log, int32_t* win_log,
                                double* w_log /*[ticks][V][6]*/, double* est_log /*[ticks][V][6]*/);
+
+/* ---- the inter-vehicle clearance term.  (These calls take a brov_fleet; brov_fleet_last_error() has their texts.) ----
+ * The fleet owns a PLAN per vehicle, plan [V][N+1][3]: the positions x, y, z of the path the vehicle committed to last.  After
+ * brov_fleet_create, brov_fleet_reset and brov_fleet_set_state_host every stage of plan[v] is the position of xv[v] (the vehicle stays where
+ * it is).  With the term on (brov_clearance_set; off by default, and then every call launches exactly what it launched before), brov_fleet_step
+ * and every tick of the fleet's loops run
+ *   clearance  d2min[b], b = v * C + c: the minimum over the peers w != v and the stages k = 0..N of ((dx*dx + dy*dy) + dz*dz) with
+ *              d = x[b][k][0..2] - plan[w][min(k + shift, N)], x the solver's iterate; every operation rounded on its own; the minimum starts
+ *              at +Inf and is updated by d2 < m, so a NaN distance is skipped; V = 1 gives +Inf.  Two calls return the same bytes.
+ *   re-score   into records the fleet owns: a copy of every record, with cost := cost + weight * (r2 - d2min[b]) where d2min[b] < r2 =
+ *              radius * radius (three operations, each rounded; a cost that is NaN already keeps its bytes, a NaN the sum generates, -Inf + Inf,
+ *              is written as the quiet NaN 0x7ff8000000000000).
+ *              weight = +Inf makes the term a hard constraint: the cost becomes +Inf, which the select treats as ineligible
+ *   the select, the plant and the broadcast of brov_fleet_step on the re-scored records (a vehicle whose candidates were all priced out holds
+ *              its input, with the logged status of that rule)
+ *   publish    with a winner c, plan[v][k] := x[v*C+c][k][0..2] for k = 0..N; without one the old plan advances by `shift` stages,
+ *              plan[v][k] := plan[v][min(k + shift, N)].  Statistics per vehicle, reset where the plan is: last_d2 = d2min of this step's
+ *              winner or -1.0 without one (and before the first step), min_d2 = the minimum of last_d2 over the steps that had a winner (+Inf
+ *              before the first), below = the number of steps whose winner had d2min < r2
+ * Steps with the term off leave plan and statistics alone; brov_clearance_off keeps the plan, the statistics and the parameters. */
+int brov_clearance_set(brov_fleet* f, double radius, double weight, int shift);
+        /* radius finite > 0 with radius * radius finite and > 0 (about 1.5e-162 < radius < 1.3e154), weight > 0 (may be +Inf, not NaN),
+         * 0 <= shift <= N; else BROV_ERR_ARG */
+int brov_clearance_off(brov_fleet* f);
+int brov_clearance_enabled(const brov_fleet* f);                      /* 0 for NULL */
+int brov_clearance_set_plan_host(brov_fleet* f, const double* plan /*[V][N+1][3]*/);
+int brov_clearance_get_plan_host(brov_fleet* f, double* plan);
+/* the two kernels alone, against the plan as it stands (moves nothing): x DEVICE [B][N+1][12] or NULL = brov_x_device(solver),
+ * rec DEVICE [B] or NULL = the solver's records; d2min DEVICE [B]; out DEVICE [B] or NULL.  BROV_ERR_ARG while the term is off: radius,
+ * weight and shift come from brov_clearance_set.  Ordered behind the solver's last stream and the fleet's own last work. */
+int brov_clearance_eval_device(brov_fleet* f, const double* x, const brov_result* rec, double* d2min, brov_result* out, void* stream);
+int brov_clearance_eval_host(brov_fleet* f, const brov_result* rec_host /*[B] or NULL*/, double* d2min /*[B]*/, brov_result* out /*[B] or NULL*/);
+int brov_clearance_get_stats_host(brov_fleet* f, double* last_d2, double* min_d2, int32_t* below /*[V] each, any NULL*/);
+int brov_clearance_last_seconds(brov_fleet* f, double* seconds);      /* the distance kernel, HIP events */
+/* development and tests: into how many grid-level slices the distance kernel cuts the peer range (1..8; 0: the default, chosen from B and V).
+ * A tuning knob only: d2min is a minimum, its bytes do not depend on the count -- which is what the tests hold with it. */
+int brov_clearance_dev_set_slices(brov_fleet* f, int slices);
+int brov_clearance_dev_slices(const brov_fleet* f);                   /* the count in force; 0 for NULL */
 
 #ifdef __cplusplus
 }
