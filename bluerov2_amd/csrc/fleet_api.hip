@@ -283,6 +283,11 @@ static int plant_modes_ok(const brov_fleet* f, const char* who) {
                       "brov_vehicle_wrench_*";
         return BROV_ERR_ARG;
     }
+    if (brov_thruster_enabled(f->s) == 1) {
+        g_fleet_err = std::string(who) + ": the thruster stage of the solver's plant is on (brov_thruster_set_host); the fleet's plant gives every "
+                      "vehicle the wrench it asked for";
+        return BROV_ERR_ARG;
+    }
     if (brov_dist6_enabled(f->s) == 1) {
         g_fleet_err = std::string(who) + ": the 6-disturbance variant is on (brov_enable_dist6); the fleet's plant integrates the shipped model";
         return BROV_ERR_ARG;

@@ -18,6 +18,7 @@
 #include "nmpc_device.hpp"
 #include "select_device.hpp"
 #include "wrench_source.hpp"
+#include "thruster_source.hpp"
 
 using namespace brov;
 
@@ -104,6 +105,7 @@ struct brov_solver {
     bool pplant_set = false;     // explicit plant parameters given (brov_plant_set_params_host)
     bool pplant_stale = true;    // controller parameters changed since the plant's copy of them was taken
     WrenchSource wr;             // world-frame wrench of the plant (brov_plant_wrench_*), its buffers allocated on first use; its counter: plant steps so far
+    ThrusterSource th;           // thruster stage of the plant (brov_thruster_*): limits, faults and propulsion matrix, its buffers allocated on first use
     bool cand_set = false;       // candidate shape parameters resident in scratch3
     int cand_kind = 0;
     bool dump_lin = false;
@@ -327,6 +329,7 @@ extern "C" int brov_create(brov_solver** out, int device, int B, const brov_opts
     s->N = opts->N;
     s->opts = *opts;
     s->wr.B = (size_t)B;
+    s->th.B = (size_t)B;
     const size_t N = opts->N, Bz = B;
     int rc = BROV_OK;
 #define AL(ptr, n) if (rc == BROV_OK) rc = s->mem.alloc(&s->ptr, (n), g_err)
@@ -396,6 +399,7 @@ extern "C" void brov_destroy(brov_solver* s) {
     s->mem.free_all();
     if (s->traj) hipFree(s->traj);
     s->wr.destroy();
+    s->th.destroy();
     if (s->dbg) hipFree(s->dbg);
     s->tick.destroy();
     for (int k = 0; k < 3; k++)
@@ -779,9 +783,42 @@ extern "C" int brov_plant_wrench_eval_host(brov_solver* s, int64_t tick, double*
     if (!s) return no_solver("brov_plant_wrench_eval_host");
     return s->wr.eval_host(tick, w, s->last_stream, [s] { return wrench_wait(s); }, s->mem, g_err, "brov_plant_wrench_eval_host");
 }
-// one plant step of the tick counter's tick on `st`, with optional DEVICE logs of this tick; mode OFF: the plant kernel as it always was
+// ---- thruster stage of the plant (plant_wrench.hip): thin forwards to its host side, thruster_source.hpp ----------------------------------
+extern "C" void brov_thruster_default_matrix(double K[36]) { if (K) ThrusterSource::default_matrix(K); }
+extern "C" int brov_thruster_set_host(brov_solver* s, const double* K, const double* lo, const double* hi, const double* gain, const double* bias,
+                                      const int64_t* onset) {
+    if (!s) return no_solver("brov_thruster_set_host");
+    return s->th.set_host(K, lo, hi, gain, bias, onset, [s] { return wrench_wait(s); }, s->mem, g_err, "brov_thruster_set_host");
+}
+extern "C" int brov_thruster_off(brov_solver* s) { return s ? s->th.set_off() : no_solver("brov_thruster_off"); }
+extern "C" int brov_thruster_enabled(const brov_solver* s) { return s && s->th.on ? 1 : 0; }
+extern "C" int brov_thruster_eval_host(brov_solver* s, int64_t tick, const double* commanded, double* applied, double* wrench) {
+    if (!s) return no_solver("brov_thruster_eval_host");
+    return s->th.eval_host(tick, commanded, applied, wrench, s->last_stream, [s] { return wrench_wait(s); }, s->mem, g_err, "brov_thruster_eval_host");
+}
+extern "C" int brov_thruster_last_host(brov_solver* s, double* applied) {
+    if (!s) return no_solver("brov_thruster_last_host");
+    return s->th.last_host(applied, [s] { return wrench_wait(s); }, s->mem, g_err, "brov_thruster_last_host");
+}
+extern "C" int brov_thruster_get_stats_host(brov_solver* s, int32_t* clip_ticks, double* lost_sq, int64_t* steps) {
+    if (!s) return no_solver("brov_thruster_get_stats_host");
+    return s->th.get_stats_host(clip_ticks, lost_sq, steps, [s] { return wrench_wait(s); }, s->mem, g_err);
+}
+extern "C" int brov_thruster_reset_stats(brov_solver* s) {
+    if (!s) return no_solver("brov_thruster_reset_stats");
+    return s->th.reset_stats([s] { return wrench_wait(s); }, s->mem, g_err);
+}
+extern "C" int brov_thruster_last_seconds(brov_solver* s, double* seconds) {
+    if (!s) return no_solver("brov_thruster_last_seconds");
+    HIPCHK(hipSetDevice(s->device));
+    return s->th.last_seconds(seconds, g_err, "brov_thruster_last_seconds");
+}
+// one plant step of the tick counter's tick on `st`, with optional DEVICE logs of this tick: the one place that picks the plant kernel.
+// Thruster stage off and mode OFF: the plant kernel as it always was
 static void plant_step_on(brov_solver* s, double dt, int substeps, double* xlog, double* ulog, double* wlog, hipStream_t st) {
-    if (s->wr.off())
+    if (s->th.on)
+        s->th.step(s->x0, s->res, s->pplant, plant_rp(s), plant_rp_stride(s), dt, substeps, xlog, ulog, s->wr.gen, s->wr.tick, wlog, st);
+    else if (s->wr.off())
         launch_plant(s->x0, s->res, s->pplant, plant_rp(s), plant_rp_stride(s), s->B, dt, substeps, xlog, ulog, st);
     else
         launch_plant_wrench(s->x0, s->res, s->pplant, plant_rp(s), plant_rp_stride(s), s->B, dt, substeps, xlog, ulog, s->wr.gen, s->wr.tick, wlog, st);
@@ -968,12 +1005,12 @@ static void gather_status(const brov_solver* s, int* out, hipStream_t st) {
 // One launch for the whole loop where the fused kernels serve the solver and every window is rows of the table in place (round 5,
 // rti_fused_kernel_ticks with the plant update behind every step): every instance runs its own closed loop at its own pace -- no launch
 // boundaries, three launches per tick saved, and a tick on which one instance grinds through the QP loop holds nobody else.
-// (The fused and windowed *_ticks kernels integrate the plant themselves and know no wrench: with a wrench mode in force the loop takes
-// a launch per step.)
+// (The fused and windowed *_ticks kernels integrate the plant themselves and know neither a wrench nor thrusters: with a wrench mode in
+// force or the thruster stage on the loop takes a launch per step.)
 static bool loop_in_one_launch(const brov_solver* s, int ticks, int line0, int ncols, int* which) {
     *which = ticks_kernel(s);
     return s->k.closed_loop_fused && ncols == 16 && line0 >= 0 && line0 + (ticks - 1) + s->N <= s->traj_rows - 1 && *which != 0 &&
-           s->wr.off();
+           s->wr.off() && !s->th.on;
 }
 // `n` ticks of the plain loop (window -> RTI step -> plant step) from trajectory row `line` on `st`, logged into L
 static int run_loop_ticks(brov_solver* s, int n, int line, int ncols, double dt, int substeps, bool one_launch, int which, const LoopLog& L,

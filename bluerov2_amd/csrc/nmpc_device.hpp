@@ -146,4 +146,24 @@ void launch_plant_wrench(double* x0, const brov_result* res, const double* pplan
 void launch_wrench_eval(const WrenchGen& g, int B, long long tick, double* out /*[B][6]*/, hipStream_t st);
 void launch_gather_cols(const double* src, int B, int src_stride, int col0, int ncols, double* dst /*[B][ncols]*/, hipStream_t st);
 
+// thruster stage of the plant (plant_wrench.hip; include/bluerov2_nmpc.h, brov_thruster_*): between the six commands of the result record and
+// the body wrench the model integrates.  A pure function of (these records, instance, tick): the stage keeps no state.
+struct ThrusterPar {              // shared by the batch and wave-uniform: passed by value in the kernel arguments
+    double K[36];                 // [6][6] rows = generalised force axes [X Y Z K M N], columns = thrusters
+    double lo[6], hi[6];          // limits of the commands, always applied
+};
+struct ThrusterDev {              // per instance
+    const double* gain = nullptr;        // [B][6]
+    const double* bias = nullptr;        // [B][6]
+    const long long* onset = nullptr;    // [B]: gain and bias apply from this tick on
+    int32_t* clip_ticks = nullptr;       // [B][6] statistics of the plant steps ...
+    double* lost_sq = nullptr;           // [B]
+    double* last = nullptr;              // [B][6] ... and the thrusts the last one applied
+};
+void launch_plant_thruster(double* x0, const brov_result* res, const double* pplant, const double* prp, int rp_stride, int B, double dt, int substeps,
+                           double* xlog, double* ulog, const ThrusterPar& T, const ThrusterDev& D, const WrenchGen& g, long long tick,
+                           double* wlog /*[B][6] or nullptr*/, hipStream_t st);   // g.mode OFF: the instantiation without a world wrench
+void launch_thruster_eval(const ThrusterPar& T, const ThrusterDev& D, int B, long long tick, const double* commanded /*[B][6]*/,
+                          double* applied /*[B][6]*/, double* wrench /*[B][6]*/, hipStream_t st);
+
 }  // namespace brov

@@ -12,6 +12,8 @@
 // scratch.  plant_kernel is the device's one plant step (bluerov2_model.hpp: plant_inputs, plant_erk4, store_row / log_row);
 // plant_wrench_kernel restates it (see there) with the wrench projected into the body frame at EVERY stage with that stage's attitude
 // (model_f<WorldWrench>).  ~600 / ~660 FP64 ops, 240 B (+ 48 B) in, 96 B (+ logs) out per instance.
+// thruster_eval_kernel / plant_thruster_kernel<WW>: the same step behind the thruster stage (limits, per-instance gain / bias faults from an
+// onset tick, a 6 x 6 propulsion matrix; brov_thruster_*), with or without the world wrench on top, and the stage alone.
 #include <hip/hip_runtime.h>
 
 #include "nmpc_device.hpp"
@@ -142,6 +144,109 @@ __global__ __launch_bounds__(128) void plant_wrench_kernel(double* __restrict__ 
     }
 }
 
+// ---- the thruster stage (brov_thruster_*): limits, per-instance faults and the propulsion matrix between the six commands of the result
+// record and the body wrench the model integrates.  For instance b at plant tick k, t = the commands:
+//   c[i] = t[i] < lo[i] ? lo[i] : (t[i] > hi[i] ? hi[i] : t[i])                 (a NaN passes through)
+//   a[i] = k >= onset[b] ? gain[b][i] * c[i] + bias[b][i] : c[i]                product rounded, then the sum
+//   g[r] = ((((K[r][0] a[0] + K[r][1] a[1]) + K[r][2] a[2]) + K[r][3] a[3]) + K[r][4] a[4]) + K[r][5] a[5]
+// every operation rounded on its own: the evaluation kernel, the plant kernel and the numpy restatement of tests/thruster_restatement.py
+// agree bit for bit.  No state: any tick can be evaluated again.
+//
+// rn_mul / rn_add: one product / one sum, rounded to nearest, that no caller's context fuses.  __dmul_rn / __dadd_rn do not give that here: the header defines
+// them as inline functions `x * y` / `x + y` compiled OUTSIDE a caller's `fp contract(off)`, so their instructions carry the contract flag
+// into the caller, and a stage written with them compiled to 36 v_fmac_f64 (wrench_at's two products happen to be exact or added to zero
+// in every test).  Written here under the pragma, the instructions carry no such flag wherever they are inlined.
+__device__ __forceinline__ double rn_mul(double p, double q) {
+#pragma clang fp contract(off)
+    return p * q;
+}
+__device__ __forceinline__ double rn_add(double p, double q) {
+#pragma clang fp contract(off)
+    return p + q;
+}
+__device__ __forceinline__ void thruster_stage(const ThrusterPar& T, const ThrusterDev& D, int b, long long k, const double (&t)[6], double (&a)[6],
+                                               double (&g)[6]) {
+#pragma clang fp contract(off)
+    const bool faulty = k >= D.onset[b];
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        const double c = t[i] < T.lo[i] ? T.lo[i] : (t[i] > T.hi[i] ? T.hi[i] : t[i]);
+        const double f = rn_add(rn_mul(D.gain[(size_t)b * 6 + i], c), D.bias[(size_t)b * 6 + i]);
+        a[i] = faulty ? f : c;
+    }
+#pragma unroll
+    for (int r = 0; r < 6; r++) {
+        double acc = rn_add(rn_mul(T.K[r * 6], a[0]), rn_mul(T.K[r * 6 + 1], a[1]));
+#pragma unroll
+        for (int i = 2; i < 6; i++) acc = rn_add(acc, rn_mul(T.K[r * 6 + i], a[i]));
+        g[r] = acc;
+    }
+}
+
+// what a plant step leaves behind per instance (one lane per instance, no atomics): ticks on which a command lay outside its limits, the
+// running sum of |commanded - applied|^2 -- six squares summed in index order, then ONE add into the sum --, the thrusts applied
+__device__ __forceinline__ void thruster_account(const ThrusterPar& T, const ThrusterDev& D, int b, const double (&t)[6], const double (&a)[6]) {
+#pragma clang fp contract(off)
+    double sq = 0.0;
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        D.clip_ticks[(size_t)b * 6 + i] += (t[i] < T.lo[i] || t[i] > T.hi[i]) ? 1 : 0;
+        const double d = rn_add(t[i], -a[i]);
+        sq = i == 0 ? rn_mul(d, d) : rn_add(sq, rn_mul(d, d));
+        D.last[(size_t)b * 6 + i] = a[i];
+    }
+    D.lost_sq[b] = rn_add(D.lost_sq[b], sq);
+}
+
+__global__ __launch_bounds__(128) void thruster_eval_kernel(ThrusterPar T, ThrusterDev D, int B, long long tick, const double* __restrict__ commanded,
+                                                            double* __restrict__ applied, double* __restrict__ wrench) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double t[6], a[6], g[6];
+#pragma unroll
+    for (int i = 0; i < 6; i++) t[i] = commanded[(size_t)b * 6 + i];
+    thruster_stage(T, D, b, tick, t, a, g);
+    store_row(applied + (size_t)b * 6, a);
+    store_row(wrench + (size_t)b * 6, g);
+}
+
+// The plant step behind the thruster stage: gather -> stage -> plant_erk4 -> store / logs / statistics.  The wrench of the step is the
+// stage's g = [X Y Z K M N] in place of make_wrench(u0); the roll / pitch moments of the 6-disturbance variant are ADDED to its k3, k4.
+// WW = WorldWrench: the generator g at `tick` on top, evaluated and logged as plant_wrench_kernel does.  The `u` log stays the commanded input.
+template <class WW>
+__global__ __launch_bounds__(128) void plant_thruster_kernel(double* __restrict__ x0, const brov_result* __restrict__ res,
+                                                             const double* __restrict__ pplant, const double* __restrict__ prp, int rp_stride, int B,
+                                                             double dt, int substeps, double* __restrict__ xlog, double* __restrict__ ulog,
+                                                             ThrusterPar T, ThrusterDev D, WrenchGen gen, long long tick, double* __restrict__ wlog) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double x[NX], u[NU], t[6], a[6], g[6];
+#pragma unroll
+    for (int j = 0; j < NX; j++) x[j] = x0[(size_t)b * NX + j];
+#pragma unroll
+    for (int j = 0; j < NU; j++) u[j] = res[b].u0[j];
+#pragma unroll
+    for (int i = 0; i < 6; i++) t[i] = res[b].thrust[i];
+    const ModelPar m = make_par(pplant + (size_t)b * NP);
+    thruster_stage(T, D, b, tick, t, a, g);
+    thruster_account(T, D, b, t, a);
+    Wrench w;
+    w.k0 = g[0]; w.k1 = g[1]; w.k2 = g[2]; w.k3 = g[3]; w.k4 = g[4]; w.k5 = g[5];
+    if (prp) { w.k3 += prp[(size_t)b * rp_stride]; w.k4 += prp[(size_t)b * rp_stride + 1]; }   // 6-disturbance variant
+    if constexpr (std::is_same_v<WW, WorldWrench>) {
+        double wv[6];
+        wrench_at(gen, b, tick, wv);
+        const WorldWrench ww = {wv[0], wv[1], wv[2], wv[3], wv[4], wv[5]};   // held over the tick
+        log_row(wlog, b, wv);
+        plant_erk4(x, w, m, ww, dt, substeps);
+    } else {
+        plant_erk4(x, w, m, NoWorldWrench{}, dt, substeps);
+    }
+    store_row(x0 + (size_t)b * NX, x);
+    log_row(xlog, b, x);
+    log_row(ulog, b, u);
+}
+
 // dst[b][c] = src[b * src_stride + col0 + c]: the disturbance estimate out of the observer's state for brov_closed_loop_dob's log
 __global__ void gather_cols_kernel(const double* __restrict__ src, int B, int src_stride, int col0, int ncols, double* __restrict__ dst) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -161,6 +266,20 @@ void launch_plant_wrench(double* x0, const brov_result* res, const double* pplan
 }
 void launch_wrench_eval(const WrenchGen& g, int B, long long tick, double* out, hipStream_t st) {
     hipLaunchKernelGGL(wrench_eval_kernel, dim3((B + 127) / 128), dim3(128), 0, st, g, B, tick, out);
+}
+void launch_plant_thruster(double* x0, const brov_result* res, const double* pplant, const double* prp, int rp_stride, int B, double dt, int substeps,
+                           double* xlog, double* ulog, const ThrusterPar& T, const ThrusterDev& D, const WrenchGen& g, long long tick, double* wlog,
+                           hipStream_t st) {
+    if (g.mode == BROV_WRENCH_OFF)
+        hipLaunchKernelGGL(plant_thruster_kernel<NoWorldWrench>, dim3((B + 127) / 128), dim3(128), 0, st, x0, res, pplant, prp, rp_stride, B, dt,
+                           substeps, xlog, ulog, T, D, g, tick, wlog);
+    else
+        hipLaunchKernelGGL(plant_thruster_kernel<WorldWrench>, dim3((B + 127) / 128), dim3(128), 0, st, x0, res, pplant, prp, rp_stride, B, dt,
+                           substeps, xlog, ulog, T, D, g, tick, wlog);
+}
+void launch_thruster_eval(const ThrusterPar& T, const ThrusterDev& D, int B, long long tick, const double* commanded, double* applied, double* wrench,
+                          hipStream_t st) {
+    hipLaunchKernelGGL(thruster_eval_kernel, dim3((B + 127) / 128), dim3(128), 0, st, T, D, B, tick, commanded, applied, wrench);
 }
 void launch_gather_cols(const double* src, int B, int src_stride, int col0, int ncols, double* dst, hipStream_t st) {
     const int tot = B * ncols;

@@ -132,7 +132,12 @@ def _protos(L):
         "brov_plant_wrench_seek": [vp, C.c_int64], "brov_plant_wrench_eval_host": [vp, C.c_int64, dp],
         "brov_closed_loop_ex": [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, dp, dp, C.POINTER(C.c_int32), dp],
         "brov_closed_loop_dob": [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, dp, dp, C.POINTER(C.c_int32), dp, dp],
+        "brov_thruster_set_host": [vp, dp, dp, dp, dp, dp, C.POINTER(C.c_int64)], "brov_thruster_off": [vp], "brov_thruster_enabled": [vp],
+        "brov_thruster_eval_host": [vp, C.c_int64, dp, dp, dp], "brov_thruster_last_host": [vp, dp],
+        "brov_thruster_get_stats_host": [vp, C.POINTER(C.c_int32), dp, C.POINTER(C.c_int64)], "brov_thruster_reset_stats": [vp],
+        "brov_thruster_last_seconds": [vp, dp],
     })
+    _bind(L, {"brov_thruster_default_matrix": [dp]}, None)
 
 
 def _dp(a):
@@ -531,6 +536,66 @@ class BatchSolver(_Handle):
     def plant_wrench_tick(self):
         """the tick counter: plant steps so far (plant_step and every closed-loop tick add one)"""
         return self._wrench.get("tick")
+
+    # ---- thruster stage of the plant: limits, per-instance faults, propulsion matrix (brov_thruster_*) ---------------------------
+    def set_thrusters(self, K=None, lo=None, hi=None, gain=None, bias=None, onset=None):
+        """the plant steps from now on run behind the thruster stage, and its statistics start afresh.  With t the six commands of the result
+        record (thrusts()): c = clamp(t, lo, hi);  a = gain * c + bias from tick onset[b] on, else c;  wrench [X Y Z K M N] = K a.
+            K            [6, 6] rows = force axes, columns = thrusters (None: the model's own, thruster_matrix())
+            lo, hi       scalar or [6], shared by the batch (None: no limit); the reference's thruster manager has -1540, 1540
+            gain, bias   scalar, [6] or [B, 6] (None: 1, 0); a weak thruster is gain 0.5, a dead one 0, a stuck one gain 0 and bias c
+            onset        scalar or [B], plant ticks (plant_wrench_tick()) from which gain and bias apply (None: 0)"""
+        def rows(v, shape):
+            return None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), shape))
+        Ka = None if K is None else _arr(K, (6, 6))
+        on = None if onset is None else np.ascontiguousarray(np.broadcast_to(np.asarray(onset, dtype=np.int64), (self.B,)))
+        lo_, hi_, g_, b_ = rows(lo, (6,)), rows(hi, (6,)), rows(gain, (self.B, 6)), rows(bias, (self.B, 6))
+        self._chk(self._L.brov_thruster_set_host(self._h, _dp(Ka), _dp(lo_), _dp(hi_), _dp(g_), _dp(b_),
+                                                 None if on is None else on.ctypes.data_as(C.POINTER(C.c_int64))), "set_thrusters")
+
+    def thrusters_off(self):
+        """the plant kernels as they always were; the statistics stay readable"""
+        self._chk(self._L.brov_thruster_off(self._h), "thrusters_off")
+
+    def thrusters_enabled(self):
+        return bool(self._L.brov_thruster_enabled(self._h))
+
+    def thruster_eval(self, tick, commanded):
+        """(applied [B, 6], wrench [B, 6]) of the stage alone for `commanded` [B, 6] at `tick`; moves no counter, touches no statistic"""
+        c = _arr(commanded, (self.B, 6))
+        a, g = np.empty((self.B, 6)), np.empty((self.B, 6))
+        self._chk(self._L.brov_thruster_eval_host(self._h, int(tick), _dp(c), _dp(a), _dp(g)), "thruster_eval")
+        return a, g
+
+    def thruster_last(self):
+        """[B, 6]: the thrusts the last plant step behind the stage applied"""
+        a = np.empty((self.B, 6))
+        self._chk(self._L.brov_thruster_last_host(self._h, _dp(a)), "thruster_last")
+        return a
+
+    def thruster_stats(self):
+        """dict(clip_ticks [B, 6] int32: plant steps on which the command lay outside its limits; lost_sq [B]: running sum of
+        |commanded - applied|^2; steps: plant steps behind the stage since the statistics were reset)"""
+        clip, lost, steps = np.zeros((self.B, 6), dtype=np.int32), np.empty(self.B), C.c_int64(0)
+        self._chk(self._L.brov_thruster_get_stats_host(self._h, clip.ctypes.data_as(C.POINTER(C.c_int32)), _dp(lost), C.byref(steps)),
+                  "thruster_stats")
+        return dict(clip_ticks=clip, lost_sq=lost, steps=int(steps.value))
+
+    def thruster_reset_stats(self):
+        self._chk(self._L.brov_thruster_reset_stats(self._h), "thruster_reset_stats")
+
+    def thruster_last_seconds(self):
+        """duration of the last plant kernel launched behind the stage (HIP events)"""
+        sec = C.c_double(0.0)
+        self._chk(self._L.brov_thruster_last_seconds(self._h, C.byref(sec)), "thruster_last_seconds")
+        return sec.value
+
+    @staticmethod
+    def thruster_matrix():
+        """[6, 6]: the model's own propulsion matrix, the default K"""
+        K = np.empty((6, 6))
+        _load().brov_thruster_default_matrix(_dp(K))
+        return K
 
     # ---- iterate ----------------------------------------------------------------------------------------------
     def set_iterate(self, x=None, u=None, pi=None, lam=None):

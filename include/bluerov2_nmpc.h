@@ -215,6 +215,39 @@ int brov_plant_wrench_eval_host(brov_solver* s, int64_t tick, double* w /*[B][6]
 int brov_closed_loop_ex(brov_solver* s, int ticks, int line0, int ncols, double dt, int substeps, double* u_log, double* x_log,
                         int32_t* st_log, double* w_log);
 
+/* ---- thruster stage of the plant: limits, per-instance faults and the propulsion matrix between the six thruster commands and the forces.
+ * Without it every plant step gives the model exactly the wrench the controller asked for.  The vehicle does not: the reference's thruster
+ * manager saturates at max_thrust 1540 (bluerov2_dobmpc/config/thruster_manager.yaml:7) while the OCP only boxes the four axes, and a weak,
+ * stuck or dead thruster is the disturbance a disturbance observer exists for -- the observer is fed the COMMANDED thrusts, as in the
+ * reference, so what the thrusters fail to deliver shows up as an estimated disturbance.  For instance b at plant tick k (the counter
+ * brov_plant_wrench_tick reads), t = the six commands of the result record (brov_get_thrusts_host):
+ *     c[i] = t[i] < lo[i] ? lo[i] : (t[i] > hi[i] ? hi[i] : t[i])                  a NaN passes through
+ *     a[i] = k >= onset[b] ? gain[b][i] * c[i] + bias[b][i] : c[i]                 product rounded, then the sum rounded: no FMA
+ *     g[r] = ((((K[r][0]*a[0] + K[r][1]*a[1]) + K[r][2]*a[2]) + K[r][3]*a[3]) + K[r][4]*a[4]) + K[r][5]*a[5]      every operation rounded
+ * g = the body wrench [X Y Z K M N] the model integrates in place of the allocation of u0; the roll / pitch moments of the 6-disturbance
+ * variant are added to g[3], g[4].  K is [6][6] row-major, rows = generalised force axes, columns = thrusters (the layout of the reference's
+ * config/TAM.yaml); the default is the model's own (bluerov2.py:95-100, rows 3 and 4 zero).  Limits are shared by the batch and always apply;
+ * gain, bias and onset are per instance and apply from the onset tick on: a weak thruster is gain 0.5, a dead one gain 0, a stuck one gain 0
+ * and bias c.  The stage keeps no state (no thruster lag): a pure function of (data, instance, tick), bit-reproducible.
+ * With the stage on, brov_plant_step and every loop built on it (brov_closed_loop / _ex / _dob / _track) launch plant_thruster_kernel, with the
+ * wrench mode in force on top; the one-launch closed loop knows no thrusters, so the loops take their launch-per-tick branch; the u log stays
+ * the commanded input; a brov_fleet refuses such a solver.  Each such plant step also keeps, per instance: clip_ticks[b][i] += (t[i] outside
+ * [lo[i], hi[i]]), lost_sq[b] += sum_i (t[i] - a[i])^2 (six squares summed in index order, one add into the sum), and the applied thrusts a.
+ * Refused with BROV_ERR_ARG and a text in brov_last_error() that starts with the call's name (nothing changes, nothing is waited for): a NULL
+ * handle, lo[i] > hi[i], a NaN limit, a non-finite K, gain or bias, a negative onset or tick. */
+void brov_thruster_default_matrix(double K[36]);
+int brov_thruster_set_host(brov_solver* s, const double* K /*[6][6]; NULL: the model's*/, const double* lo /*[6]; NULL: -inf*/,
+                           const double* hi /*[6]; NULL: +inf*/, const double* gain /*[B][6]; NULL: 1*/,
+                           const double* bias /*[B][6]; NULL: 0*/, const int64_t* onset /*[B]; NULL: 0*/);   /* switches the stage on, resets the statistics */
+int brov_thruster_off(brov_solver* s);                                /* the plant kernels as they always were; the statistics stay readable */
+int brov_thruster_enabled(const brov_solver* s);                      /* 0 for NULL */
+/* the stage alone at `tick`: moves neither the plant nor a counter nor a statistic (before any brov_thruster_set_host: the defaults) */
+int brov_thruster_eval_host(brov_solver* s, int64_t tick, const double* commanded /*[B][6]*/, double* applied /*[B][6]*/, double* wrench /*[B][6]*/);
+int brov_thruster_last_host(brov_solver* s, double* applied /*[B][6]*/);          /* of the last plant step behind the stage */
+int brov_thruster_get_stats_host(brov_solver* s, int32_t* clip_ticks /*[B][6]*/, double* lost_sq /*[B]*/, int64_t* steps /*any NULL*/);
+int brov_thruster_reset_stats(brov_solver* s);
+int brov_thruster_last_seconds(brov_solver* s, double* seconds);                  /* the plant kernel's last launch behind the stage, HIP events */
+
 /* iterate (warm start) access; any pointer may be NULL to skip that block */
 int brov_set_iterate_host(brov_solver* s, const double* x, const double* u, const double* pi, const double* lam);
 int brov_get_iterate_host(brov_solver* s, double* x, double* u, double* pi, double* lam);
