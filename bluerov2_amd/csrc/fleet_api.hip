@@ -276,7 +276,8 @@ extern "C" int brov_vehicle_wrench_eval_host(brov_fleet* f, int64_t tick, double
 }
 
 // what the plant of the fleet does not model: the vehicles' wrench is the fleet's (brov_vehicle_wrench_*), indexed
-// by the vehicle; the solver's is indexed by the instance v * C + c
+// by the vehicle; the solver's is indexed by the instance v * C + c.  Nor does its broadcast of the vehicles' states know the solver's
+// sensor stage (brov_sensor_*): the candidates would be solved at a measured state nothing refreshes
 static int plant_modes_ok(const brov_fleet* f, const char* who) {
     if (brov_plant_wrench_mode(f->s) != BROV_WRENCH_OFF) {
         g_fleet_err = std::string(who) + ": a plant wrench mode of the solver is in force (brov_plant_wrench_*); the vehicles' wrench is set with "
@@ -286,6 +287,11 @@ static int plant_modes_ok(const brov_fleet* f, const char* who) {
     if (brov_thruster_enabled(f->s) == 1) {
         g_fleet_err = std::string(who) + ": the thruster stage of the solver's plant is on (brov_thruster_set_host); the fleet's plant gives every "
                       "vehicle the wrench it asked for";
+        return BROV_ERR_ARG;
+    }
+    if (brov_sensor_enabled(f->s) == 1) {
+        g_fleet_err = std::string(who) + ": the sensor stage of the solver is on (brov_sensor_set_host); the fleet hands every candidate its "
+                      "vehicle's true state";
         return BROV_ERR_ARG;
     }
     if (brov_dist6_enabled(f->s) == 1) {

@@ -104,6 +104,9 @@ struct SolverView {
     hipStream_t last_stream = nullptr;    // where the solver enqueued last: the stream its closed loops run on
 };
 SolverView solver_view(const brov_solver* s);
+// [B][12] what the controller knows of the state: the measured state while the solver's sensor stage is on (brov_sensor_*), else the plant's
+// own state, brov_x0_device(); read by the observer's and the estimator's *_from_solver / *_from_ekf updates
+const double* solver_measured_state(const brov_solver* s);
 
 // ---- a device buffer that lives as long as a scope: freed on every way out, unless release() hands it on ---------------------------------
 template <typename T>

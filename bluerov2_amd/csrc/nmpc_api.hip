@@ -19,6 +19,7 @@
 #include "select_device.hpp"
 #include "wrench_source.hpp"
 #include "thruster_source.hpp"
+#include "sensor_source.hpp"
 
 using namespace brov;
 
@@ -106,6 +107,7 @@ struct brov_solver {
     bool pplant_stale = true;    // controller parameters changed since the plant's copy of them was taken
     WrenchSource wr;             // world-frame wrench of the plant (brov_plant_wrench_*), its buffers allocated on first use; its counter: plant steps so far
     ThrusterSource th;           // thruster stage of the plant (brov_thruster_*): limits, faults and propulsion matrix, its buffers allocated on first use
+    SensorSource sn;             // sensor stage (brov_sensor_*): the measured state the solve, the observer and the estimator read while it is on, its buffers allocated on first use
     bool cand_set = false;       // candidate shape parameters resident in scratch3
     int cand_kind = 0;
     bool dump_lin = false;
@@ -330,6 +332,7 @@ extern "C" int brov_create(brov_solver** out, int device, int B, const brov_opts
     s->opts = *opts;
     s->wr.B = (size_t)B;
     s->th.B = (size_t)B;
+    s->sn.B = (size_t)B;
     const size_t N = opts->N, Bz = B;
     int rc = BROV_OK;
 #define AL(ptr, n) if (rc == BROV_OK) rc = s->mem.alloc(&s->ptr, (n), g_err)
@@ -400,6 +403,7 @@ extern "C" void brov_destroy(brov_solver* s) {
     if (s->traj) hipFree(s->traj);
     s->wr.destroy();
     s->th.destroy();
+    s->sn.destroy();
     if (s->dbg) hipFree(s->dbg);
     s->tick.destroy();
     for (int k = 0; k < 3; k++)
@@ -457,8 +461,19 @@ static int copy_in(brov_solver* s, double* dst, const double* src, size_t n, boo
     return BROV_OK;
 }
 
-extern "C" int brov_set_x0_host(brov_solver* s, const double* x0) { return copy_in(s, s ? s->x0 : nullptr, x0, s ? (size_t)s->B * 12 : 0, true, nullptr); }
-extern "C" int brov_set_x0_device(brov_solver* s, const double* x0, void* st) { return copy_in(s, s ? s->x0 : nullptr, x0, s ? (size_t)s->B * 12 : 0, false, st); }
+// the plant's true state; with the sensor stage on the measured state follows it: a forced refresh at the current index behind the copy
+static int set_x0(brov_solver* s, const double* x0, bool host, void* st, const char* who) {
+    const bool measured = s && x0 && s->sn.on;
+    if (measured) { if (int rc = SensorSource::index_ok(s->wr.tick, g_err, who)) return rc; }
+    if (int rc = copy_in(s, s ? s->x0 : nullptr, x0, s ? (size_t)s->B * 12 : 0, host, st)) return rc;
+    if (measured) {
+        s->sn.measure(s->x0, s->wr.tick, true, host ? s->last_stream : (hipStream_t)st);
+        HIPCHK(hipGetLastError());
+    }
+    return BROV_OK;
+}
+extern "C" int brov_set_x0_host(brov_solver* s, const double* x0) { return set_x0(s, x0, true, nullptr, "brov_set_x0_host"); }
+extern "C" int brov_set_x0_device(brov_solver* s, const double* x0, void* st) { return set_x0(s, x0, false, st, "brov_set_x0_device"); }
 
 static const double* shared_window(const brov_solver* s) { return s->yref_view ? s->yref_view : s->yref_sh; }
 
@@ -813,8 +828,56 @@ extern "C" int brov_thruster_last_seconds(brov_solver* s, double* seconds) {
     HIPCHK(hipSetDevice(s->device));
     return s->th.last_seconds(seconds, g_err, "brov_thruster_last_seconds");
 }
+// ---- sensor stage between plant and controller (sensor_kernel.hip): thin forwards to its host side, sensor_source.hpp -------------------------
+// the device, and the host wait for everything on it: a refresh may have been enqueued on any stream a plant step was given
+static int sensor_wait(brov_solver* s) {
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipDeviceSynchronize());
+    s->tick.copies_pending = false;
+    return BROV_OK;
+}
+extern "C" int brov_sensor_set_host(brov_solver* s, uint64_t seed, const double* sigma, const double* bias, const double* quant, const int32_t* period,
+                                    const double* dropout) {
+    if (!s) return no_solver("brov_sensor_set_host");
+    return s->sn.set_host(seed, sigma, bias, quant, period, dropout, s->x0, s->wr.tick, s->last_stream, [s] { return sensor_wait(s); }, s->mem, g_err,
+                          "brov_sensor_set_host");
+}
+extern "C" int brov_sensor_off(brov_solver* s) { return s ? s->sn.set_off() : no_solver("brov_sensor_off"); }
+extern "C" int brov_sensor_enabled(const brov_solver* s) { return s && s->sn.on ? 1 : 0; }
+extern "C" int brov_sensor_measure(brov_solver* s, void* stream) {
+    if (!s) return no_solver("brov_sensor_measure");
+    if (!s->sn.on) { g_err = "brov_sensor_measure: the sensor stage is off (brov_sensor_set_host)"; return BROV_ERR_ARG; }
+    if (int rc = SensorSource::index_ok(s->wr.tick, g_err, "brov_sensor_measure")) return rc;
+    HIPCHK(hipSetDevice(s->device));
+    if (int rc = order_behind_last(s, (hipStream_t)stream)) return rc;
+    s->sn.measure(s->x0, s->wr.tick, true, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return BROV_OK;
+}
+extern "C" int brov_sensor_eval_host(brov_solver* s, int64_t index, const double* x, double* y, int32_t* dropped) {
+    if (!s) return no_solver("brov_sensor_eval_host");
+    return s->sn.eval_host(index, x, y, dropped, s->last_stream, [s] { return sensor_wait(s); }, s->mem, g_err, "brov_sensor_eval_host");
+}
+extern "C" int brov_sensor_get_measurement_host(brov_solver* s, double* y) {
+    if (!s) return no_solver("brov_sensor_get_measurement_host");
+    return s->sn.get_measurement_host(y, [s] { return sensor_wait(s); }, s->mem, g_err, "brov_sensor_get_measurement_host");
+}
+extern "C" int brov_sensor_get_stats_host(brov_solver* s, int32_t* dropped, double* err_sq, int64_t* refreshes) {
+    if (!s) return no_solver("brov_sensor_get_stats_host");
+    return s->sn.get_stats_host(dropped, err_sq, refreshes, [s] { return sensor_wait(s); }, s->mem, g_err);
+}
+extern "C" int brov_sensor_reset_stats(brov_solver* s) {
+    if (!s) return no_solver("brov_sensor_reset_stats");
+    return s->sn.reset_stats([s] { return sensor_wait(s); }, s->mem, g_err);
+}
+extern "C" int brov_sensor_last_seconds(brov_solver* s, double* seconds) {
+    if (!s) return no_solver("brov_sensor_last_seconds");
+    HIPCHK(hipSetDevice(s->device));
+    return s->sn.last_seconds(seconds, g_err, "brov_sensor_last_seconds");
+}
 // one plant step of the tick counter's tick on `st`, with optional DEVICE logs of this tick: the one place that picks the plant kernel.
-// Thruster stage off and mode OFF: the plant kernel as it always was
+// Thruster stage off and mode OFF: the plant kernel as it always was.  Sensor stage on: a regular refresh of the measured state behind the plant
+// kernel, at the counter's new value (the caller has checked the index, SensorSource::steps_ok)
 static void plant_step_on(brov_solver* s, double dt, int substeps, double* xlog, double* ulog, double* wlog, hipStream_t st) {
     if (s->th.on)
         s->th.step(s->x0, s->res, s->pplant, plant_rp(s), plant_rp_stride(s), dt, substeps, xlog, ulog, s->wr.gen, s->wr.tick, wlog, st);
@@ -823,10 +886,12 @@ static void plant_step_on(brov_solver* s, double dt, int substeps, double* xlog,
     else
         launch_plant_wrench(s->x0, s->res, s->pplant, plant_rp(s), plant_rp_stride(s), s->B, dt, substeps, xlog, ulog, s->wr.gen, s->wr.tick, wlog, st);
     s->wr.tick++;
+    if (s->sn.on) s->sn.measure(s->x0, s->wr.tick, false, st);
 }
 extern "C" int brov_plant_step(brov_solver* s, double dt, int substeps, void* stream) {
     if (!s || !(dt > 0.0) || substeps < 1) return BROV_ERR_ARG;
     if (int rc = s->wr.steps_ok(1, g_err, "brov_plant_step")) return rc;
+    if (int rc = s->sn.steps_ok(s->wr.tick, 1, g_err, "brov_plant_step")) return rc;
     HIPCHK(hipSetDevice(s->device));
     if (int rc = order_behind_last(s, (hipStream_t)stream)) return rc;
     ensure_plant_params(s, (hipStream_t)stream);
@@ -910,7 +975,7 @@ static DevParams make_params(const brov_solver* s, const SolvePlan& plan, const 
     for (int j = 0; j < 16; j++) P.W[j] = s->opts.W[j];
     for (int j = 0; j < 12; j++) P.We[j] = s->opts.We[j];
     for (int j = 0; j < 4; j++) { P.lbu[j] = s->opts.lbu[j]; P.ubu[j] = s->opts.ubu[j]; }
-    P.x0 = in->x0 ? in->x0 : s->x0;
+    P.x0 = in->x0 ? in->x0 : (s->sn.on ? s->sn.ymeas : s->x0);   // sensor stage on: the measured state; a tick's own x0 is the caller's measurement
     P.yref = in->yref ? in->yref : (s->yref_shared ? shared_window(s) : s->yref);
     P.yref_stride = s->yref_shared ? 0 : (int64_t)(s->N + 1) * 16;
     P.par = in->par ? in->par : s->par;
@@ -995,7 +1060,8 @@ static int loop_args_ok(const brov_solver* s, const brov_ekf* e, const brov_rls*
     }
     if ((e && brov_ekf_batch(e) != s->B) || (r && brov_rls_batch(r) != s->B)) { g_err = std::string(who) + ": batch sizes differ"; return BROV_ERR_ARG; }
     if (r && rls_mode != BROV_RLS_APPLY_DISTURBANCE && rls_mode != BROV_RLS_APPLY_MODEL) { g_err = std::string(who) + ": unknown rls_mode"; return BROV_ERR_ARG; }
-    return s->wr.steps_ok(ticks, g_err, who);
+    if (int rc = s->wr.steps_ok(ticks, g_err, who)) return rc;
+    return s->sn.steps_ok(s->wr.tick, ticks, g_err, who);
 }
 // the statuses of the step just enqueued on `st` into a DEVICE log row (null: not logged)
 static void gather_status(const brov_solver* s, int* out, hipStream_t st) {
@@ -1005,12 +1071,12 @@ static void gather_status(const brov_solver* s, int* out, hipStream_t st) {
 // One launch for the whole loop where the fused kernels serve the solver and every window is rows of the table in place (round 5,
 // rti_fused_kernel_ticks with the plant update behind every step): every instance runs its own closed loop at its own pace -- no launch
 // boundaries, three launches per tick saved, and a tick on which one instance grinds through the QP loop holds nobody else.
-// (The fused and windowed *_ticks kernels integrate the plant themselves and know neither a wrench nor thrusters: with a wrench mode in
-// force or the thruster stage on the loop takes a launch per step.)
+// (The fused and windowed *_ticks kernels integrate the plant themselves and know neither a wrench nor thrusters nor sensors: with a wrench
+// mode in force, the thruster stage or the sensor stage on the loop takes a launch per step.)
 static bool loop_in_one_launch(const brov_solver* s, int ticks, int line0, int ncols, int* which) {
     *which = ticks_kernel(s);
     return s->k.closed_loop_fused && ncols == 16 && line0 >= 0 && line0 + (ticks - 1) + s->N <= s->traj_rows - 1 && *which != 0 &&
-           s->wr.off() && !s->th.on;
+           s->wr.off() && !s->th.on && !s->sn.on;
 }
 // `n` ticks of the plain loop (window -> RTI step -> plant step) from trajectory row `line` on `st`, logged into L
 static int run_loop_ticks(brov_solver* s, int n, int line, int ncols, double dt, int substeps, bool one_launch, int which, const LoopLog& L,
@@ -1445,7 +1511,8 @@ extern "C" int brov_tick_host(brov_solver* s, const double* x0, const double* yr
     if (int rc = stage_inputs(s, L, t.set, x0, yref_shared, par_stage)) return rc;
     if (int rc = enqueue_ahead(s, L, t, passed, rti_phase)) return rc;
     if (t.mailbox) ch.mail_seq = ch.mail_seq == 0x7fffffff ? 1 : ch.mail_seq + 1;
-    const LaunchInputs in = tick_launch_inputs(ch, L, t, passed);   // a local: no path out of this call leaves a later solve reading the pinned buffer
+    LaunchInputs in = tick_launch_inputs(ch, L, t, passed);   // a local: no path out of this call leaves a later solve reading the pinned buffer
+    if (s->sn.on && (passed & 1) && !in.x0) in.x0 = s->x0;   // sensor stage on: an x0 copied in ahead of the launch is the caller's measurement, as one read in place is
     if (brk) tb1 = clk::now();
     if (t.copies_beside) HIPCHK(hipEventRecord(ch.ev_pre, st));   // (ahead of the launch like enqueue_ahead, but on the launch's side of the breakdown)
     const int rc = solve_phase(s, st, rti_phase, &in);
@@ -1569,6 +1636,10 @@ extern "C" int brov_get_u0_host(brov_solver* s, double* u0) {
 }
 extern "C" const brov_result* brov_results_device(const brov_solver* s) { return s ? s->res : nullptr; }
 extern "C" double* brov_x0_device(brov_solver* s) { return s ? s->x0 : nullptr; }
+namespace brov {
+// what the controller knows of the state: the measured state while the sensor stage is on, else the plant's own (for the observer and the estimator)
+const double* solver_measured_state(const brov_solver* s) { return s ? (s->sn.on ? s->sn.ymeas : s->x0) : nullptr; }
+}  // namespace brov
 extern "C" double* brov_yref_device(brov_solver* s) { if (!s) return nullptr; s->yref_shared = false; forget_traj_window(s); return s->yref; }
 extern "C" double* brov_params_device(brov_solver* s) { if (!s) return nullptr; s->pplant_stale = true; return s->par; }
 extern "C" double* brov_x_device(brov_solver* s) { return s ? s->x : nullptr; }

@@ -166,4 +166,25 @@ void launch_plant_thruster(double* x0, const brov_result* res, const double* ppl
 void launch_thruster_eval(const ThrusterPar& T, const ThrusterDev& D, int B, long long tick, const double* commanded /*[B][6]*/,
                           double* applied /*[B][6]*/, double* wrench /*[B][6]*/, hipStream_t st);
 
+// sensor stage between the plant and the controller (sensor_kernel.hip; include/bluerov2_nmpc.h, brov_sensor_*): the measured state the
+// solve, the observer and the estimator read in place of the plant's true state.  A fresh sample is a pure function of (these records,
+// instance, measurement index, channel, true value); the only state is the measured state itself, which a held channel keeps.
+struct SensorPar {                // shared by the batch and wave-uniform: passed by value in the kernel arguments
+    double quant[12];             // quantisation step of a channel, 0: none
+    int32_t period[12];           // a regular refresh samples channel c where index % period[c] == 0
+    unsigned long long seed;
+};
+struct SensorDev {                // per instance
+    const double* sigma = nullptr;       // [B][12] standard deviation of the noise
+    const double* bias = nullptr;        // [B][12]
+    const double* dropout = nullptr;     // [B] probability that a regular refresh's fix is dropped
+    int32_t* dropped = nullptr;          // [B] statistics of the regular refreshes: fixes dropped ...
+    double* err_sq = nullptr;            // [B][12] ... and the running sum of (measured - true)^2 behind each of them
+};
+// one refresh of ymeas [B][12] from the true state x [B][12] at measurement index m (0 <= m < 2^24): regular (periods, dropout, statistics)
+// or forced (every channel fresh, no dropout draw, statistics untouched)
+void launch_sensor_measure(const SensorPar& P, const SensorDev& D, int B, long long m, bool forced, const double* x, double* ymeas, hipStream_t st);
+// the stage alone: fresh samples y [B][12] of the states x [B][12] at index m and the dropout verdicts [B]; moves nothing
+void launch_sensor_eval(const SensorPar& P, const SensorDev& D, int B, long long m, const double* x, double* y, int32_t* dropped, hipStream_t st);
+
 }  // namespace brov

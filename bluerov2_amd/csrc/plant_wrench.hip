@@ -18,15 +18,9 @@
 
 #include "nmpc_device.hpp"
 #include "bluerov2_model.hpp"
+#include "rounded_ops.hpp"   // splitmix64_finalise, rn_mul, rn_add
 
 namespace brov {
-
-// the output function of SplitMix64 (Steele, Lea, Flood 2014; public domain reference implementation by S. Vigna)
-__device__ __forceinline__ unsigned long long splitmix64_finalise(unsigned long long z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
 
 // amplitude of channel c (X = 0, Y = 1, Z = 2, N = 3) of instance b in half period j: scale * uniform[0.5, 1), counter-based
 __device__ __forceinline__ double wrench_amplitude(const WrenchGen& g, int b, long long j, int c) {
@@ -150,20 +144,7 @@ __global__ __launch_bounds__(128) void plant_wrench_kernel(double* __restrict__ 
 //   a[i] = k >= onset[b] ? gain[b][i] * c[i] + bias[b][i] : c[i]                product rounded, then the sum
 //   g[r] = ((((K[r][0] a[0] + K[r][1] a[1]) + K[r][2] a[2]) + K[r][3] a[3]) + K[r][4] a[4]) + K[r][5] a[5]
 // every operation rounded on its own: the evaluation kernel, the plant kernel and the numpy restatement of tests/thruster_restatement.py
-// agree bit for bit.  No state: any tick can be evaluated again.
-//
-// rn_mul / rn_add: one product / one sum, rounded to nearest, that no caller's context fuses.  __dmul_rn / __dadd_rn do not give that here: the header defines
-// them as inline functions `x * y` / `x + y` compiled OUTSIDE a caller's `fp contract(off)`, so their instructions carry the contract flag
-// into the caller, and a stage written with them compiled to 36 v_fmac_f64 (wrench_at's two products happen to be exact or added to zero
-// in every test).  Written here under the pragma, the instructions carry no such flag wherever they are inlined.
-__device__ __forceinline__ double rn_mul(double p, double q) {
-#pragma clang fp contract(off)
-    return p * q;
-}
-__device__ __forceinline__ double rn_add(double p, double q) {
-#pragma clang fp contract(off)
-    return p + q;
-}
+// agree bit for bit.  No state: any tick can be evaluated again.  (rn_mul / rn_add, and why not __dmul_rn / __dadd_rn: rounded_ops.hpp)
 __device__ __forceinline__ void thruster_stage(const ThrusterPar& T, const ThrusterDev& D, int b, long long k, const double (&t)[6], double (&a)[6],
                                                double (&g)[6]) {
 #pragma clang fp contract(off)

@@ -437,7 +437,7 @@ extern "C" int brov_rls_update_from_ekf(brov_rls* r, const brov_ekf* ekf, brov_s
     if (ekf_wait_last_update(ekf, st) != BROV_OK) { g_rls_err = "brov_rls_update_from_ekf: could not order behind the EKF's last update"; return BROV_ERR_HIP; }
     if (r->last_stream != st) if (int rc = sync_last(r)) return rc;
     hipLaunchKernelGGL(rls_inputs_kernel, dim3((r->G + kRlsBlock - 1) / kRlsBlock), dim3(kRlsBlock), 0, st, r->G, r->par.dt,
-                       (const double*)brov_x0_device(s), brov_ekf_x_device(ekf), r->vprev, r->y, r->acc, r->vel, r->rpy);
+                       solver_measured_state(s), brov_ekf_x_device(ekf), r->vprev, r->y, r->acc, r->vel, r->rpy);
     HIPCHK(hipGetLastError());
     return launch_update(r, r->y, r->acc, r->vel, r->rpy, st);
 }

@@ -136,6 +136,10 @@ def _protos(L):
         "brov_thruster_eval_host": [vp, C.c_int64, dp, dp, dp], "brov_thruster_last_host": [vp, dp],
         "brov_thruster_get_stats_host": [vp, C.POINTER(C.c_int32), dp, C.POINTER(C.c_int64)], "brov_thruster_reset_stats": [vp],
         "brov_thruster_last_seconds": [vp, dp],
+        "brov_sensor_set_host": [vp, C.c_uint64, dp, dp, dp, C.POINTER(C.c_int32), dp], "brov_sensor_off": [vp], "brov_sensor_enabled": [vp],
+        "brov_sensor_measure": [vp, vp], "brov_sensor_eval_host": [vp, C.c_int64, dp, dp, C.POINTER(C.c_int32)],
+        "brov_sensor_get_measurement_host": [vp, dp], "brov_sensor_get_stats_host": [vp, C.POINTER(C.c_int32), dp, C.POINTER(C.c_int64)],
+        "brov_sensor_reset_stats": [vp], "brov_sensor_last_seconds": [vp, dp],
     })
     _bind(L, {"brov_thruster_default_matrix": [dp]}, None)
 
@@ -596,6 +600,64 @@ class BatchSolver(_Handle):
         K = np.empty((6, 6))
         _load().brov_thruster_default_matrix(_dp(K))
         return K
+
+    # ---- sensor stage between plant and controller: noise, bias, quantisation, slow and dropped fixes (brov_sensor_*) ------------------
+    def set_sensors(self, seed=0, sigma=None, bias=None, quant=None, period=None, dropout=None):
+        """from now on solve(), the loops, the observer and the estimator read the MEASURED state instead of the plant's true state (the plant,
+        the logs and the tracker keep the true one); the statistics start afresh and the measured state is refreshed from x0.  The fresh sample
+        of channel c at measurement index m (plant_wrench_tick()): v = (x + bias) + sigma * n(b, m, c);  y = rint(v / quant) * quant where
+        quant > 0.  n is an Irwin-Hall(12) variate -- unit variance, bounded by +-6, kurtosis 2.9 --, not a Gaussian.
+            sigma, bias  scalar, [12] or [B, 12] (None: 0)
+            quant        scalar or [12], shared by the batch (None or 0: none)
+            period       scalar or [12] int >= 1: a plant step refreshes channel c where the index is a multiple of period[c] (None: 1)
+            dropout      scalar or [B] in [0, 1]: probability that the fix behind a plant step is dropped and every channel holds (None: 0)"""
+        def rows(v, shape, dtype=np.float64):
+            return None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dtype), shape))
+        sg, bi, dr = rows(sigma, (self.B, NX)), rows(bias, (self.B, NX)), rows(dropout, (self.B,))
+        qu, pe = rows(quant, (NX,)), rows(period, (NX,), np.int32)
+        self._chk(self._L.brov_sensor_set_host(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, _dp(sg), _dp(bi), _dp(qu),
+                                               None if pe is None else pe.ctypes.data_as(C.POINTER(C.c_int32)), _dp(dr)), "set_sensors")
+
+    def sensors_off(self):
+        """everything reads the plant's true state again, no extra launch; the statistics stay readable"""
+        self._chk(self._L.brov_sensor_off(self._h), "sensors_off")
+
+    def sensors_enabled(self):
+        return bool(self._L.brov_sensor_enabled(self._h))
+
+    def sensor_measure(self, stream=0):
+        """a forced refresh of the measured state at the current index, for a caller that wrote x0 through x0_device_ptr()"""
+        self._chk(self._L.brov_sensor_measure(self._h, C.c_void_p(stream)), "sensor_measure")
+
+    def sensor_eval(self, index, x):
+        """(y [B, 12], dropped [B] int32): fresh samples of the states `x` [B, 12] at `index` and the dropout verdicts of that index; moves
+        nothing, touches no statistic"""
+        xa = _arr(x, (self.B, NX))
+        y, dr = np.empty((self.B, NX)), np.zeros(self.B, dtype=np.int32)
+        self._chk(self._L.brov_sensor_eval_host(self._h, int(index), _dp(xa), _dp(y), dr.ctypes.data_as(C.POINTER(C.c_int32))), "sensor_eval")
+        return y, dr
+
+    def measured_state(self):
+        """[B, 12]: the measured state as the last refresh left it"""
+        y = np.empty((self.B, NX))
+        self._chk(self._L.brov_sensor_get_measurement_host(self._h, _dp(y)), "measured_state")
+        return y
+
+    def sensor_stats(self):
+        """dict(dropped [B] int32: fixes dropped; err_sq [B, 12]: running sum of (measured - true)^2 behind every plant step, held values
+        included; refreshes: plant steps behind which the stage ran since the statistics were reset)"""
+        dr, esq, n = np.zeros(self.B, dtype=np.int32), np.empty((self.B, NX)), C.c_int64(0)
+        self._chk(self._L.brov_sensor_get_stats_host(self._h, dr.ctypes.data_as(C.POINTER(C.c_int32)), _dp(esq), C.byref(n)), "sensor_stats")
+        return dict(dropped=dr, err_sq=esq, refreshes=int(n.value))
+
+    def sensor_reset_stats(self):
+        self._chk(self._L.brov_sensor_reset_stats(self._h), "sensor_reset_stats")
+
+    def sensor_last_seconds(self):
+        """duration of the measure kernel's last launch (HIP events)"""
+        sec = C.c_double(0.0)
+        self._chk(self._L.brov_sensor_last_seconds(self._h, C.byref(sec)), "sensor_last_seconds")
+        return sec.value
 
     # ---- iterate ----------------------------------------------------------------------------------------------
     def set_iterate(self, x=None, u=None, pi=None, lam=None):

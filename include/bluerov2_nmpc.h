@@ -248,6 +248,45 @@ int brov_thruster_get_stats_host(brov_solver* s, int32_t* clip_ticks /*[B][6]*/,
 int brov_thruster_reset_stats(brov_solver* s);
 int brov_thruster_last_seconds(brov_solver* s, double* seconds);                  /* the plant kernel's last launch behind the stage, HIP events */
 
+/* ---- sensor stage between the plant and the controller: noisy, biased, quantised, slow and dropped measurements.  Without it the solve, the
+ * observer (brov_ekf_update_from_solver) and the estimator (brov_rls_update_from_ekf) read the plant's true state.  While the stage is on they
+ * read the MEASURED state ymeas [B][12] instead; the plant, the logs and the tracker keep the true state x0.  The fresh sample of channel c of
+ * instance b at measurement index m (the plant's tick counter, brov_plant_wrench_tick), x the true value:
+ *     v = (x + bias[b][c]) + sigma[b][c] * n(b, m, c)                              every operation rounded on its own: no FMA
+ *     y = quant[c] > 0 ? rint(v / quant[c]) * quant[c] : v                         rint: ties to even; a NaN passes through
+ * n is a counter-based variate built from integers alone (a restatement needs no libm and agrees bit for bit): with
+ * H(k) = splitmix64_finalise((seed ^ 0x53454E534F52) + (k + 1) * 0x9E3779B97F4A7C15) and k = (b << 32) | (m << 8) | (c << 2) | j, S = the sum of
+ * the twelve 16-bit fields of H at j = 0, 1, 2 and n = (S - 393210) / 65536.  This is an Irwin-Hall(12) variate, not a Gaussian: variance
+ * 1 - 2^-32, bounded by +-6, kurtosis 2.9 instead of 3.  The dropout draw of (b, m) is u = (H(k) >> 11) * 2^-53 at the channel slot c = 12,
+ * j = 0; the fix is dropped iff dropout[b] > 0 && u < dropout[b].  sigma, bias [B][12] and dropout [B] are per instance; quant [12] (0: none),
+ * period [12] and the seed are shared by the batch.  Indices are limited to 0 <= m < 2^24.
+ * Two kinds of refresh of ymeas (sensor_measure_kernel):
+ *   regular, at index m   a dropped fix samples nothing; otherwise channel c takes its fresh sample iff m % period[c] == 0 and else keeps its
+ *                         value.  Then the statistics: dropped[b] += drop, err_sq[b][c] += (ymeas[c] - x[c])^2 AFTER the refresh, so a held,
+ *                         stale value counts as the error the controller really sees; the host counts the refreshes.
+ *   forced, at index m    every channel takes its fresh sample; no dropout draw, the statistics untouched.
+ * Regular: behind the plant kernel of brov_plant_step and of every tick of the loops built on it (brov_closed_loop / _ex / _dob / _track), on
+ * the same stream, at the counter's new value.  Forced, at the current index: brov_sensor_set_host (which first resets the statistics),
+ * brov_set_x0_host / brov_set_x0_device while the stage is on (on their stream), and brov_sensor_measure for a caller that wrote x0 some
+ * other way.  A brov_tick_host that brings its own x0 is solved at that x0: the caller supplied the measurement.  The one-launch closed loop
+ * and the *_ticks kernels know no sensor: the loops take their launch-per-tick branch.  A loop that would pass index 2^24 is refused before
+ * anything is launched.  Out of scope and refused while the stage is on: brov_fleet_step, brov_closed_loop_fleet, brov_closed_loop_fleet_dob.
+ * Stage off (the default, and after brov_sensor_off): no extra launch, everything reads x0 as before; the statistics stay readable.
+ * Refused with BROV_ERR_ARG and a text in brov_last_error() that starts with the call's name (nothing changes, nothing is waited for): a NULL
+ * handle, a NaN or negative sigma or quant, a non-finite bias, period < 1, dropout outside [0, 1], an index outside [0, 2^24). */
+int brov_sensor_set_host(brov_solver* s, uint64_t seed, const double* sigma /*[B][12]; NULL: 0*/, const double* bias /*[B][12]; NULL: 0*/,
+                         const double* quant /*[12]; NULL: none*/, const int32_t* period /*[12]; NULL: 1*/, const double* dropout /*[B]; NULL: 0*/);
+int brov_sensor_off(brov_solver* s);
+int brov_sensor_enabled(const brov_solver* s);                 /* 0 for NULL */
+int brov_sensor_measure(brov_solver* s, void* stream);         /* forced refresh at the current index */
+/* the stage alone: fresh samples of the states x at `index` and the dropout verdicts; moves nothing, touches no statistic (before any
+ * brov_sensor_set_host: the defaults) */
+int brov_sensor_eval_host(brov_solver* s, int64_t index, const double* x /*[B][12]*/, double* y /*[B][12]*/, int32_t* dropped /*[B] or NULL*/);
+int brov_sensor_get_measurement_host(brov_solver* s, double* y /*[B][12]*/);   /* as the last refresh left it (zeros before the first) */
+int brov_sensor_get_stats_host(brov_solver* s, int32_t* dropped /*[B]*/, double* err_sq /*[B][12]*/, int64_t* refreshes /*any NULL*/);
+int brov_sensor_reset_stats(brov_solver* s);
+int brov_sensor_last_seconds(brov_solver* s, double* seconds); /* the measure kernel's last launch, HIP events */
+
 /* iterate (warm start) access; any pointer may be NULL to skip that block */
 int brov_set_iterate_host(brov_solver* s, const double* x, const double* u, const double* pi, const double* lam);
 int brov_get_iterate_host(brov_solver* s, double* x, double* u, double* pi, double* lam);
