@@ -62,6 +62,14 @@ struct brov_fleet {
 };
 
 extern "C" const char* brov_fleet_last_error(void) { return g_fleet_err.c_str(); }
+// What the entry point `who` hands to the wrench source (CallCtx, host_common.hpp); its wait: the device, and the host wait for a step in flight
+// that may still read the generator's buffers
+static int wrench_wait(brov_fleet* f) {
+    HIPCHK(hipSetDevice(f->device));
+    HIPCHK(hipStreamSynchronize(f->last_stream));
+    return BROV_OK;
+}
+static CallCtx call_ctx(brov_fleet* f, const char* who) { return {[f] { return wrench_wait(f); }, f->mem, g_fleet_err, who}; }
 
 extern "C" void brov_fleet_destroy(brov_fleet* f) {
     if (!f) return;
@@ -172,7 +180,7 @@ extern "C" int brov_fleet_create(brov_fleet** out, brov_solver* s, int candidate
     if (rc == BROV_OK) rc = f->mem.alloc(&f->cl.min_d2, V, g_fleet_err);
     if (rc == BROV_OK) rc = f->mem.alloc(&f->cl.below, V, g_fleet_err);
     f->wr.B = V;
-    if (rc == BROV_OK) rc = f->wr.reserve(f->mem, g_fleet_err);   // eager: a step reads the eval buffer without a host wait
+    if (rc == BROV_OK) rc = f->wr.reserve(call_ctx(f, "brov_fleet_create"));   // eager: a step reads the eval buffer without a host wait
     if (rc != BROV_OK) { g_fleet_err = "brov_fleet_create: " + g_fleet_err; brov_fleet_destroy(f); return rc; }
     if (f->timer.create() != hipSuccess || f->cl.timer.create() != hipSuccess || hipEventCreateWithFlags(&f->ev_done, hipEventDisableTiming) != hipSuccess) {
         g_fleet_err = "brov_fleet_create: device initialisation failed";
@@ -246,33 +254,24 @@ extern "C" int brov_fleet_select_host(brov_fleet* f, const brov_result* rec_host
 // ---- the world-frame wrench of the vehicles: the solver's generator (plant_wrench.hip) at batch V, thin forwards to the one host side,
 // wrench_source.hpp -------------------------------------------------------------------------------------------------------------------------
 static int no_fleet(const char* who) { g_fleet_err = std::string(who) + ": null argument"; return BROV_ERR_ARG; }
-// the device, and the host wait for a step in flight that may still read the generator's buffers
-static int wrench_wait(brov_fleet* f) {
-    HIPCHK(hipSetDevice(f->device));
-    HIPCHK(hipStreamSynchronize(f->last_stream));
-    return BROV_OK;
-}
 extern "C" int brov_vehicle_wrench_constant_host(brov_fleet* f, const double* w) {
-    if (!f) return no_fleet("brov_vehicle_wrench_constant_host");
-    return f->wr.constant_host(w, [f] { return wrench_wait(f); }, f->mem, g_fleet_err, "brov_vehicle_wrench_constant_host");
+    return f ? f->wr.constant_host(w, call_ctx(f, "brov_vehicle_wrench_constant_host")) : no_fleet("brov_vehicle_wrench_constant_host");
 }
 extern "C" int brov_vehicle_wrench_periodic(brov_fleet* f, uint64_t seed, double scale, double phase0, double dphi, double tz_div) {
     if (!f) return no_fleet("brov_vehicle_wrench_periodic");
-    return f->wr.periodic(seed, scale, phase0, dphi, tz_div, g_fleet_err, "brov_vehicle_wrench_periodic");
+    return f->wr.periodic(seed, scale, phase0, dphi, tz_div, call_ctx(f, "brov_vehicle_wrench_periodic"));
 }
 extern "C" int brov_vehicle_wrench_table_host(brov_fleet* f, const double* tab, int rows, const double* gain) {
-    if (!f) return no_fleet("brov_vehicle_wrench_table_host");
-    return f->wr.table_host(tab, rows, gain, [f] { return wrench_wait(f); }, f->mem, g_fleet_err, "brov_vehicle_wrench_table_host");
+    return f ? f->wr.table_host(tab, rows, gain, call_ctx(f, "brov_vehicle_wrench_table_host")) : no_fleet("brov_vehicle_wrench_table_host");
 }
 extern "C" int brov_vehicle_wrench_off(brov_fleet* f) { return f ? f->wr.set_off() : no_fleet("brov_vehicle_wrench_off"); }
 extern "C" int brov_vehicle_wrench_mode(const brov_fleet* f) { return f ? f->wr.mode() : BROV_WRENCH_OFF; }
 extern "C" int brov_vehicle_wrench_seek(brov_fleet* f, int64_t tick) {
-    return f ? f->wr.seek(tick, g_fleet_err, "brov_vehicle_wrench_seek") : no_fleet("brov_vehicle_wrench_seek");
+    return f ? f->wr.seek(tick, call_ctx(f, "brov_vehicle_wrench_seek")) : no_fleet("brov_vehicle_wrench_seek");
 }
 extern "C" int64_t brov_vehicle_wrench_tick(const brov_fleet* f) { return f ? (int64_t)f->wr.tick : 0; }
 extern "C" int brov_vehicle_wrench_eval_host(brov_fleet* f, int64_t tick, double* w) {
-    if (!f) return no_fleet("brov_vehicle_wrench_eval_host");
-    return f->wr.eval_host(tick, w, f->last_stream, [f] { return wrench_wait(f); }, f->mem, g_fleet_err, "brov_vehicle_wrench_eval_host");
+    return f ? f->wr.eval_host(tick, w, f->last_stream, call_ctx(f, "brov_vehicle_wrench_eval_host")) : no_fleet("brov_vehicle_wrench_eval_host");
 }
 
 // what the plant of the fleet does not model: the vehicles' wrench is the fleet's (brov_vehicle_wrench_*), indexed
@@ -355,7 +354,7 @@ extern "C" int brov_fleet_step(brov_fleet* f, const brov_result* rec, double dt,
         return BROV_ERR_ARG;
     }
     if (int rc = plant_modes_ok(f, "brov_fleet_step")) return rc;
-    if (int rc = f->wr.steps_ok(1, g_fleet_err, "brov_fleet_step")) return rc;
+    if (int rc = f->wr.steps_ok(1, call_ctx(f, "brov_fleet_step"))) return rc;
     HIPCHK(hipSetDevice(f->device));
     hipStream_t st = (hipStream_t)stream;
     if (int rc = order_both(f, st, "brov_fleet_step")) return rc;
@@ -447,7 +446,7 @@ static int fleet_loop(brov_fleet* f, brov_ekf* e, const char* who, int ticks, do
         if (int rc = observer_ok(f, e, who)) return rc;
         if (int rc = apply_ok(f, who)) return rc;
     }
-    if (int rc = f->wr.steps_ok(ticks, g_fleet_err, who)) return rc;
+    if (int rc = f->wr.steps_ok(ticks, call_ctx(f, who))) return rc;
     const SolverView sv = solver_view(f->s);
     if (!sv.cand_set) {
         g_fleet_err = pre + "no candidate parameters (brov_set_candidate_params_host)";

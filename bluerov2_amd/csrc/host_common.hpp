@@ -1,11 +1,13 @@
 // host_common.hpp -- the host-side scaffolding every device object of the C ABI is built from (brov_solver, brov_ekf, brov_rls, brov_track,
 // brov_group): the HIP error check, the "is this device usable" test of the create calls, an owner of device allocations, a two-event kernel
-// timer, a scoped temporary device buffer, the logs of a closed loop.  Host code only, header only.  Each component keeps its OWN thread-local
-// error string and brov_*_last_error(): a failing observer call must not overwrite brov_last_error(), so what reports here takes the string to write.
+// timer, the call context and the common part of the plant's stages, a scoped temporary device buffer, the logs of a closed loop.  Host code
+// only, header only.  Each component keeps its OWN thread-local error string and brov_*_last_error(): a failing observer call must not
+// overwrite brov_last_error(), so what reports here takes the string to write.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -91,6 +93,42 @@ struct KernelTimer {
         float ms = 0.f;
         BROV_HIPCHK(err, hipEventElapsedTime(&ms, ev[0], ev[1]));
         *out = ms * 1e-3;
+        return BROV_OK;
+    }
+};
+
+// ---- what an entry point hands to the host side of a plant stage (wrench_source.hpp, thruster_source.hpp, sensor_source.hpp) with its own
+// arguments.  Built per call in the calling thread by the owner's one helper and never stored: the error string is thread-local.  A method
+// checks its arguments first and calls wait() once they have passed: a refused call waits for nothing and changes nothing.
+struct CallCtx {
+    std::function<int()> wait;   // the owner's: it selects the device, waits on the host for what may still use the buffers and returns a code
+    DeviceAllocs& mem;           // the owner's allocations, which the stage's buffers come from
+    std::string& err;            // the owner's error string ...
+    const char* who;             // ... and the public name this call reports under
+    int refuse(const char* why) const { err = std::string(who) + ": " + why; return BROV_ERR_ARG; }
+};
+
+// ---- what the two switchable stages of a solver's plant (ThrusterSource, SensorSource) have in common --------------------------------------
+struct PlantStage {
+    bool on = false;               // the stage is in force (off: everything as it always was)
+    bool configured = false;       // the buffers hold a configuration (the last *_set_host's, or the defaults)
+    size_t B = 0;                  // instances, set by the owner at create
+    KernelTimer timer;             // around the last launch of the stage's kernel
+    void destroy() { timer.destroy(); }
+    int set_off() { on = false; return BROV_OK; }
+    int last_seconds(double* seconds, const char* nothing_timed, const CallCtx& c) {
+        if (!seconds || !timer.valid) return c.refuse(seconds ? nothing_timed : "null argument");
+        return timer.seconds(seconds, c.err);
+    }
+    // one buffer of the stage on first use: from the owner's allocations, zeroed before the stage sees it (and, ahead of the first, the timer)
+    template <typename T>
+    int buffer(T** p, size_t n, const CallCtx& c) {
+        T* q = nullptr;
+        if (*p) return BROV_OK;
+        if (!timer.ev[0]) BROV_HIPCHK(c.err, timer.create());
+        if (int rc = c.mem.alloc(&q, n, c.err)) return rc;
+        BROV_HIPCHK(c.err, hipMemset(q, 0, n * sizeof(T)));
+        *p = q;
         return BROV_OK;
     }
 };

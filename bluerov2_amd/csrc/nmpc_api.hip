@@ -17,9 +17,7 @@
 #include "host_common.hpp"
 #include "nmpc_device.hpp"
 #include "select_device.hpp"
-#include "wrench_source.hpp"
-#include "thruster_source.hpp"
-#include "sensor_source.hpp"
+#include "solver_plant.hpp"
 
 using namespace brov;
 
@@ -99,15 +97,9 @@ struct brov_solver {
     double* traj = nullptr;
     int traj_rows = 0;
     double* scratch3 = nullptr;  // [3][B] candidate parameters
-    double* pplant = nullptr;    // [B][16] true plant parameters
     double* par_rp = nullptr;    // 6-disturbance variant: roll / pitch disturbance moments [B][N+1][2] (allocated by brov_enable_dist6)
-    double* prp_plant = nullptr; // ... of the plant [B][2] (brov_plant_set_rp_disturbance_host); else the controller's stage 0
-    bool dist6 = false, prp_plant_set = false;
-    bool pplant_set = false;     // explicit plant parameters given (brov_plant_set_params_host)
-    bool pplant_stale = true;    // controller parameters changed since the plant's copy of them was taken
-    WrenchSource wr;             // world-frame wrench of the plant (brov_plant_wrench_*), its buffers allocated on first use; its counter: plant steps so far
-    ThrusterSource th;           // thruster stage of the plant (brov_thruster_*): limits, faults and propulsion matrix, its buffers allocated on first use
-    SensorSource sn;             // sensor stage (brov_sensor_*): the measured state the solve, the observer and the estimator read while it is on, its buffers allocated on first use
+    bool dist6 = false;
+    SolverPlant plant;           // the simulated plant (solver_plant.hpp): its parameters, wrench, thruster and sensor stages, its step counter
     bool cand_set = false;       // candidate shape parameters resident in scratch3
     int cand_kind = 0;
     bool dump_lin = false;
@@ -330,9 +322,6 @@ extern "C" int brov_create(brov_solver** out, int device, int B, const brov_opts
     s->B = B;
     s->N = opts->N;
     s->opts = *opts;
-    s->wr.B = (size_t)B;
-    s->th.B = (size_t)B;
-    s->sn.B = (size_t)B;
     const size_t N = opts->N, Bz = B;
     int rc = BROV_OK;
 #define AL(ptr, n) if (rc == BROV_OK) rc = s->mem.alloc(&s->ptr, (n), g_err)
@@ -361,7 +350,7 @@ extern "C" int brov_create(brov_solver** out, int device, int B, const brov_opts
     AL(best, 2);
     AL(scratch3, 3 * Bz);
     AL(lines, Bz);
-    AL(pplant, Bz * 16);
+    AL(plant.pplant, Bz * 16);
     AL(counter, 64);   // two hand-out counters of the windowed kernel, 128 bytes apart, used alternately
     AL(pit_done, Bz);   // rti_pit_kernel's per-instance verdict
     AL(sched, 3 * (size_t)sched_buffer_ints_host(B));
@@ -374,6 +363,7 @@ extern "C" int brov_create(brov_solver** out, int device, int B, const brov_opts
     if (w.split_doubles) { AL(ws_split, w.split_doubles); }
 #undef AL
     if (rc != BROV_OK) { brov_destroy(s); return rc; }
+    s->plant.init(B, opts->N, s->x0, s->res, s->par, &s->par_rp, &s->dist6);
     // create defaults: yref = 0, p = 0, x0 = [0,0,-20,0..] (acados_solver_bluerov2.c:355-364, 405-420, 520-527)
     hipMemset(s->yref, 0, Bz * (N + 1) * 16 * sizeof(double));
     hipMemset(s->yref_sh, 0, (N + 1) * 16 * sizeof(double));
@@ -401,9 +391,7 @@ extern "C" void brov_destroy(brov_solver* s) {
     // (a caller's own stream is the caller's to drain -- it may not exist any more; hipFree below waits for the device in any case)
     s->mem.free_all();
     if (s->traj) hipFree(s->traj);
-    s->wr.destroy();
-    s->th.destroy();
-    s->sn.destroy();
+    s->plant.destroy();
     if (s->dbg) hipFree(s->dbg);
     s->tick.destroy();
     for (int k = 0; k < 3; k++)
@@ -461,15 +449,28 @@ static int copy_in(brov_solver* s, double* dst, const double* src, size_t n, boo
     return BROV_OK;
 }
 
+// What the entry point `who` hands to the plant and its stages (CallCtx, host_common.hpp).  The solver has two waits: wrench_wait, for a plant step
+// in flight that may still read the buffers; sensor_wait, for the whole device: a refresh may be enqueued on any stream a plant step was given
+static int wrench_wait(brov_solver* s) {
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(sync_last(s));
+    return BROV_OK;
+}
+static int sensor_wait(brov_solver* s) {
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipDeviceSynchronize());
+    s->tick.copies_pending = false;
+    return BROV_OK;
+}
+static CallCtx call_ctx(brov_solver* s, const char* who, int (*wait)(brov_solver*) = wrench_wait) {
+    return {[s, wait] { return wait(s); }, s->mem, g_err, who};
+}
+
 // the plant's true state; with the sensor stage on the measured state follows it: a forced refresh at the current index behind the copy
 static int set_x0(brov_solver* s, const double* x0, bool host, void* st, const char* who) {
-    const bool measured = s && x0 && s->sn.on;
-    if (measured) { if (int rc = SensorSource::index_ok(s->wr.tick, g_err, who)) return rc; }
+    if (s && x0) { if (int rc = s->plant.rewrite_ok(call_ctx(s, who))) return rc; }
     if (int rc = copy_in(s, s ? s->x0 : nullptr, x0, s ? (size_t)s->B * 12 : 0, host, st)) return rc;
-    if (measured) {
-        s->sn.measure(s->x0, s->wr.tick, true, host ? s->last_stream : (hipStream_t)st);
-        HIPCHK(hipGetLastError());
-    }
+    if (s->plant.rewritten(host ? s->last_stream : (hipStream_t)st)) HIPCHK(hipGetLastError());
     return BROV_OK;
 }
 extern "C" int brov_set_x0_host(brov_solver* s, const double* x0) { return set_x0(s, x0, true, nullptr, "brov_set_x0_host"); }
@@ -514,7 +515,7 @@ static int set_stage_rows(brov_solver* s, double* dst, const double* p, int w, i
 }
 static int set_par(brov_solver* s, const double* p, int per_stage, bool host, void* st) {
     if (!s || !p) return BROV_ERR_ARG;
-    s->pplant_stale = true;
+    s->plant.params_changed();
     return set_stage_rows(s, s->par, p, 16, per_stage, host, st);
 }
 extern "C" int brov_set_params_host(brov_solver* s, const double* p, int per_stage) { return set_par(s, p, per_stage, true, nullptr); }
@@ -525,7 +526,7 @@ extern "C" int brov_set_param_stage_host(brov_solver* s, int inst, int stage, co
     HIPCHK(hipSetDevice(s->device));
     HIPCHK(sync_last(s));
     HIPCHK(hipMemcpy(s->par + ((size_t)inst * (s->N + 1) + stage) * 16, p16, 16 * sizeof(double), hipMemcpyHostToDevice));
-    if (stage == 0) s->pplant_stale = true;
+    if (stage == 0) s->plant.params_changed();
     return BROV_OK;
 }
 // ---- boundary corners of the reference API: non-uniform grids and a separate stage-0 weight ------------------------------------
@@ -581,10 +582,10 @@ extern "C" int brov_enable_dist6(brov_solver* s, int on) {
     if (on && !s->par_rp) {
         const size_t n = (size_t)s->B * (s->N + 1) * 2;
         int rc = s->mem.alloc(&s->par_rp, n, g_err);
-        if (rc == BROV_OK) rc = s->mem.alloc(&s->prp_plant, (size_t)s->B * 2, g_err);
+        if (rc == BROV_OK) rc = s->mem.alloc(&s->plant.prp_plant, (size_t)s->B * 2, g_err);
         if (rc != BROV_OK) return rc;
         HIPCHK(hipMemset(s->par_rp, 0, n * sizeof(double)));
-        HIPCHK(hipMemset(s->prp_plant, 0, (size_t)s->B * 2 * sizeof(double)));
+        HIPCHK(hipMemset(s->plant.prp_plant, 0, (size_t)s->B * 2 * sizeof(double)));
     }
     s->dist6 = on != 0;
     return BROV_OK;
@@ -622,16 +623,16 @@ extern "C" int brov_set_params18_host(brov_solver* s, const double* p18, int per
     HIPCHK(hipMemcpy(tmp.p, p18, nsrc * sizeof(double), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(split_p18_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, nullptr, tmp.p, s->par, s->par_rp, rows, (int)N1, per_stage);
     HIPCHK(hipDeviceSynchronize());
-    s->pplant_stale = true;
+    s->plant.params_changed();
     return BROV_OK;
 }
 extern "C" int brov_plant_set_rp_disturbance_host(brov_solver* s, const double* d) {
     if (int rc = need_dist6(s, "brov_plant_set_rp_disturbance_host")) return rc;
-    if (!d) { s->prp_plant_set = false; return BROV_OK; }
+    if (!d) { s->plant.prp_plant_set = false; return BROV_OK; }
     HIPCHK(hipSetDevice(s->device));
     HIPCHK(sync_last(s));
-    HIPCHK(hipMemcpy(s->prp_plant, d, (size_t)s->B * 2 * sizeof(double), hipMemcpyHostToDevice));
-    s->prp_plant_set = true;
+    HIPCHK(hipMemcpy(s->plant.prp_plant, d, (size_t)s->B * 2 * sizeof(double), hipMemcpyHostToDevice));
+    s->plant.prp_plant_set = true;
     return BROV_OK;
 }
 
@@ -752,150 +753,106 @@ __global__ void gather_status_kernel(const brov_result* __restrict__ res, int* _
 extern "C" int brov_plant_set_params_host(brov_solver* s, const double* p) {
     if (!s || !p) return BROV_ERR_ARG;
     HIPCHK(hipSetDevice(s->device));
-    HIPCHK(hipMemcpy(s->pplant, p, (size_t)s->B * 16 * sizeof(double), hipMemcpyHostToDevice));
-    s->pplant_set = true;
-    return BROV_OK;
-}
-// Without explicit plant parameters the plant is the controller's own model: stage-0 parameters, re-read whenever the
-// controller's parameters may have changed (setters, brov_params_device() hand-outs, the EKF's write-back).
-// roll / pitch disturbance moments the plant integrates (6-disturbance variant): its own, else the controller's stage 0, else none
-static const double* plant_rp(const brov_solver* s) { return s->prp_plant_set ? s->prp_plant : (s->dist6 && !s->pplant_set ? s->par_rp : nullptr); }
-static int plant_rp_stride(const brov_solver* s) { return s->prp_plant_set ? 2 : (s->N + 1) * 2; }
-static int ensure_plant_params(brov_solver* s, hipStream_t st) {
-    if (!s->pplant_set && s->pplant_stale) {
-        hipLaunchKernelGGL(copy_stage0_par_kernel, dim3((s->B * 16 + 255) / 256), dim3(256), 0, st, s->par, s->pplant, s->B, s->N + 1);
-        s->pplant_stale = false;
-    }
+    HIPCHK(hipMemcpy(s->plant.pplant, p, (size_t)s->B * 16 * sizeof(double), hipMemcpyHostToDevice));
+    s->plant.pplant_set = true;
     return BROV_OK;
 }
 // ---- time-varying world-frame wrench of the plant (plant_wrench.hip): thin forwards to the one host side, wrench_source.hpp -------------------
 static int no_solver(const char* who) { g_err = std::string(who) + ": null argument"; return BROV_ERR_ARG; }
-// the device, and the host wait for a plant step in flight that may still read the generator's buffers
-static int wrench_wait(brov_solver* s) {
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(sync_last(s));
-    return BROV_OK;
-}
 extern "C" int brov_plant_wrench_constant_host(brov_solver* s, const double* w) {
-    if (!s) return no_solver("brov_plant_wrench_constant_host");
-    return s->wr.constant_host(w, [s] { return wrench_wait(s); }, s->mem, g_err, "brov_plant_wrench_constant_host");
+    return s ? s->plant.wr.constant_host(w, call_ctx(s, "brov_plant_wrench_constant_host")) : no_solver("brov_plant_wrench_constant_host");
 }
 extern "C" int brov_plant_wrench_periodic(brov_solver* s, uint64_t seed, double scale, double phase0, double dphi, double tz_div) {
     if (!s) return no_solver("brov_plant_wrench_periodic");
-    return s->wr.periodic(seed, scale, phase0, dphi, tz_div, g_err, "brov_plant_wrench_periodic");
+    return s->plant.wr.periodic(seed, scale, phase0, dphi, tz_div, call_ctx(s, "brov_plant_wrench_periodic"));
 }
 extern "C" int brov_plant_wrench_table_host(brov_solver* s, const double* tab, int rows, const double* gain) {
-    if (!s) return no_solver("brov_plant_wrench_table_host");
-    return s->wr.table_host(tab, rows, gain, [s] { return wrench_wait(s); }, s->mem, g_err, "brov_plant_wrench_table_host");
+    return s ? s->plant.wr.table_host(tab, rows, gain, call_ctx(s, "brov_plant_wrench_table_host")) : no_solver("brov_plant_wrench_table_host");
 }
-extern "C" int brov_plant_wrench_off(brov_solver* s) { return s ? s->wr.set_off() : no_solver("brov_plant_wrench_off"); }
-extern "C" int brov_plant_wrench_mode(const brov_solver* s) { return s ? s->wr.mode() : BROV_WRENCH_OFF; }
+extern "C" int brov_plant_wrench_off(brov_solver* s) { return s ? s->plant.wr.set_off() : no_solver("brov_plant_wrench_off"); }
+extern "C" int brov_plant_wrench_mode(const brov_solver* s) { return s ? s->plant.wr.mode() : BROV_WRENCH_OFF; }
 extern "C" int brov_plant_wrench_seek(brov_solver* s, int64_t tick) {
-    return s ? s->wr.seek(tick, g_err, "brov_plant_wrench_seek") : no_solver("brov_plant_wrench_seek");
+    return s ? s->plant.wr.seek(tick, call_ctx(s, "brov_plant_wrench_seek")) : no_solver("brov_plant_wrench_seek");
 }
-extern "C" int64_t brov_plant_wrench_tick(const brov_solver* s) { return s ? (int64_t)s->wr.tick : 0; }
+extern "C" int64_t brov_plant_wrench_tick(const brov_solver* s) { return s ? (int64_t)s->plant.wr.tick : 0; }
 extern "C" int brov_plant_wrench_eval_host(brov_solver* s, int64_t tick, double* w) {
-    if (!s) return no_solver("brov_plant_wrench_eval_host");
-    return s->wr.eval_host(tick, w, s->last_stream, [s] { return wrench_wait(s); }, s->mem, g_err, "brov_plant_wrench_eval_host");
+    return s ? s->plant.wr.eval_host(tick, w, s->last_stream, call_ctx(s, "brov_plant_wrench_eval_host")) : no_solver("brov_plant_wrench_eval_host");
 }
 // ---- thruster stage of the plant (plant_wrench.hip): thin forwards to its host side, thruster_source.hpp ----------------------------------
 extern "C" void brov_thruster_default_matrix(double K[36]) { if (K) ThrusterSource::default_matrix(K); }
 extern "C" int brov_thruster_set_host(brov_solver* s, const double* K, const double* lo, const double* hi, const double* gain, const double* bias,
                                       const int64_t* onset) {
     if (!s) return no_solver("brov_thruster_set_host");
-    return s->th.set_host(K, lo, hi, gain, bias, onset, [s] { return wrench_wait(s); }, s->mem, g_err, "brov_thruster_set_host");
+    return s->plant.th.set_host(K, lo, hi, gain, bias, onset, call_ctx(s, "brov_thruster_set_host"));
 }
-extern "C" int brov_thruster_off(brov_solver* s) { return s ? s->th.set_off() : no_solver("brov_thruster_off"); }
-extern "C" int brov_thruster_enabled(const brov_solver* s) { return s && s->th.on ? 1 : 0; }
+extern "C" int brov_thruster_off(brov_solver* s) { return s ? s->plant.th.set_off() : no_solver("brov_thruster_off"); }
+extern "C" int brov_thruster_enabled(const brov_solver* s) { return s && s->plant.th.on ? 1 : 0; }
 extern "C" int brov_thruster_eval_host(brov_solver* s, int64_t tick, const double* commanded, double* applied, double* wrench) {
     if (!s) return no_solver("brov_thruster_eval_host");
-    return s->th.eval_host(tick, commanded, applied, wrench, s->last_stream, [s] { return wrench_wait(s); }, s->mem, g_err, "brov_thruster_eval_host");
+    return s->plant.th.eval_host(tick, commanded, applied, wrench, s->last_stream, call_ctx(s, "brov_thruster_eval_host"));
 }
 extern "C" int brov_thruster_last_host(brov_solver* s, double* applied) {
-    if (!s) return no_solver("brov_thruster_last_host");
-    return s->th.last_host(applied, [s] { return wrench_wait(s); }, s->mem, g_err, "brov_thruster_last_host");
+    return s ? s->plant.th.last_host(applied, call_ctx(s, "brov_thruster_last_host")) : no_solver("brov_thruster_last_host");
 }
 extern "C" int brov_thruster_get_stats_host(brov_solver* s, int32_t* clip_ticks, double* lost_sq, int64_t* steps) {
     if (!s) return no_solver("brov_thruster_get_stats_host");
-    return s->th.get_stats_host(clip_ticks, lost_sq, steps, [s] { return wrench_wait(s); }, s->mem, g_err);
+    return s->plant.th.get_stats_host(clip_ticks, lost_sq, steps, call_ctx(s, "brov_thruster_get_stats_host"));
 }
 extern "C" int brov_thruster_reset_stats(brov_solver* s) {
-    if (!s) return no_solver("brov_thruster_reset_stats");
-    return s->th.reset_stats([s] { return wrench_wait(s); }, s->mem, g_err);
+    return s ? s->plant.th.reset_stats(call_ctx(s, "brov_thruster_reset_stats")) : no_solver("brov_thruster_reset_stats");
 }
 extern "C" int brov_thruster_last_seconds(brov_solver* s, double* seconds) {
     if (!s) return no_solver("brov_thruster_last_seconds");
     HIPCHK(hipSetDevice(s->device));
-    return s->th.last_seconds(seconds, g_err, "brov_thruster_last_seconds");
+    return s->plant.th.last_seconds(seconds, call_ctx(s, "brov_thruster_last_seconds"));
 }
-// ---- sensor stage between plant and controller (sensor_kernel.hip): thin forwards to its host side, sensor_source.hpp -------------------------
-// the device, and the host wait for everything on it: a refresh may have been enqueued on any stream a plant step was given
-static int sensor_wait(brov_solver* s) {
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(hipDeviceSynchronize());
-    s->tick.copies_pending = false;
-    return BROV_OK;
-}
+// ---- sensor stage between plant and controller (sensor_kernel.hip): thin forwards to its host side, sensor_source.hpp, with sensor_wait ---------
+static CallCtx sensor_ctx(brov_solver* s, const char* who) { return call_ctx(s, who, sensor_wait); }
 extern "C" int brov_sensor_set_host(brov_solver* s, uint64_t seed, const double* sigma, const double* bias, const double* quant, const int32_t* period,
                                     const double* dropout) {
     if (!s) return no_solver("brov_sensor_set_host");
-    return s->sn.set_host(seed, sigma, bias, quant, period, dropout, s->x0, s->wr.tick, s->last_stream, [s] { return sensor_wait(s); }, s->mem, g_err,
-                          "brov_sensor_set_host");
+    return s->plant.sn.set_host(seed, sigma, bias, quant, period, dropout, s->x0, s->plant.tick(), s->last_stream,
+                                sensor_ctx(s, "brov_sensor_set_host"));
 }
-extern "C" int brov_sensor_off(brov_solver* s) { return s ? s->sn.set_off() : no_solver("brov_sensor_off"); }
-extern "C" int brov_sensor_enabled(const brov_solver* s) { return s && s->sn.on ? 1 : 0; }
+extern "C" int brov_sensor_off(brov_solver* s) { return s ? s->plant.sn.set_off() : no_solver("brov_sensor_off"); }
+extern "C" int brov_sensor_enabled(const brov_solver* s) { return s && s->plant.sn.on ? 1 : 0; }
 extern "C" int brov_sensor_measure(brov_solver* s, void* stream) {
     if (!s) return no_solver("brov_sensor_measure");
-    if (!s->sn.on) { g_err = "brov_sensor_measure: the sensor stage is off (brov_sensor_set_host)"; return BROV_ERR_ARG; }
-    if (int rc = SensorSource::index_ok(s->wr.tick, g_err, "brov_sensor_measure")) return rc;
+    if (!s->plant.sn.on) { g_err = "brov_sensor_measure: the sensor stage is off (brov_sensor_set_host)"; return BROV_ERR_ARG; }
+    if (int rc = s->plant.rewrite_ok(sensor_ctx(s, "brov_sensor_measure"))) return rc;
     HIPCHK(hipSetDevice(s->device));
     if (int rc = order_behind_last(s, (hipStream_t)stream)) return rc;
-    s->sn.measure(s->x0, s->wr.tick, true, (hipStream_t)stream);
+    s->plant.rewritten((hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return BROV_OK;
 }
 extern "C" int brov_sensor_eval_host(brov_solver* s, int64_t index, const double* x, double* y, int32_t* dropped) {
     if (!s) return no_solver("brov_sensor_eval_host");
-    return s->sn.eval_host(index, x, y, dropped, s->last_stream, [s] { return sensor_wait(s); }, s->mem, g_err, "brov_sensor_eval_host");
+    return s->plant.sn.eval_host(index, x, y, dropped, s->last_stream, sensor_ctx(s, "brov_sensor_eval_host"));
 }
 extern "C" int brov_sensor_get_measurement_host(brov_solver* s, double* y) {
-    if (!s) return no_solver("brov_sensor_get_measurement_host");
-    return s->sn.get_measurement_host(y, [s] { return sensor_wait(s); }, s->mem, g_err, "brov_sensor_get_measurement_host");
+    return s ? s->plant.sn.get_measurement_host(y, sensor_ctx(s, "brov_sensor_get_measurement_host")) : no_solver("brov_sensor_get_measurement_host");
 }
 extern "C" int brov_sensor_get_stats_host(brov_solver* s, int32_t* dropped, double* err_sq, int64_t* refreshes) {
     if (!s) return no_solver("brov_sensor_get_stats_host");
-    return s->sn.get_stats_host(dropped, err_sq, refreshes, [s] { return sensor_wait(s); }, s->mem, g_err);
+    return s->plant.sn.get_stats_host(dropped, err_sq, refreshes, sensor_ctx(s, "brov_sensor_get_stats_host"));
 }
 extern "C" int brov_sensor_reset_stats(brov_solver* s) {
-    if (!s) return no_solver("brov_sensor_reset_stats");
-    return s->sn.reset_stats([s] { return sensor_wait(s); }, s->mem, g_err);
+    return s ? s->plant.sn.reset_stats(sensor_ctx(s, "brov_sensor_reset_stats")) : no_solver("brov_sensor_reset_stats");
 }
 extern "C" int brov_sensor_last_seconds(brov_solver* s, double* seconds) {
     if (!s) return no_solver("brov_sensor_last_seconds");
     HIPCHK(hipSetDevice(s->device));
-    return s->sn.last_seconds(seconds, g_err, "brov_sensor_last_seconds");
+    return s->plant.sn.last_seconds(seconds, sensor_ctx(s, "brov_sensor_last_seconds"));
 }
-// one plant step of the tick counter's tick on `st`, with optional DEVICE logs of this tick: the one place that picks the plant kernel.
-// Thruster stage off and mode OFF: the plant kernel as it always was.  Sensor stage on: a regular refresh of the measured state behind the plant
-// kernel, at the counter's new value (the caller has checked the index, SensorSource::steps_ok)
-static void plant_step_on(brov_solver* s, double dt, int substeps, double* xlog, double* ulog, double* wlog, hipStream_t st) {
-    if (s->th.on)
-        s->th.step(s->x0, s->res, s->pplant, plant_rp(s), plant_rp_stride(s), dt, substeps, xlog, ulog, s->wr.gen, s->wr.tick, wlog, st);
-    else if (s->wr.off())
-        launch_plant(s->x0, s->res, s->pplant, plant_rp(s), plant_rp_stride(s), s->B, dt, substeps, xlog, ulog, st);
-    else
-        launch_plant_wrench(s->x0, s->res, s->pplant, plant_rp(s), plant_rp_stride(s), s->B, dt, substeps, xlog, ulog, s->wr.gen, s->wr.tick, wlog, st);
-    s->wr.tick++;
-    if (s->sn.on) s->sn.measure(s->x0, s->wr.tick, false, st);
-}
+// ---- the end of the forwards: from here on the plant is asked as one object ------------------------------------------------------------------
 extern "C" int brov_plant_step(brov_solver* s, double dt, int substeps, void* stream) {
     if (!s || !(dt > 0.0) || substeps < 1) return BROV_ERR_ARG;
-    if (int rc = s->wr.steps_ok(1, g_err, "brov_plant_step")) return rc;
-    if (int rc = s->sn.steps_ok(s->wr.tick, 1, g_err, "brov_plant_step")) return rc;
+    if (int rc = s->plant.steps_ok(1, call_ctx(s, "brov_plant_step"))) return rc;
     HIPCHK(hipSetDevice(s->device));
     if (int rc = order_behind_last(s, (hipStream_t)stream)) return rc;
-    ensure_plant_params(s, (hipStream_t)stream);
-    plant_step_on(s, dt, substeps, nullptr, nullptr, nullptr, (hipStream_t)stream);
+    s->plant.ensure_params((hipStream_t)stream);
+    s->plant.step(dt, substeps, nullptr, nullptr, nullptr, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return BROV_OK;
 }
@@ -975,7 +932,7 @@ static DevParams make_params(const brov_solver* s, const SolvePlan& plan, const 
     for (int j = 0; j < 16; j++) P.W[j] = s->opts.W[j];
     for (int j = 0; j < 12; j++) P.We[j] = s->opts.We[j];
     for (int j = 0; j < 4; j++) { P.lbu[j] = s->opts.lbu[j]; P.ubu[j] = s->opts.ubu[j]; }
-    P.x0 = in->x0 ? in->x0 : (s->sn.on ? s->sn.ymeas : s->x0);   // sensor stage on: the measured state; a tick's own x0 is the caller's measurement
+    P.x0 = in->x0 ? in->x0 : s->plant.controller_state();   // sensor stage on: the measured state; a tick's own x0 is the caller's measurement
     P.yref = in->yref ? in->yref : (s->yref_shared ? shared_window(s) : s->yref);
     P.yref_stride = s->yref_shared ? 0 : (int64_t)(s->N + 1) * 16;
     P.par = in->par ? in->par : s->par;
@@ -1012,8 +969,6 @@ static void launch_lds(brov_solver* s, const DevParams& P, int family, hipStream
 static void time_mark(brov_solver* s, int k, hipStream_t st) {
     if (s->timing) { hipEventRecord(s->ev[k], st); s->ev_valid = s->ev_valid || k == 2; }
 }
-// the plant update a closed loop's launch of many steps does behind every step, with its DEVICE logs
-struct PlantInLaunch { double dt; int substeps; double *xlog, *ulog; };
 // `n` steps of every instance in ONE launch of the family's *_ticks kernel on `st`, the shared window moving on row_stride_doubles per step;
 // the window in force afterwards is the last step's.  brov_last_solve_seconds then reports THIS launch.
 static int launch_ticks(brov_solver* s, int family, int n, int64_t row_stride_doubles, int32_t* status_log, const PlantInLaunch* plant,
@@ -1022,10 +977,7 @@ static int launch_ticks(brov_solver* s, int family, int n, int64_t row_stride_do
     DevParams P = make_params(s, plan_solve(s, 0));
     P.sched = nullptr;                 // a launch of many steps neither reads nor writes the work ordering: every instance follows its own history
     P.ticks = n; P.tick_yref = row_stride_doubles; P.tick_status = status_log;
-    if (plant) {
-        P.plant_pp = s->pplant; P.plant_rp = plant_rp(s); P.plant_rp_stride = plant_rp_stride(s); P.plant_substeps = plant->substeps; P.plant_dt = plant->dt;
-        P.x0_rw = s->x0; P.plant_xlog = plant->xlog; P.plant_ulog = plant->ulog;
-    }
+    if (plant) s->plant.into_ticks(P, *plant);   // (moves the plant's counter on by the n steps)
     time_mark(s, 0, st); time_mark(s, 1, st);
     launch_lds(s, P, family, st); s->prep_path = 0;
     time_mark(s, 2, st);
@@ -1047,11 +999,11 @@ static void declare_logs(LoopLog& L, double* x, double* u, int32_t* st, double* 
 // a whole loop's logs on `st`: allocated, the start state ahead of the states, and the wrench log zeroed where no wrench kernel writes it
 static int begin_logs(LoopLog& L, const brov_solver* s, int ticks, hipStream_t st, const std::string& pre) {
     if (int rc = L.alloc(s->B, ticks, g_err, pre)) return rc;
-    return L.init(s->x0, s->wr.off() ? LOG_W : -1, st, g_err, pre);
+    return L.init(s->x0, brov_plant_wrench_mode(s) == BROV_WRENCH_OFF ? LOG_W : -1, st, g_err, pre);
 }
 // what the closed-loop entry points ask of their arguments alike, reported under the caller's name (an observer and an estimator are optional
 // here; brov_closed_loop_dob asks for its observer itself)
-static int loop_args_ok(const brov_solver* s, const brov_ekf* e, const brov_rls* r, int rls_mode, int ticks, int ncols, double dt, int substeps,
+static int loop_args_ok(brov_solver* s, const brov_ekf* e, const brov_rls* r, int rls_mode, int ticks, int ncols, double dt, int substeps,
                         const char* who) {
     if (!s || (r && !e) || ticks < 1 || !s->traj || (ncols != 12 && ncols != 16) || !(dt > 0.0) || substeps < 1) {
         g_err = std::string(who) + ": bad argument (needs ticks >= 1, ncols 12 or 16, dt > 0, substeps >= 1, an observer with an estimator, and a "
@@ -1060,8 +1012,7 @@ static int loop_args_ok(const brov_solver* s, const brov_ekf* e, const brov_rls*
     }
     if ((e && brov_ekf_batch(e) != s->B) || (r && brov_rls_batch(r) != s->B)) { g_err = std::string(who) + ": batch sizes differ"; return BROV_ERR_ARG; }
     if (r && rls_mode != BROV_RLS_APPLY_DISTURBANCE && rls_mode != BROV_RLS_APPLY_MODEL) { g_err = std::string(who) + ": unknown rls_mode"; return BROV_ERR_ARG; }
-    if (int rc = s->wr.steps_ok(ticks, g_err, who)) return rc;
-    return s->sn.steps_ok(s->wr.tick, ticks, g_err, who);
+    return s->plant.steps_ok(ticks, call_ctx(s, who));
 }
 // the statuses of the step just enqueued on `st` into a DEVICE log row (null: not logged)
 static void gather_status(const brov_solver* s, int* out, hipStream_t st) {
@@ -1071,12 +1022,12 @@ static void gather_status(const brov_solver* s, int* out, hipStream_t st) {
 // One launch for the whole loop where the fused kernels serve the solver and every window is rows of the table in place (round 5,
 // rti_fused_kernel_ticks with the plant update behind every step): every instance runs its own closed loop at its own pace -- no launch
 // boundaries, three launches per tick saved, and a tick on which one instance grinds through the QP loop holds nobody else.
-// (The fused and windowed *_ticks kernels integrate the plant themselves and know neither a wrench nor thrusters nor sensors: with a wrench
-// mode in force, the thruster stage or the sensor stage on the loop takes a launch per step.)
+// (The fused and windowed *_ticks kernels integrate the plant themselves and know none of its stages: unless the plant is plain, the loop
+// takes a launch per step.)
 static bool loop_in_one_launch(const brov_solver* s, int ticks, int line0, int ncols, int* which) {
     *which = ticks_kernel(s);
     return s->k.closed_loop_fused && ncols == 16 && line0 >= 0 && line0 + (ticks - 1) + s->N <= s->traj_rows - 1 && *which != 0 &&
-           s->wr.off() && !s->th.on && !s->sn.on;
+           s->plant.plain();
 }
 // `n` ticks of the plain loop (window -> RTI step -> plant step) from trajectory row `line` on `st`, logged into L
 static int run_loop_ticks(brov_solver* s, int n, int line, int ncols, double dt, int substeps, bool one_launch, int which, const LoopLog& L,
@@ -1086,7 +1037,6 @@ static int run_loop_ticks(brov_solver* s, int n, int line, int ncols, double dt,
         rc = brov_set_yref_from_traj(s, line, 16, st);
         const PlantInLaunch plant{dt, substeps, L.row<double>(LOG_X, 0), L.row<double>(LOG_U, 0)};
         if (rc == BROV_OK) rc = launch_ticks(s, which, n, 16, L.row<int32_t>(LOG_ST, 0), &plant, st);
-        if (rc == BROV_OK) s->wr.tick += n;
     }
     for (int k = 0; k < n && rc == BROV_OK && !one_launch; k++) {
         forget_traj_window(s);
@@ -1094,7 +1044,7 @@ static int run_loop_ticks(brov_solver* s, int n, int line, int ncols, double dt,
         s->yref_shared = true;
         rc = brov_solve_phase(s, st, 0);
         gather_status(s, L.row<int32_t>(LOG_ST, k), st);
-        plant_step_on(s, dt, substeps, L.row<double>(LOG_X, k), L.row<double>(LOG_U, k), L.row<double>(LOG_W, k), st);
+        s->plant.step(dt, substeps, L.row<double>(LOG_X, k), L.row<double>(LOG_U, k), L.row<double>(LOG_W, k), st);
     }
     return rc;
 }
@@ -1113,8 +1063,8 @@ static int run_dob_ticks(brov_solver* s, brov_ekf* e, brov_rls* r, int rls_mode,
         if (rc == BROV_OK) rc = brov_solve_phase(s, st, 0);
         if (rc != BROV_OK) break;
         gather_status(s, L.row<int32_t>(LOG_ST, k), st);
-        ensure_plant_params(s, st);   // (the hand-off below rewrites the controller's stage 0, which a plant without parameters of its own follows)
-        plant_step_on(s, dt, substeps, L.row<double>(LOG_X, k), L.row<double>(LOG_U, k), L.row<double>(LOG_W, k), st);
+        s->plant.ensure_params(st);   // (the hand-off below rewrites the controller's stage 0, which a plant without parameters of its own follows)
+        s->plant.step(dt, substeps, L.row<double>(LOG_X, k), L.row<double>(LOG_U, k), L.row<double>(LOG_W, k), st);
         if (!sub(brov_ekf_update_from_solver(e, s, st), brov_ekf_last_error())) break;
         if (double* est = L.row<double>(LOG_EST, k)) launch_gather_cols(brov_ekf_x_device(e), (int)B, 18, 12, 6, est, st);
         if (!r) sub(brov_ekf_apply_to_solver(e, s, st), brov_ekf_last_error());
@@ -1131,7 +1081,7 @@ extern "C" int brov_closed_loop_ex(brov_solver* s, int ticks, int line0, int nco
     if (int rc = loop_args_ok(s, nullptr, nullptr, 0, ticks, ncols, dt, substeps, "brov_closed_loop")) return rc;
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = s->last_stream;
-    ensure_plant_params(s, st);
+    s->plant.ensure_params(st);
     LoopLog L;
     declare_logs(L, x_log, u_log, st_log, w_log, nullptr, false);
     int rc = begin_logs(L, s, ticks, st, "brov_closed_loop: ");
@@ -1169,7 +1119,7 @@ extern "C" int brov_closed_loop_track(brov_solver* s, brov_ekf* e, brov_rls* r, 
     if (brov_track_batch(t) != s->B) { g_err = "brov_closed_loop_track: batch sizes differ"; return BROV_ERR_ARG; }
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = s->last_stream;
-    if (!e) ensure_plant_params(s, st);
+    if (!e) s->plant.ensure_params(st);
     int which = 0;
     const bool one_launch = !e && loop_in_one_launch(s, ticks, line0, ncols, &which);   // decided for the whole run, as brov_closed_loop_ex does
     const int C = std::min(chunk == 0 ? 64 : chunk, ticks);
@@ -1396,7 +1346,7 @@ static int stage_inputs(brov_solver* s, const TickLayout& L, int set, const doub
         forget_traj_window(s);
         s->yref_shared = true;
     }
-    if (par_stage) { if (par_stage != pp) std::memcpy(pp, par_stage, L.n_p * sizeof(double)); s->pplant_stale = true; }
+    if (par_stage) { if (par_stage != pp) std::memcpy(pp, par_stage, L.n_p * sizeof(double)); s->plant.params_changed(); }
     return BROV_OK;
 }
 // the inputs `passed` with a tick from input set `set` to the device arrays every other entry point works on, on `cs`
@@ -1512,7 +1462,7 @@ extern "C" int brov_tick_host(brov_solver* s, const double* x0, const double* yr
     if (int rc = enqueue_ahead(s, L, t, passed, rti_phase)) return rc;
     if (t.mailbox) ch.mail_seq = ch.mail_seq == 0x7fffffff ? 1 : ch.mail_seq + 1;
     LaunchInputs in = tick_launch_inputs(ch, L, t, passed);   // a local: no path out of this call leaves a later solve reading the pinned buffer
-    if (s->sn.on && (passed & 1) && !in.x0) in.x0 = s->x0;   // sensor stage on: an x0 copied in ahead of the launch is the caller's measurement, as one read in place is
+    in.x0 = s->plant.tick_state(passed & 1, in.x0);   // sensor stage on: an x0 copied in ahead of the launch is the caller's measurement, as one read in place is
     if (brk) tb1 = clk::now();
     if (t.copies_beside) HIPCHK(hipEventRecord(ch.ev_pre, st));   // (ahead of the launch like enqueue_ahead, but on the launch's side of the breakdown)
     const int rc = solve_phase(s, st, rti_phase, &in);
@@ -1638,10 +1588,13 @@ extern "C" const brov_result* brov_results_device(const brov_solver* s) { return
 extern "C" double* brov_x0_device(brov_solver* s) { return s ? s->x0 : nullptr; }
 namespace brov {
 // what the controller knows of the state: the measured state while the sensor stage is on, else the plant's own (for the observer and the estimator)
-const double* solver_measured_state(const brov_solver* s) { return s ? (s->sn.on ? s->sn.ymeas : s->x0) : nullptr; }
+const double* solver_measured_state(const brov_solver* s) { return s ? s->plant.controller_state() : nullptr; }
+void launch_copy_stage0_par(const double* par, double* pp, int B, int N1, hipStream_t st) {   // for SolverPlant::ensure_params
+    hipLaunchKernelGGL(copy_stage0_par_kernel, dim3((B * 16 + 255) / 256), dim3(256), 0, st, par, pp, B, N1);
+}
 }  // namespace brov
 extern "C" double* brov_yref_device(brov_solver* s) { if (!s) return nullptr; s->yref_shared = false; forget_traj_window(s); return s->yref; }
-extern "C" double* brov_params_device(brov_solver* s) { if (!s) return nullptr; s->pplant_stale = true; return s->par; }
+extern "C" double* brov_params_device(brov_solver* s) { if (!s) return nullptr; s->plant.params_changed(); return s->par; }
 extern "C" double* brov_x_device(brov_solver* s) { return s ? s->x : nullptr; }
 extern "C" double* brov_u_device(brov_solver* s) { return s ? s->u : nullptr; }
 
