@@ -105,6 +105,9 @@ struct StagePoint {
 // over a control tick; its body-frame image turns with the vehicle.  NoWorldWrench: the tag of a model without one.
 struct WorldWrench { double fx, fy, fz, tx, ty, tz; };
 struct NoWorldWrench {};
+// A world wrench (possibly zero) AND an ocean current: a WORLD-frame water velocity (vx, vy, vz) in m/s, constant over a control tick (the
+// reference's underwater_current_plugin, bluerov2_environ/worlds/ocean_waves.world).  The third tag of model_f: the plant of plant_current.hip.
+struct WorldWrenchCurrent { WorldWrench ww; double vx, vy, vz; };
 
 // xdot = f(x,u,p), WW = NoWorldWrench: the model of the OCP; also returns the stage point record.
 // WW = WorldWrench: the same model under an additional world-frame wrench, the plant of brov_plant_step with a wrench mode in force
@@ -113,10 +116,14 @@ struct NoWorldWrench {};
 // One body for both: the projection sits under `if constexpr`, so the NoWorldWrench instantiation holds no statement of it and the
 // solver kernels that inline it -- at their register limit, behind the build's scratch gate and ISA checkers -- compile to the code they
 // compiled to when the function had no such parameter (profiles/plant_step_refactor_isa.txt: instruction for instruction).
+// WW = WorldWrenchCurrent: the world wrench as above, and the water moves: the current is projected like the force, c = R^T vc, and the two
+// damping terms of rows 6, 7, 8 are evaluated at the velocity through the water, v - c.  Quasi-static drag only: the state stays the velocity
+// over ground, and no other row sees the current (profiles/current_isa.txt: the other two instantiations unchanged).
 template <class WW>
 __device__ __forceinline__ void model_f(const double (&x)[NX], const Wrench& w, const ModelPar& m, const WW& ww, double (&f)[NX],
                                         StagePoint& sp) {
-    static_assert(std::is_same_v<WW, WorldWrench> || std::is_same_v<WW, NoWorldWrench>, "a world wrench or the tag for none");
+    static_assert(std::is_same_v<WW, WorldWrench> || std::is_same_v<WW, NoWorldWrench> || std::is_same_v<WW, WorldWrenchCurrent>,
+                  "a world wrench, a world wrench with a current, or the tag for none");
     sincos_pio2(x[3], &sp.sph, &sp.cph);
     sincos_pio2(x[4], &sp.sth, &sp.cth);
     sincos_pio2(x[5], &sp.sps, &sp.cps);
@@ -136,6 +143,18 @@ __device__ __forceinline__ void model_f(const double (&x)[NX], const Wrench& w, 
         k4 += (r01 * ww.tx + r11 * ww.ty + r21 * ww.tz);
         dn += (r02 * ww.tx + r12 * ww.ty + r22 * ww.tz);
     }
+    double ur = sp.vu, vr = sp.vv, wr = sp.vw;   // velocity through the water: over ground, unless there is a current
+    if constexpr (std::is_same_v<WW, WorldWrenchCurrent>) {
+        dx += (r00 * ww.ww.fx + r10 * ww.ww.fy + r20 * ww.ww.fz);
+        dy += (r01 * ww.ww.fx + r11 * ww.ww.fy + r21 * ww.ww.fz);
+        dz += (r02 * ww.ww.fx + r12 * ww.ww.fy + r22 * ww.ww.fz);
+        k3 += (r00 * ww.ww.tx + r10 * ww.ww.ty + r20 * ww.ww.tz);
+        k4 += (r01 * ww.ww.tx + r11 * ww.ww.ty + r21 * ww.ww.tz);
+        dn += (r02 * ww.ww.tx + r12 * ww.ww.ty + r22 * ww.ww.tz);
+        ur -= (r00 * ww.vx + r10 * ww.vy + r20 * ww.vz);
+        vr -= (r01 * ww.vx + r11 * ww.vy + r21 * ww.vz);
+        wr -= (r02 * ww.vx + r12 * ww.vy + r22 * ww.vz);
+    }
     f[0] = r00 * sp.vu + r01 * sp.vv + r02 * sp.vw;
     f[1] = r10 * sp.vu + r11 * sp.vv + r12 * sp.vw;
     f[2] = r20 * sp.vu + r21 * sp.vv + r22 * sp.vw;   // (r20 * vu is the product -sth * vu: the unary minus binds first)
@@ -143,9 +162,9 @@ __device__ __forceinline__ void model_f(const double (&x)[NX], const Wrench& w, 
     f[3] = sp.wp + sp.sps * tth * sp.wq + sp.cph * tth * sp.wr;  // sin(psi): reference quirk, bluerov2.py:133
     f[4] = sp.cph * sp.wq + sp.sph * sp.wr;
     f[5] = (sp.sph * sp.wq + sp.cph * sp.wr) * sp.icth;
-    f[6] = (w.k0 - kBouy * sp.sth + dx + m.lx * sp.vu + m.qx * fabs(sp.vu) * sp.vu) * m.imx;
-    f[7] = (w.k1 + kBouy * r21 + dy + m.ly * sp.vv + m.qy * fabs(sp.vv) * sp.vv) * m.imy;
-    f[8] = (w.k2 + kBouy * r22 + dz + m.lz * sp.vw + m.qz * fabs(sp.vw) * sp.vw) * m.imz;
+    f[6] = (w.k0 - kBouy * sp.sth + dx + m.lx * ur + m.qx * fabs(ur) * ur) * m.imx;
+    f[7] = (w.k1 + kBouy * r21 + dy + m.ly * vr + m.qy * fabs(vr) * vr) * m.imy;
+    f[8] = (w.k2 + kBouy * r22 + dz + m.lz * wr + m.qz * fabs(wr) * wr) * m.imz;
     f[9] = (k3 + (kIy - kIz) * sp.wq * sp.wr - kMzg * r21) * (1.0 / kIx);
     f[10] = (k4 + (kIz - kIx) * sp.wp * sp.wr - kMzg * sp.sth) * (1.0 / kIy);
     f[11] = (w.k5 - (kIy - kIx) * sp.wp * sp.wq + dn + m.ln * sp.wr + m.qn * fabs(sp.wr) * sp.wr) * m.imn;
@@ -173,7 +192,7 @@ __device__ __forceinline__ void erk4_step(const double (&x)[NX], const Wrench& w
 }
 
 // x <- the state one control period dt later, in `substeps` ERK4 steps with input and wrenches held.  The plant of plant_kernel
-// (plant_wrench.hip) and fleet_plant_kernel (fleet_kernel.hip).  NOT of plant_wrench_kernel (plant_wrench.hip) and plant_step_wave
+// and plant_thruster_kernel (plant_wrench.hip), plant_current_kernel (plant_current.hip) and fleet_plant_kernel (fleet_kernel.hip).  NOT of plant_wrench_kernel (plant_wrench.hip) and plant_step_wave
 // (qp/fused.hpp), which restate erk4_step's statements for the reasons given there: a change to the step is made here AND in those two.
 template <class WW>
 __device__ __forceinline__ void plant_erk4(double (&x)[NX], const Wrench& w, const ModelPar& m, const WW& ww, double dt, int substeps) {

@@ -806,6 +806,38 @@ extern "C" int brov_thruster_last_seconds(brov_solver* s, double* seconds) {
     HIPCHK(hipSetDevice(s->device));
     return s->plant.th.last_seconds(seconds, call_ctx(s, "brov_thruster_last_seconds"));
 }
+// ---- ocean current on the plant (plant_current.hip): thin forwards to its host side, current_source.hpp ----------------------------------------
+extern "C" int brov_current_constant_host(brov_solver* s, const double* v) {
+    return s ? s->plant.cu.constant_host(v, call_ctx(s, "brov_current_constant_host")) : no_solver("brov_current_constant_host");
+}
+extern "C" int brov_current_table_host(brov_solver* s, const double* tab, int rows, const double* gain) {
+    return s ? s->plant.cu.table_host(tab, rows, gain, call_ctx(s, "brov_current_table_host")) : no_solver("brov_current_table_host");
+}
+extern "C" int brov_current_gauss_markov_host(brov_solver* s, uint64_t seed, const double* mean, const double* mu, const double* amp, const double* lo,
+                                              const double* hi, double step) {
+    if (!s) return no_solver("brov_current_gauss_markov_host");
+    return s->plant.cu.gauss_markov_host(seed, mean, mu, amp, lo, hi, step, call_ctx(s, "brov_current_gauss_markov_host"));
+}
+extern "C" int brov_current_off(brov_solver* s) { return s ? s->plant.cu.set_off() : no_solver("brov_current_off"); }
+extern "C" int brov_current_mode(const brov_solver* s) { return s ? s->plant.cu.mode() : BROV_CURRENT_OFF; }
+extern "C" int brov_current_eval_host(brov_solver* s, int64_t tick, double* v) {
+    return s ? s->plant.cu.eval_host(tick, v, s->last_stream, call_ctx(s, "brov_current_eval_host")) : no_solver("brov_current_eval_host");
+}
+extern "C" int brov_current_get_state_host(brov_solver* s, double* v) {
+    if (!s) return no_solver("brov_current_get_state_host");
+    return s->plant.cu.get_state_host(s->plant.tick(), v, s->last_stream, call_ctx(s, "brov_current_get_state_host"));
+}
+extern "C" int brov_current_set_state_host(brov_solver* s, const double* v) {
+    return s ? s->plant.cu.set_state_host(v, call_ctx(s, "brov_current_set_state_host")) : no_solver("brov_current_set_state_host");
+}
+extern "C" int brov_current_last_host(brov_solver* s, double* v) {
+    return s ? s->plant.cu.last_host(v, call_ctx(s, "brov_current_last_host")) : no_solver("brov_current_last_host");
+}
+extern "C" int brov_current_last_seconds(brov_solver* s, double* seconds) {
+    if (!s) return no_solver("brov_current_last_seconds");
+    HIPCHK(hipSetDevice(s->device));
+    return s->plant.cu.last_seconds(seconds, call_ctx(s, "brov_current_last_seconds"));
+}
 // ---- sensor stage between plant and controller (sensor_kernel.hip): thin forwards to its host side, sensor_source.hpp, with sensor_wait ---------
 static CallCtx sensor_ctx(brov_solver* s, const char* who) { return call_ctx(s, who, sensor_wait); }
 extern "C" int brov_sensor_set_host(brov_solver* s, uint64_t seed, const double* sigma, const double* bias, const double* quant, const int32_t* period,

@@ -166,6 +166,28 @@ void launch_plant_thruster(double* x0, const brov_result* res, const double* ppl
 void launch_thruster_eval(const ThrusterPar& T, const ThrusterDev& D, int B, long long tick, const double* commanded /*[B][6]*/,
                           double* applied /*[B][6]*/, double* wrench /*[B][6]*/, hipStream_t st);
 
+// ocean current on the plant (plant_current.hip; include/bluerov2_nmpc.h, brov_current_*): a world-frame water velocity per instance and tick.
+// CONSTANT / TABLE: a pure function of (this record, instance, tick).  GAUSS_MARKOV: the device state c, which every plant step advances.
+struct CurrentGen {
+    int mode = 0;                    // BROV_CURRENT_*
+    int rows = 0;                    // table mode
+    const double* v = nullptr;       // constant mode: [B][3]
+    const double* tab = nullptr;     // table mode: [rows][3], shared by the batch
+    const double* gain = nullptr;    // table mode: [B] or nullptr
+    double* c = nullptr;             // Gauss-Markov mode: [B][3] the state, what the next step applies
+    const double* mean = nullptr;    // Gauss-Markov mode: [B][3]
+    unsigned long long seed = 0;
+    double mu[3] = {0, 0, 0}, amp[3] = {0, 0, 0}, lo[3] = {-5, -5, -5}, hi[3] = {5, 5, 5};   // per world axis, shared by the batch
+    double step = 0.0;               // seconds per tick
+    double* last = nullptr;          // [B][3] the current the last plant step applied
+};
+// one plant step under the current of `cg` at `tick` (mode not OFF): behind the thruster stage where th_on, under the world wrench of g where
+// its mode is not OFF; statistics and logs as launch_plant_thruster / launch_plant_wrench leave them; Gauss-Markov mode: the state advances
+void launch_plant_current(double* x0, const brov_result* res, const double* pplant, const double* prp, int rp_stride, int B, double dt, int substeps,
+                          double* xlog, double* ulog, bool th_on, const ThrusterPar& T, const ThrusterDev& D, const WrenchGen& g, const CurrentGen& cg,
+                          long long tick, double* wlog /*[B][6] or nullptr*/, hipStream_t st);
+void launch_current_eval(const CurrentGen& cg, int B, long long tick, double* out /*[B][3]*/, hipStream_t st);
+
 // sensor stage between the plant and the controller (sensor_kernel.hip; include/bluerov2_nmpc.h, brov_sensor_*): the measured state the
 // solve, the observer and the estimator read in place of the plant's true state.  A fresh sample is a pure function of (these records,
 // instance, measurement index, channel, true value); the only state is the measured state itself, which a held channel keeps.

@@ -1,9 +1,10 @@
 // solver_plant.hpp -- the simulated plant of a brov_solver as one object: its true parameters, the world wrench it is under (WrenchSource),
-// the thruster stage ahead of it (ThrusterSource), the sensor stage behind it (SensorSource), its step counter, and what the solver's entry
+// the thruster stage ahead of it (ThrusterSource), the water it moves in (CurrentSource), the sensor stage behind it (SensorSource), its step counter, and what the solver's entry
 // points ask of them: which state the controller sees, whether the next n steps may run, whether the loop's own kernels can integrate it, and
 // the one place that picks the plant kernel.  What it shares with the controller stays the solver's: non-owning pointers, given once at
-// create.  The public brov_plant_* / brov_thruster_* / brov_sensor_* forwards stay in nmpc_api.hip.  Host code only, header only.
+// create.  The public brov_plant_* / brov_thruster_* / brov_current_* / brov_sensor_* forwards stay in nmpc_api.hip.  Host code only, header only.
 #pragma once
+#include "current_source.hpp"
 #include "sensor_source.hpp"
 #include "thruster_source.hpp"
 #include "wrench_source.hpp"
@@ -30,19 +31,24 @@ struct SolverPlant {
     bool pplant_stale = true;      // controller parameters changed since the plant's copy of them was taken
     WrenchSource wr;               // world-frame wrench (brov_plant_wrench_*), its buffers allocated on first use; it stores the step counter
     ThrusterSource th;             // thruster stage (brov_thruster_*): limits, faults and propulsion matrix, its buffers allocated on first use
+    CurrentSource cu;              // ocean current (brov_current_*): a world-frame water velocity, its buffers allocated on first use
     SensorSource sn;               // sensor stage (brov_sensor_*): the measured state, its buffers allocated on first use
 
     void init(int B_, int N_, double* x0_, const brov_result* res_, const double* par_, double* const* par_rp_, const bool* dist6_) {
         B = B_; N = N_; x0 = x0_; res = res_; par = par_; par_rp = par_rp_; dist6 = dist6_;
-        wr.B = th.B = sn.B = (size_t)B_;
+        wr.B = th.B = cu.B = sn.B = (size_t)B_;
     }
-    void destroy() { wr.destroy(); th.destroy(); sn.destroy(); }
+    void destroy() { wr.destroy(); th.destroy(); cu.destroy(); sn.destroy(); }
 
     long long tick() const { return wr.tick; }   // plant steps so far (brov_plant_wrench_seek sets it): the wrench's tick, the sensor's index
-    // may the next `n` steps run?  The wrench's generator, then the sensor's index
-    int steps_ok(long long n, const CallCtx& c) const { const int rc = wr.steps_ok(n, c); return rc ? rc : sn.steps_ok(wr.tick, n, c); }
+    // may the next `n` steps run?  The wrench's generator, then the current's draws, then the sensor's index
+    int steps_ok(long long n, const CallCtx& c) const {
+        if (int rc = wr.steps_ok(n, c)) return rc;
+        if (int rc = cu.steps_ok(wr.tick, n, c)) return rc;
+        return sn.steps_ok(wr.tick, n, c);
+    }
     // no stage in force: the *_ticks kernels, which integrate the plant themselves and know none of them, can run the loop in one launch
-    bool plain() const { return wr.off() && !th.on && !sn.on; }
+    bool plain() const { return wr.off() && !th.on && cu.off() && !sn.on; }
 
     // what the controller knows of the state: the measured state while the sensor stage is on, else the true one
     const double* controller_state() const { return sn.on ? sn.ymeas : x0; }
@@ -63,9 +69,13 @@ struct SolverPlant {
     int rp_stride() const { return prp_plant_set ? 2 : (N + 1) * 2; }
 
     // one plant step at the counter's tick on `st`, with optional DEVICE logs of this tick: the one place that picks the plant kernel (thruster
-    // stage off and mode OFF: as it always was).  Sensor stage on: a regular refresh behind it at the counter's new value (the caller has asked steps_ok)
+    // stage off and both modes OFF: as it always was; a current in force: its kernel, which knows the other two).  Sensor stage on: a regular refresh behind it at the counter's new value (the caller has asked steps_ok)
     void step(double dt, int substeps, double* xlog, double* ulog, double* wlog, hipStream_t st) {
-        if (th.on) th.step(x0, res, pplant, rp(), rp_stride(), dt, substeps, xlog, ulog, wr.gen, wr.tick, wlog, st);
+        if (!cu.off()) {
+            if (th.on) (void)th.timer.start(st);   // the thruster stage's timing and step count, as its own step() keeps them
+            cu.step(x0, res, pplant, rp(), rp_stride(), dt, substeps, xlog, ulog, th.on, th.par, th.dev, wr.gen, wr.tick, wlog, st);
+            if (th.on) { (void)th.timer.stop(st); th.steps++; }
+        } else if (th.on) th.step(x0, res, pplant, rp(), rp_stride(), dt, substeps, xlog, ulog, wr.gen, wr.tick, wlog, st);
         else if (wr.off()) launch_plant(x0, res, pplant, rp(), rp_stride(), B, dt, substeps, xlog, ulog, st);
         else launch_plant_wrench(x0, res, pplant, rp(), rp_stride(), B, dt, substeps, xlog, ulog, wr.gen, wr.tick, wlog, st);
         wr.tick++;

@@ -21,6 +21,7 @@ MAX_N = 256      # BROV_MAX_N (streaming pair)
 MAX_N_LDS = 128  # BROV_MAX_N_LDS (LDS-resident kernels)
 PATH_AUTO, PATH_STREAMING, PATH_FUSED, PATH_WINDOWED = 0, 1, 2, 3
 WRENCH_OFF, WRENCH_CONSTANT, WRENCH_PERIODIC, WRENCH_TABLE = 0, 1, 2, 3   # BROV_WRENCH_*
+CURRENT_OFF, CURRENT_CONSTANT, CURRENT_TABLE, CURRENT_GAUSS_MARKOV = 0, 1, 2, 3   # BROV_CURRENT_*
 
 # nominal hydrodynamic parameters the nodes pass every tick (bluerov2_dob.cpp:340-353); p[0:4] = disturbance
 P_NOMINAL = np.array([0, 0, 0, 0, 1.7182, 0, 5.468, 0.4006, -11.7391, -20, -31.8678, -5, -18.18, -21.66, -36.99, -1.55])
@@ -140,6 +141,10 @@ def _protos(L):
         "brov_sensor_measure": [vp, vp], "brov_sensor_eval_host": [vp, C.c_int64, dp, dp, C.POINTER(C.c_int32)],
         "brov_sensor_get_measurement_host": [vp, dp], "brov_sensor_get_stats_host": [vp, C.POINTER(C.c_int32), dp, C.POINTER(C.c_int64)],
         "brov_sensor_reset_stats": [vp], "brov_sensor_last_seconds": [vp, dp],
+        "brov_current_constant_host": [vp, dp], "brov_current_table_host": [vp, dp, C.c_int, dp],
+        "brov_current_gauss_markov_host": [vp, C.c_uint64, dp, dp, dp, dp, dp, C.c_double], "brov_current_off": [vp], "brov_current_mode": [vp],
+        "brov_current_eval_host": [vp, C.c_int64, dp], "brov_current_get_state_host": [vp, dp], "brov_current_set_state_host": [vp, dp],
+        "brov_current_last_host": [vp, dp], "brov_current_last_seconds": [vp, dp],
     })
     _bind(L, {"brov_thruster_default_matrix": [dp]}, None)
 
@@ -232,6 +237,14 @@ def thrust_allocation(u0):
     return np.stack([(-u0[..., 0] + u0[..., 1] + u0[..., 3]) / c, (-u0[..., 0] - u0[..., 1] - u0[..., 3]) / c,
                      (u0[..., 0] + u0[..., 1] - u0[..., 3]) / c, (u0[..., 0] - u0[..., 1] + u0[..., 3]) / c,
                      -u0[..., 2] / c, -u0[..., 2] / c], axis=-1)
+
+
+def current_from_angles(speed, horizontal, vertical):
+    """world-frame current (vx, vy, vz) from speed V and the horizontal and vertical angles h, v in radians, the convention of the
+    reference's underwater_current_plugin: (V cos h cos v, V sin h cos v, V sin v); broadcasts, the components on the last axis"""
+    V, h, v = np.broadcast_arrays(np.asarray(speed, dtype=np.float64), np.asarray(horizontal, dtype=np.float64),
+                                  np.asarray(vertical, dtype=np.float64))
+    return np.stack([V * np.cos(h) * np.cos(v), V * np.sin(h) * np.cos(v), V * np.sin(v)], axis=-1)
 
 
 class _Wrench:
@@ -600,6 +613,75 @@ class BatchSolver(_Handle):
         K = np.empty((6, 6))
         _load().brov_thruster_default_matrix(_dp(K))
         return K
+
+    # ---- ocean current on the plant: a world-frame water velocity, drag on the velocity through the water (brov_current_*) ------------------
+    def set_current(self, constant=None, table=None, gain=None, gauss_markov=None):
+        """the plant steps from now on run in moving water: exactly one of
+            constant=      [3] for all or [B, 3], world-frame (vx, vy, vz) in m/s (current_from_angles() gives it from speed and two angles)
+            table=         [rows, 3], one row per plant tick (plant_wrench_tick()), the last row repeated; gain= [B] scales it per instance
+            gauss_markov=  dict(mean [3] or [B, 3], mu, amp: scalar or [3]; optional seed=0, lo=-5, hi=5: scalar or [3], step=0.05 seconds per
+                           tick): per world axis c <- clamp((c - step * mu * (c - mean)) + amp * (2 U - 1), lo, hi) behind every plant step,
+                           U a counter-based uniform draw of (seed, instance, tick, axis); the state starts at the mean (set_current_state())"""
+        if (constant is not None) + (table is not None) + (gauss_markov is not None) != 1:
+            raise ValueError("set_current takes exactly one of constant=, table=, gauss_markov=")
+        if gain is not None and table is None:
+            raise ValueError("gain= goes with table=")
+
+        def rows(v, shape):
+            return None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), shape))
+        if constant is not None:
+            self._chk(self._L.brov_current_constant_host(self._h, _dp(rows(constant, (self.B, 3)))), "set_current")
+        elif table is not None:
+            tab = np.ascontiguousarray(table, dtype=np.float64)
+            if tab.ndim != 2 or tab.shape[1] != 3 or tab.shape[0] < 1:
+                raise ValueError("current table must be [rows][3]")
+            self._chk(self._L.brov_current_table_host(self._h, _dp(tab), tab.shape[0], _dp(_arr_opt(gain, (self.B,)))), "set_current")
+        else:
+            kw = dict(seed=0, mean=None, mu=None, amp=None, lo=None, hi=None, step=0.05)
+            unknown = set(gauss_markov) - set(kw)
+            if unknown:
+                raise ValueError(f"unknown Gauss-Markov current parameters {sorted(unknown)}")
+            kw.update(gauss_markov)
+            if kw["mean"] is None or kw["mu"] is None or kw["amp"] is None:
+                raise ValueError("gauss_markov= needs mean, mu and amp")
+            self._chk(self._L.brov_current_gauss_markov_host(
+                self._h, int(kw["seed"]) & 0xFFFFFFFFFFFFFFFF, _dp(rows(kw["mean"], (self.B, 3))), _dp(rows(kw["mu"], (3,))), _dp(rows(kw["amp"], (3,))),
+                _dp(rows(kw["lo"], (3,))), _dp(rows(kw["hi"], (3,))), float(kw["step"])), "set_current")
+
+    def current_off(self):
+        """still water: the plant kernels as they always were"""
+        self._chk(self._L.brov_current_off(self._h), "current_off")
+
+    def current_mode(self):
+        return int(self._L.brov_current_mode(self._h))
+
+    def _current_out(self, fn, name, *args):
+        v = np.empty((self.B, 3))
+        self._chk(fn(self._h, *args, _dp(v)), name)
+        return v
+
+    def current(self, tick):
+        """[B, 3]: the constant / table current of every instance at `tick`, evaluated by the device generator (moves nothing)"""
+        return self._current_out(self._L.brov_current_eval_host, "current", int(tick))
+
+    def current_state(self):
+        """[B, 3]: the current the next plant step applies (Gauss-Markov mode: the state)"""
+        return self._current_out(self._L.brov_current_get_state_host, "current_state")
+
+    def set_current_state(self, v):
+        """Gauss-Markov mode: the state, [3] for all or [B, 3]"""
+        v = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (self.B, 3)))
+        self._chk(self._L.brov_current_set_state_host(self._h, _dp(v)), "set_current_state")
+
+    def current_last(self):
+        """[B, 3]: the current the last plant step applied"""
+        return self._current_out(self._L.brov_current_last_host, "current_last")
+
+    def current_last_seconds(self):
+        """duration of the last plant kernel launched under a current (HIP events)"""
+        sec = C.c_double(0.0)
+        self._chk(self._L.brov_current_last_seconds(self._h, C.byref(sec)), "current_last_seconds")
+        return sec.value
 
     # ---- sensor stage between plant and controller: noise, bias, quantisation, slow and dropped fixes (brov_sensor_*) ------------------
     def set_sensors(self, seed=0, sigma=None, bias=None, quant=None, period=None, dropout=None):

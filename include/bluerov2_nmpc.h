@@ -287,6 +287,49 @@ int brov_sensor_get_stats_host(brov_solver* s, int32_t* dropped /*[B]*/, double*
 int brov_sensor_reset_stats(brov_solver* s);
 int brov_sensor_last_seconds(brov_solver* s, double* seconds); /* the measure kernel's last launch, HIP events */
 
+/* ---- ocean current on the plant: moving water, the constant_current block of the reference's simulated world
+ * (bluerov2_environ/worlds/ocean_waves.world, underwater_current_plugin; Gauss-Markov arguments in bluerov2_dobmpc/launch/
+ * start_dobmpc_demo.launch).  A current is a WORLD-frame water velocity vc = (vx, vy, vz) in m/s, held over a plant tick.  It is not a wrench:
+ * at every RK stage it is projected with that stage's attitude, c = R^T vc, and the linear and quadratic damping of the three linear
+ * velocity rows are evaluated at the velocity through the water v - c.  Nothing else changes: the state stays the velocity over ground; the
+ * controller, the sensor stage, the tracker and the logs see what they saw.  Quasi-static drag only (no added-mass term of a changing current).
+ *   BROV_CURRENT_OFF           (default) every launch is the one of a solver without the stage
+ *   BROV_CURRENT_CONSTANT      v[B][3]
+ *   BROV_CURRENT_TABLE         [rows][3] shared by the batch, row min(k, rows - 1) at plant tick k (the counter brov_plant_wrench_tick reads),
+ *                              times gain[b]: one rounded product
+ *   BROV_CURRENT_GAUSS_MARKOV  the plugin's first-order process per WORLD AXIS (not in speed and two angles), with DEVICE state c[B][3].  A plant
+ *                              step at counter tick k integrates under c as it stands and then advances it, for axis i of instance b:
+ *                                  U  = (splitmix64_finalise(seed + (n + 1) * 0x9E3779B97F4A7C15) >> 11) * 2^-53,  n = (b << 24) | (k << 2) | i
+ *                                  xi = 2 U - 1
+ *                                  v  = (c[i] - step * (mu[i] * (c[i] - mean[b][i]))) + amp[i] * xi        every operation rounded on its own
+ *                                  c[i] = v < lo[i] ? lo[i] : (v > hi[i] ? hi[i] : v)
+ *                              (the periodic wrench's counter draw with the tick in place of the half period; channel 3 stays reserved).
+ *                              Entering the mode sets c = mean.  The tick field has 22 bits: a step or loop that would draw at a tick >= 2^22
+ *                              is refused before anything is launched.  brov_plant_wrench_seek moves the noise counter only; the state is
+ *                              set with brov_current_set_state_host.  One lane per instance, no atomics: bit-reproducible.
+ * With a mode in force brov_plant_step and every loop built on it (brov_closed_loop / _ex / _dob / _track) launch plant_current_kernel, behind
+ * the thruster stage and under the wrench mode in force, with their statistics and logs as ever; the one-launch closed loop knows no current,
+ * so the loops take their launch-per-tick branch.  Out of scope and refused while a mode is in force: brov_fleet_step, brov_closed_loop_fleet,
+ * brov_closed_loop_fleet_dob.
+ * Refused with BROV_ERR_ARG and a text in brov_last_error() that starts with the call's name (nothing changes, nothing is waited for): a NULL
+ * handle or array, a non-finite value, lo[i] > hi[i], step < 0, rows < 1, a negative tick. */
+#define BROV_CURRENT_OFF 0
+#define BROV_CURRENT_CONSTANT 1
+#define BROV_CURRENT_TABLE 2
+#define BROV_CURRENT_GAUSS_MARKOV 3
+int brov_current_constant_host(brov_solver* s, const double* v /*[B][3]*/);
+int brov_current_table_host(brov_solver* s, const double* tab /*[rows][3]*/, int rows, const double* gain /*[B] or NULL*/);
+int brov_current_gauss_markov_host(brov_solver* s, uint64_t seed, const double* mean /*[B][3]*/, const double* mu /*[3]*/, const double* amp /*[3]*/,
+                                   const double* lo /*[3]; NULL: -5*/, const double* hi /*[3]; NULL: 5*/, double step /*seconds per tick*/);
+int brov_current_off(brov_solver* s);
+int brov_current_mode(const brov_solver* s);                                   /* BROV_CURRENT_*; OFF for NULL */
+/* the current of every instance at `tick` in CONSTANT / TABLE mode (zeros while OFF); moves nothing; refused in GAUSS_MARKOV mode */
+int brov_current_eval_host(brov_solver* s, int64_t tick, double* v /*[B][3]*/);
+int brov_current_get_state_host(brov_solver* s, double* v /*[B][3]*/);         /* what the next plant step applies */
+int brov_current_set_state_host(brov_solver* s, const double* v /*[B][3]*/);   /* GAUSS_MARKOV only */
+int brov_current_last_host(brov_solver* s, double* v /*[B][3]*/);              /* of the last plant step under a current (zeros before the first) */
+int brov_current_last_seconds(brov_solver* s, double* seconds);                /* plant_current_kernel's last launch, HIP events */
+
 /* iterate (warm start) access; any pointer may be NULL to skip that block */
 int brov_set_iterate_host(brov_solver* s, const double* x, const double* u, const double* pi, const double* lam);
 int brov_get_iterate_host(brov_solver* s, double* x, double* u, double* pi, double* lam);
