@@ -602,9 +602,15 @@ __device__ __forceinline__ FwdIn load_fwd(const Inst& I, int i) {
 // 240 multiply-adds).  Here a 16-row x 16-column stage matrix is spread over the wave as lane (k, q) = (lane >> 2, lane & 3) <->
 // row k, columns 4q..4q+3: four fmas per lane, a two-step DPP quad reduction, and the result vector goes through LDS (where the
 // sweeps store it anyway) to come back as "four elements per lane".  A forward stage is ~60 VALU instructions + two LDS round trips.
+template <bool ALL = false>   // ALL: every lane of the wave is active (the one-wave fused kernels' adjoint sweep): see dpp_f64_all
 __device__ __forceinline__ double quad_sum(double v) {
-    v += dpp_f64<0xB1>(v);   // quad_perm [1,0,3,2]
-    v += dpp_f64<0x4E>(v);   // quad_perm [2,3,0,1]
+    if constexpr (ALL) {
+        v += dpp_f64_all<0xB1>(v);
+        v += dpp_f64_all<0x4E>(v);
+    } else {
+        v += dpp_f64<0xB1>(v);   // quad_perm [1,0,3,2]
+        v += dpp_f64<0x4E>(v);   // quad_perm [2,3,0,1]
+    }
     return v;
 }
 // "Vector in scalar registers" form of the recursions: lane k (of every 16-lane row: the four rows of the wave do the same work)
@@ -656,9 +662,7 @@ __device__ __forceinline__ void fwd_chunk(const Inst& I, d4& xx, lds_f64* first 
         // clocks, a 16-lane one for 1 -- with 17 reads per stage that is the difference between 9.2 k and 7.7 k cycles per sweep.
         double xcur = x_in[rowx ? k : 0];
         lds_f64* outp = out0;   // running store address (stages in order 0 .. N-1)
-        if (I.lane < 16)
-        pipelined<kLdsDist<LDS>, FwdV>(N, [&](int kk) { return load_fwd_v(mrow0 + lmul(kk, mstr), klo0 + kk * kKtStage, brow0 + kk * kBaStage, cvec0 + lmul(kk, cstr)); },
-                                       [&](int i, const FwdV& in) {
+        auto body = [&](int i, const FwdV& in) __attribute__((always_inline)) {
             const double m0 = rowx ? e0 : in.m[0], m1 = rowx ? e1 : in.m[1], m2 = rowx ? e2 : in.m[2];
             // The sweep is a recurrence on one wave: a dependent FP64 DPP operation issues ~13 cycles behind its producer
             // (measured: 65 cycles per stage for the B v chain), an independent one after ~5.  Four chains of three for the 12-term
@@ -671,7 +675,20 @@ __device__ __forceinline__ void fwd_chunk(const Inst& I, d4& xx, lds_f64* first 
             const double xn = xa + xb;
             *outp = rowx ? xn : dot; outp += ostr;
             xcur = xn;
-        });
+        };
+        if constexpr (LDS == 1) {
+            // running operand addresses (pipelined_seq, tiles.hpp): four adds per stage where the indexed form pays two scalar and two
+            // vector multiplies, four adds and the clamp of the index.  Two stages behind the last one, the [A B] rows are b and
+            // gain entries, the gain rows feed-forward terms and state steps, b is gains and kff candidate inputs -- all of them inside this
+            // wave's slice from N = 3 (behind [A B] lie 96 N + 43 doubles, two of its stages are 312; behind the gains 36 N + 43 for 96),
+            // and the host never launches a one-wave kernel below that (fused_two_wave, qp_kernel.hip)
+            const lds_f64 *mp = mrow0, *kp = klo0, *bp = brow0, *cp = cvec0;
+            if (I.lane < 16)
+            pipelined_seq<kLdsDist<LDS>, FwdV>(N, [&]() { const FwdV s = load_fwd_v(mp, kp, bp, cp); mp += mstr; kp += kKtStage; bp += kBaStage; cp += cstr; return s; }, body);
+        } else {
+            if (I.lane < 16)
+            pipelined<kLdsDist<LDS>, FwdV>(N, [&](int kk) { return load_fwd_v(mrow0 + lmul(kk, mstr), klo0 + kk * kKtStage, brow0 + kk * kBaStage, cvec0 + lmul(kk, cstr)); }, body);
+        }
         // the last state step back into the row-replicated form the callers carry between windows
         const lds_f64* xl = I.lds_dxb + N * NX + rg;
         xx = d4{xl[0], xl[4], xl[8], 0.0};
@@ -808,6 +825,26 @@ __device__ __forceinline__ AdjV load_adj_v(const IT& I, int om, int ox, int ou, 
     }
     return s;
 }
+// the same operands through running addresses (the one-wave fused kernels, pipelined_seq): stage il, then every address one stage down
+struct AdjPtr { const lds_f64 *col, *dx, *q, *v, *r; int il; };
+template <class IT = Inst>
+__device__ __forceinline__ AdjV load_adj_v_seq(const IT& I, AdjPtr& A, int ox, int ou) {
+    AdjV s;
+#pragma unroll
+    for (int t = 0; t < 4; t++) s.m[t] = A.col[t * kBaStride];
+    s.dxc = *A.dx;
+    s.qc = *A.q;
+    s.vm = *A.v;
+    s.rm = *A.r;
+    s.wq = 0.0; s.wr = 0.0;
+    if constexpr (IT::kGrid) {
+        s.wq = I.wst[(size_t)(I.i0 + A.il + 1) * 16 + ox];
+        s.wr = I.wst[(size_t)(I.i0 + A.il) * 16 + 12 + ou];
+    }
+    // (behind stage 0: the column runs against the start of the slice; state steps and gradients into the arrays in front of them)
+    A.col = lds_down(A.col, kBaStage, I.lds_ba); A.dx -= NX; A.q -= NX; A.v -= 4; A.r -= 4; A.il = A.il > 0 ? A.il - 1 : 0;
+    return s;
+}
 template <bool COMMIT, int LDS, class IT = Inst>
 __device__ __forceinline__ void adj_chunk(const IT& I, d4& atpi, const double* varr, double* garr, double* pi_out) {
     const int rg = I.rg, cl = I.cl, N = I.N;
@@ -833,7 +870,7 @@ __device__ __forceinline__ void adj_chunk(const IT& I, d4& atpi, const double* v
         const double rd = I.Ts * I.Wuq;
         lds_f64* pp = ppark + lmul(N - 1, pstr);   // running store addresses (stages in order N-1 .. 0)
         lds_f64* gp = gpark + lmul(N - 1, gstr);
-        pipelined<kLdsDist<LDS>, AdjV>(N, [&](int kk) { return load_adj_v(I, om, ox, ou, N - 1 - kk); }, [&](int kk, const AdjV& in) {
+        auto body = [&](int kk, const AdjV& in) __attribute__((always_inline)) {
             const int i = N - 1 - kk;
             const double qd = IT::kGrid ? in.wq : ((I.i0 + i + 1 == I.NT) ? I.Weq : I.Ts * I.Wq);
             const double pic = fma(qd, in.dxc, in.qc + gq);
@@ -845,10 +882,18 @@ __device__ __forceinline__ void adj_chunk(const IT& I, d4& atpi, const double* v
             double acc = m0 * p0;
             acc = fma(m1, p1, acc); acc = fma(m2, p2, acc); acc = fma(m3, p3, acc);
             acc = colx ? acc : 0.0;
-            const double G = quad_sum(acc);
+            const double G = quad_sum<LDS == 1>(acc);
             *gp = fma(IT::kGrid ? in.wr : rd, in.vm, in.rm + G); gp -= gstr;   // (parked lanes: see above)
             gq = G;
-        });
+        };
+        if constexpr (LDS == 1) {
+            // five adds per stage where the indexed form pays two scalar multiplies, seven adds / shifts and the clamp of the index
+            AdjPtr A{I.lds_ba + (N - 1) * kBaStage + om, I.lds_dxb + N * NX + ox, I.lds_q + N * NX + ox, I.lds_vhat + (N - 1) * 4 + ou,
+                     I.lds_r + (N - 1) * 4 + ou, N - 1};
+            pipelined_seq<kLdsDist<LDS>, AdjV>(N, [&]() { return load_adj_v_seq(I, A, ox, ou); }, body);
+        } else {
+            pipelined<kLdsDist<LDS>, AdjV>(N, [&](int kk) { return load_adj_v(I, om, ox, ou, N - 1 - kk); }, body);
+        }
         // hand A'pi of this window's first stage on, row-replicated
         lds_f64* tpark = rowx ? I.lds_tr + c : I.lds_tr + 16;
         *tpark = gq;

@@ -52,6 +52,15 @@ __device__ __forceinline__ double dpp_f64(double v) {
     const int hi = __builtin_amdgcn_update_dpp(__double2hiint(v), __double2hiint(v), CTRL, 0xF, 0xF, false);
     return __hiloint2double(hi, lo);
 }
+// The same permutation where EVERY lane of the wave is active and the control reads a lane for every lane (quad_perm, mirrors, row
+// broadcast): no lane ever keeps its old value, so there is none to provide -- dpp_f64 hands `v` in as the old value and pays a
+// v_mov_b32 per half in front of each DPP move for it.  A lone wave pays a four-cycle issue slot per instruction, moves included.
+template <int CTRL>
+__device__ __forceinline__ double dpp_f64_all(double v) {
+    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, false);
+    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, false);
+    return __hiloint2double(hi, lo);
+}
 template <class Op>
 __device__ __forceinline__ double wave_reduce(double v, Op op) {
     v = op(v, dpp_f64<0xB1>(v));   // quad_perm [1,0,3,2]
@@ -296,6 +305,35 @@ __device__ __forceinline__ void pipelined_mid(int count, Load load, Body body) {
             if (k + d < count) body(k + d, slot[d], issue); else issue();
         }
     }
+}
+
+// The one-wave fused kernels (a lone wave pays a four-cycle issue slot for every instruction, address arithmetic included): the same
+// pipeline (the first form) with the stages' operands requested strictly IN ORDER -- `load()` takes no index: it reads through running addresses and moves
+// them on by the stage strides (one add per address instead of index x stride + base per request, and no clamped index in front of it).
+// The D requests behind the last stage are issued like the others (their slots are never consumed), so `load()` has to keep its addresses
+// inside the wave's LDS slice there: sweeps that run upwards are followed by other arrays of the slice, sweeps that run downwards clamp the
+// addresses that would leave it (lds_down).  A guard around those requests -- a scalar branch in the stage -- was built first and is slower than
+// the index arithmetic it replaces: behind the join the compiler no longer knows how many requests are in flight and every counted
+// s_waitcnt of the stage becomes lgkmcnt(0) (profiles/early_exit_fused_issue_slots.txt).
+template <int D, class In, class Load, class Body>
+__device__ __forceinline__ void pipelined_seq(int count, Load load, Body body) {
+    constexpr int S = D + 1;
+    In slot[S];
+#pragma unroll
+    for (int d = 0; d < D; d++) slot[d] = load();
+    for (int k = 0; k < count; k += S) {
+#pragma unroll
+        for (int d = 0; d < S; d++) {
+            slot[(d + D) % S] = load();
+            if (k + d < count) body(k + d, slot[d]);
+        }
+    }
+}
+// p - stride elements, but never below `floor` (the start of the wave's LDS slice): the running address of a sweep that visits the stages
+// downwards, for the array the slice begins with -- what it reads behind stage 0 is stage 0 again, or the slice's first elements
+__device__ __forceinline__ const lds_f64* lds_down(const lds_f64* p, int stride, const lds_f64* floor) {
+    const int a = (int)(__UINTPTR_TYPE__)p - 8 * stride, f = (int)(__UINTPTR_TYPE__)floor;
+    return (const lds_f64*)(__UINTPTR_TYPE__)(unsigned)(a > f ? a : f);
 }
 
 }  // namespace brov

@@ -294,6 +294,9 @@ bool split_resident_horizon(int N) { return N >= 4 && 3 * ((N + 3) >> 2) < N && 
 
 static size_t fused_lds_bytes(int N) { return ((size_t)N * (kBaStage + NX + kKtStage + 4 + 4 + 4) + 2 * (size_t)(N + 1) * NX + 2 + 17) * sizeof(double); }
 static bool fused_two_wave(size_t lds, int force) {   // force: DevKnobs::fused_waves (development knob)
+    // (the one-wave kernel's forward sweep requests two stages ahead without a guard, fwd_chunk: its slice has to hold three stages.  Shorter
+    // horizons are the two-wave kernel's whatever the knob says)
+    if (lds < fused_lds_bytes(3)) return true;
     return force ? force == 2 : 7 * lds <= 160 * 1024;   // N <= 11 (seven slices per CU)
 }
 // what the LDS-resident kernel of this horizon asks of a CU: info = {dynamic LDS bytes per block, blocks the occupancy query grants
