@@ -893,7 +893,7 @@ extern "C" int brov_ekf_update_from_solver(brov_ekf* e, brov_solver* s, void* st
     hipStream_t st = (hipStream_t)stream;
     if (brov_order_stream(s, stream) != BROV_OK) { g_ekf_err = "brov_ekf_update_from_solver: could not order behind the solver's last stream"; return BROV_ERR_HIP; }
     hipLaunchKernelGGL(ekf_inputs_from_solver_kernel, dim3((e->B + 255) / 256), dim3(256), 0, st, e->B, e->c.dt, 1.0 / kRotor,
-                       solver_measured_state(s), brov_results_device(s), e->vprev, e->thrust, e->y12, e->acc);
+                       solver_measured_state(s), solver_observer_results(s), e->vprev, e->thrust, e->y12, e->acc);
     HIPCHK(hipGetLastError());
     return launch_update(e, e->thrust, e->y12, e->acc, st);
 }

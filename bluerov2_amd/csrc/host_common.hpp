@@ -145,6 +145,9 @@ SolverView solver_view(const brov_solver* s);
 // [B][12] what the controller knows of the state: the measured state while the solver's sensor stage is on (brov_sensor_*), else the plant's
 // own state, brov_x0_device(); read by the observer's and the estimator's *_from_solver / *_from_ekf updates
 const double* solver_measured_state(const brov_solver* s);
+// [B] the records whose thrusts brov_ekf_update_from_solver feeds the observer: the commanded ones, brov_results_device(), unless the solver's
+// delay stage is on with observer_applied set (brov_delay_set_host): then what the last plant step was given
+const brov_result* solver_observer_results(const brov_solver* s);
 
 // ---- a device buffer that lives as long as a scope: freed on every way out, unless release() hands it on ---------------------------------
 template <typename T>

@@ -877,6 +877,37 @@ extern "C" int brov_sensor_last_seconds(brov_solver* s, double* seconds) {
     HIPCHK(hipSetDevice(s->device));
     return s->plant.sn.last_seconds(seconds, sensor_ctx(s, "brov_sensor_last_seconds"));
 }
+// ---- delay stage between the controller's commands and the plant (delay_kernel.hip): thin forwards to its host side, delay_source.hpp, with
+// sensor_wait: the predictor runs on whatever stream a solve was given -----------------------------------------------------------------------
+extern "C" int brov_delay_set_host(brov_solver* s, const int32_t* delay, int32_t comp, double dt_pred, int32_t observer_applied) {
+    if (!s) return no_solver("brov_delay_set_host");
+    return s->plant.dl.set_host(delay, comp, dt_pred, s->opts.Ts, observer_applied, sensor_ctx(s, "brov_delay_set_host"));
+}
+extern "C" int brov_delay_off(brov_solver* s) { return s ? s->plant.dl.set_off() : no_solver("brov_delay_off"); }
+extern "C" int brov_delay_enabled(const brov_solver* s) { return s && s->plant.dl.on ? 1 : 0; }
+extern "C" int brov_delay_comp(const brov_solver* s) { return s ? s->plant.dl.ahead() : 0; }
+extern "C" int brov_delay_depth(const brov_solver* s) { return s ? s->plant.dl.D : 0; }
+extern "C" int brov_delay_reset(brov_solver* s) { return s ? s->plant.dl.reset(sensor_ctx(s, "brov_delay_reset")) : no_solver("brov_delay_reset"); }
+extern "C" int brov_delay_last_host(brov_solver* s, double* u0_applied, double* thrust_applied) {
+    if (!s) return no_solver("brov_delay_last_host");
+    return s->plant.dl.last_host(u0_applied, thrust_applied, sensor_ctx(s, "brov_delay_last_host"));
+}
+extern "C" int brov_delay_queue_host(brov_solver* s, double* u0) {
+    return s ? s->plant.dl.queue_host(u0, sensor_ctx(s, "brov_delay_queue_host")) : no_solver("brov_delay_queue_host");
+}
+extern "C" int brov_delay_predict_host(brov_solver* s, const double* y, double* xhat) {
+    if (!s) return no_solver("brov_delay_predict_host");
+    return s->plant.dl.predict_host(y, xhat, s->plant.controller_state(), s->plant.predict_model(), s->last_stream,
+                                    sensor_ctx(s, "brov_delay_predict_host"));
+}
+extern "C" int brov_delay_predicted_host(brov_solver* s, double* xhat) {
+    return s ? s->plant.dl.predicted_host(xhat, sensor_ctx(s, "brov_delay_predicted_host")) : no_solver("brov_delay_predicted_host");
+}
+extern "C" int brov_delay_last_seconds(brov_solver* s, double* shift_s, double* predict_s) {
+    if (!s) return no_solver("brov_delay_last_seconds");
+    HIPCHK(hipSetDevice(s->device));
+    return s->plant.dl.last_seconds(shift_s, predict_s, sensor_ctx(s, "brov_delay_last_seconds"));
+}
 // ---- the end of the forwards: from here on the plant is asked as one object ------------------------------------------------------------------
 extern "C" int brov_plant_step(brov_solver* s, double dt, int substeps, void* stream) {
     if (!s || !(dt > 0.0) || substeps < 1) return BROV_ERR_ARG;
@@ -964,7 +995,8 @@ static DevParams make_params(const brov_solver* s, const SolvePlan& plan, const 
     for (int j = 0; j < 16; j++) P.W[j] = s->opts.W[j];
     for (int j = 0; j < 12; j++) P.We[j] = s->opts.We[j];
     for (int j = 0; j < 4; j++) { P.lbu[j] = s->opts.lbu[j]; P.ubu[j] = s->opts.ubu[j]; }
-    P.x0 = in->x0 ? in->x0 : s->plant.controller_state();   // sensor stage on: the measured state; a tick's own x0 is the caller's measurement
+    // sensor stage on: the measured state; a tick's own x0 is the caller's measurement; delay stage with comp > 0: the predictor's (predicted_inputs)
+    P.x0 = in->x0 ? in->x0 : s->plant.controller_state();
     P.yref = in->yref ? in->yref : (s->yref_shared ? shared_window(s) : s->yref);
     P.yref_stride = s->yref_shared ? 0 : (int64_t)(s->N + 1) * 16;
     P.par = in->par ? in->par : s->par;
@@ -988,6 +1020,15 @@ static DevParams make_params(const brov_solver* s, const SolvePlan& plan, const 
     P.dbg = s->dbg;
     return P;
 }
+// Delay stage with comp > 0: the solve starts comp plant steps ahead.  The predictor runs on `st` ahead of the launch (the caller has ordered
+// `st`) and the launch reads its x0 from the predictor's buffer: make_params takes it as it takes a tick's own x0.  Parameters passed with a
+// tick are the predictor's too.  Returns what make_params is given: `in`, or `with`, a copy of it with the predicted state as x0.
+static const LaunchInputs* predicted_inputs(brov_solver* s, const LaunchInputs* in, LaunchInputs& with, hipStream_t st) {
+    if (!s->plant.dl.predicts() || (in && in->x0)) return in;
+    if (in) with = *in;
+    with.x0 = s->plant.predict(in ? in->par : nullptr, st);
+    return &with;
+}
 // the launch(es) of an LDS-resident family and what the solver remembers of them
 static void launch_lds(brov_solver* s, const DevParams& P, int family, hipStream_t st) {
     if (family == FAM_FUSED) launch_fused(P, st, s->k);
@@ -1006,8 +1047,9 @@ static void time_mark(brov_solver* s, int k, hipStream_t st) {
 static int launch_ticks(brov_solver* s, int family, int n, int64_t row_stride_doubles, int32_t* status_log, const PlantInLaunch* plant,
                         hipStream_t st) {
     if (int rc = order_behind_last(s, st)) return rc;
-    DevParams P = make_params(s, plan_solve(s, 0));
-    P.sched = nullptr;                 // a launch of many steps neither reads nor writes the work ordering: every instance follows its own history
+    LaunchInputs pred;   // (delay stage: every step of the launch starts from the one prediction; a plant in the launch is plain, so there is none)
+    DevParams P = make_params(s, plan_solve(s, 0), predicted_inputs(s, nullptr, pred, st));
+    P.sched = nullptr;                // a launch of many steps neither reads nor writes the work ordering: every instance follows its own history
     P.ticks = n; P.tick_yref = row_stride_doubles; P.tick_status = status_log;
     if (plant) s->plant.into_ticks(P, *plant);   // (moves the plant's counter on by the n steps)
     time_mark(s, 0, st); time_mark(s, 1, st);
@@ -1070,9 +1112,10 @@ static int run_loop_ticks(brov_solver* s, int n, int line, int ncols, double dt,
         const PlantInLaunch plant{dt, substeps, L.row<double>(LOG_X, 0), L.row<double>(LOG_U, 0)};
         if (rc == BROV_OK) rc = launch_ticks(s, which, n, 16, L.row<int32_t>(LOG_ST, 0), &plant, st);
     }
+    const int ahead = s->plant.dl.ahead();   // delay stage: the OCP starts comp ticks ahead, and so does its window (the stage is never plain: no one_launch)
     for (int k = 0; k < n && rc == BROV_OK && !one_launch; k++) {
         forget_traj_window(s);
-        launch_window(s->traj, s->traj_rows, nullptr, line + k, 1, s->N, ncols, s->yref_sh, st);
+        launch_window(s->traj, s->traj_rows, nullptr, line + k + ahead, 1, s->N, ncols, s->yref_sh, st);
         s->yref_shared = true;
         rc = brov_solve_phase(s, st, 0);
         gather_status(s, L.row<int32_t>(LOG_ST, k), st);
@@ -1090,8 +1133,9 @@ static int run_dob_ticks(brov_solver* s, brov_ekf* e, brov_rls* r, int rls_mode,
         if (code != BROV_OK) { g_err = std::string(who) + ": " + text; rc = code; }
         return code == BROV_OK;
     };
+    const int ahead = s->plant.dl.ahead();   // delay stage: the OCP starts comp ticks ahead, and so does its window
     for (int k = 0; k < n && rc == BROV_OK; k++) {
-        rc = brov_set_yref_from_traj(s, line + k, ncols, st);
+        rc = brov_set_yref_from_traj(s, line + k + ahead, ncols, st);
         if (rc == BROV_OK) rc = brov_solve_phase(s, st, 0);
         if (rc != BROV_OK) break;
         gather_status(s, L.row<int32_t>(LOG_ST, k), st);
@@ -1223,6 +1267,8 @@ static int solve_phase(brov_solver* s, hipStream_t st, int rti_phase, const Laun
         return BROV_ERR_ARG;
     }
     if (rti_phase == 1) s->prep_path = plan.prep_path;
+    LaunchInputs pred;   // (delay stage: the step and the feedback start from the predicted state; a preparation from the controller's, as ever)
+    if (rti_phase != 1) in = predicted_inputs(s, in, pred, st);
     const DevParams P = make_params(s, plan, in);
     time_mark(s, 0, st);
     if (plan.family != FAM_STREAMING) {
@@ -1475,6 +1521,11 @@ static int wait_records(brov_solver* s, const TickLayout& L, const TickPlan& t, 
 extern "C" int brov_tick_host(brov_solver* s, const double* x0, const double* yref_shared, const double* par_stage, int rti_phase,
                               brov_result* res) {
     if (!s || rti_phase < 0 || rti_phase > 2) return BROV_ERR_ARG;
+    if (x0 && s->plant.dl.predicts()) {
+        g_err = "brov_tick_host: the delay stage predicts the solve's initial state from the controller's own (comp > 0, brov_delay_set_host): "
+                "a tick that brings its own x0 is refused";
+        return BROV_ERR_ARG;
+    }
     using clk = std::chrono::steady_clock;
     const bool brk = s->k.tick_breakdown != 0;
     clk::time_point tb0, tb1, tb2, tb3, tb4;
@@ -1621,6 +1672,11 @@ extern "C" double* brov_x0_device(brov_solver* s) { return s ? s->x0 : nullptr; 
 namespace brov {
 // what the controller knows of the state: the measured state while the sensor stage is on, else the plant's own (for the observer and the estimator)
 const double* solver_measured_state(const brov_solver* s) { return s ? s->plant.controller_state() : nullptr; }
+// the records whose thrusts the observer is fed: the commanded ones, unless the delay stage is on with observer_applied set
+const brov_result* solver_observer_results(const brov_solver* s) {
+    if (!s) return nullptr;
+    return s->plant.dl.on && s->plant.dl.observer_applied ? s->plant.dl.applied : s->res;
+}
 void launch_copy_stage0_par(const double* par, double* pp, int B, int N1, hipStream_t st) {   // for SolverPlant::ensure_params
     hipLaunchKernelGGL(copy_stage0_par_kernel, dim3((B * 16 + 255) / 256), dim3(256), 0, st, par, pp, B, N1);
 }

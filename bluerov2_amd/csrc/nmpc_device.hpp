@@ -209,4 +209,15 @@ void launch_sensor_measure(const SensorPar& P, const SensorDev& D, int B, long l
 // the stage alone: fresh samples y [B][12] of the states x [B][12] at index m and the dropout verdicts [B]; moves nothing
 void launch_sensor_eval(const SensorPar& P, const SensorDev& D, int B, long long m, const double* x, double* y, int32_t* dropped, hipStream_t st);
 
+// delay stage of the plant (delay_kernel.hip; include/bluerov2_nmpc.h, brov_delay_*): a ring [B][D][10] of the last D commanded records
+// (u0[4] | thrust[6]), indexed by the stage's own step count n.
+// step n of the stage: applied[b] = res[b] with u0 and thrust of step n - delay[b] (zeros before the first), res[b]'s own into slot n mod D;
+// ulog: [B][4] the COMMANDED u0, or nullptr.  The host has checked 0 <= delay[b] <= D - 1
+void launch_delay_shift(const brov_result* res, brov_result* applied, const int32_t* delay, double* ring, int D, long long n, int B, double* ulog,
+                        hipStream_t st);
+// xhat [B][12] = y [B][12] carried through the u0 of steps n - comp ... n - 1 (comp <= D - 1) by one ERK4 step over dt_pred each, with the
+// parameters of instance b at par + b * par_stride and its roll / pitch moments at prp + b * rp_stride (or nullptr)
+void launch_delay_predict(const double* y, const double* par, int par_stride, const double* prp, int rp_stride, const double* ring, int D, long long n,
+                          int comp, double dt_pred, double* xhat, int B, hipStream_t st);
+
 }  // namespace brov

@@ -1,10 +1,11 @@
 // solver_plant.hpp -- the simulated plant of a brov_solver as one object: its true parameters, the world wrench it is under (WrenchSource),
-// the thruster stage ahead of it (ThrusterSource), the water it moves in (CurrentSource), the sensor stage behind it (SensorSource), its step counter, and what the solver's entry
+// the delay between the controller's commands and it (DelaySource), the thruster stage ahead of it (ThrusterSource), the water it moves in (CurrentSource), the sensor stage behind it (SensorSource), its step counter, and what the solver's entry
 // points ask of them: which state the controller sees, whether the next n steps may run, whether the loop's own kernels can integrate it, and
 // the one place that picks the plant kernel.  What it shares with the controller stays the solver's: non-owning pointers, given once at
-// create.  The public brov_plant_* / brov_thruster_* / brov_current_* / brov_sensor_* forwards stay in nmpc_api.hip.  Host code only, header only.
+// create.  The public brov_plant_* / brov_delay_* / brov_thruster_* / brov_current_* / brov_sensor_* forwards stay in nmpc_api.hip.  Host code only, header only.
 #pragma once
 #include "current_source.hpp"
+#include "delay_source.hpp"
 #include "sensor_source.hpp"
 #include "thruster_source.hpp"
 #include "wrench_source.hpp"
@@ -33,12 +34,13 @@ struct SolverPlant {
     ThrusterSource th;             // thruster stage (brov_thruster_*): limits, faults and propulsion matrix, its buffers allocated on first use
     CurrentSource cu;              // ocean current (brov_current_*): a world-frame water velocity, its buffers allocated on first use
     SensorSource sn;               // sensor stage (brov_sensor_*): the measured state, its buffers allocated on first use
+    DelaySource dl;                // delay stage (brov_delay_*): the queue of commanded records and the predictor, its buffers allocated on first use
 
     void init(int B_, int N_, double* x0_, const brov_result* res_, const double* par_, double* const* par_rp_, const bool* dist6_) {
         B = B_; N = N_; x0 = x0_; res = res_; par = par_; par_rp = par_rp_; dist6 = dist6_;
-        wr.B = th.B = cu.B = sn.B = (size_t)B_;
+        wr.B = th.B = cu.B = sn.B = dl.B = (size_t)B_;
     }
-    void destroy() { wr.destroy(); th.destroy(); cu.destroy(); sn.destroy(); }
+    void destroy() { wr.destroy(); th.destroy(); cu.destroy(); sn.destroy(); dl.destroy(); }
 
     long long tick() const { return wr.tick; }   // plant steps so far (brov_plant_wrench_seek sets it): the wrench's tick, the sensor's index
     // may the next `n` steps run?  The wrench's generator, then the current's draws, then the sensor's index
@@ -48,10 +50,16 @@ struct SolverPlant {
         return sn.steps_ok(wr.tick, n, c);
     }
     // no stage in force: the *_ticks kernels, which integrate the plant themselves and know none of them, can run the loop in one launch
-    bool plain() const { return wr.off() && !th.on && cu.off() && !sn.on; }
+    bool plain() const { return wr.off() && !th.on && cu.off() && !sn.on && !dl.on; }
 
     // what the controller knows of the state: the measured state while the sensor stage is on, else the true one
     const double* controller_state() const { return sn.on ? sn.ymeas : x0; }
+    // the model the delay stage's predictor integrates: the controller's own stage-0 parameters and, 6-disturbance variant, its moments
+    PredictModel predict_model(const double* par_in = nullptr) const {
+        return {par_in ? par_in : par, (N + 1) * 16, *dist6 ? *par_rp : nullptr, (N + 1) * 2};
+    }
+    // the delay stage predicts (the owner has asked dl.predicts()): x^ from what the controller knows of the state, on `st`; where the solve reads it
+    const double* predict(const double* par_in, hipStream_t st) { return dl.predict(controller_state(), predict_model(par_in), st); }
     // ... of a brov_tick_host that brought its own x0, the caller's measurement: where its kernel reads it in place, else x0, where it was copied
     const double* tick_state(bool x0_passed, const double* in_place) const { return sn.on && x0_passed && !in_place ? x0 : in_place; }
     // a caller rewrites the true state: the measured state follows it with a forced refresh at the counter's index, which must be one
@@ -71,13 +79,16 @@ struct SolverPlant {
     // one plant step at the counter's tick on `st`, with optional DEVICE logs of this tick: the one place that picks the plant kernel (thruster
     // stage off and both modes OFF: as it always was; a current in force: its kernel, which knows the other two).  Sensor stage on: a regular refresh behind it at the counter's new value (the caller has asked steps_ok)
     void step(double dt, int substeps, double* xlog, double* ulog, double* wlog, hipStream_t st) {
+        // delay stage on: its step ahead of the plant kernel, which then reads the applied records; the `u` log is the stage's, the commanded input
+        const brov_result* rec = res;
+        if (dl.on) { dl.shift(res, ulog, st); rec = dl.applied; ulog = nullptr; }
         if (!cu.off()) {
             if (th.on) (void)th.timer.start(st);   // the thruster stage's timing and step count, as its own step() keeps them
-            cu.step(x0, res, pplant, rp(), rp_stride(), dt, substeps, xlog, ulog, th.on, th.par, th.dev, wr.gen, wr.tick, wlog, st);
+            cu.step(x0, rec, pplant, rp(), rp_stride(), dt, substeps, xlog, ulog, th.on, th.par, th.dev, wr.gen, wr.tick, wlog, st);
             if (th.on) { (void)th.timer.stop(st); th.steps++; }
-        } else if (th.on) th.step(x0, res, pplant, rp(), rp_stride(), dt, substeps, xlog, ulog, wr.gen, wr.tick, wlog, st);
-        else if (wr.off()) launch_plant(x0, res, pplant, rp(), rp_stride(), B, dt, substeps, xlog, ulog, st);
-        else launch_plant_wrench(x0, res, pplant, rp(), rp_stride(), B, dt, substeps, xlog, ulog, wr.gen, wr.tick, wlog, st);
+        } else if (th.on) th.step(x0, rec, pplant, rp(), rp_stride(), dt, substeps, xlog, ulog, wr.gen, wr.tick, wlog, st);
+        else if (wr.off()) launch_plant(x0, rec, pplant, rp(), rp_stride(), B, dt, substeps, xlog, ulog, st);
+        else launch_plant_wrench(x0, rec, pplant, rp(), rp_stride(), B, dt, substeps, xlog, ulog, wr.gen, wr.tick, wlog, st);
         wr.tick++;
         if (sn.on) sn.measure(x0, wr.tick, false, st);
     }

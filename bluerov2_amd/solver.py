@@ -145,6 +145,10 @@ def _protos(L):
         "brov_current_gauss_markov_host": [vp, C.c_uint64, dp, dp, dp, dp, dp, C.c_double], "brov_current_off": [vp], "brov_current_mode": [vp],
         "brov_current_eval_host": [vp, C.c_int64, dp], "brov_current_get_state_host": [vp, dp], "brov_current_set_state_host": [vp, dp],
         "brov_current_last_host": [vp, dp], "brov_current_last_seconds": [vp, dp],
+        "brov_delay_set_host": [vp, C.POINTER(C.c_int32), C.c_int32, C.c_double, C.c_int32], "brov_delay_off": [vp], "brov_delay_enabled": [vp],
+        "brov_delay_comp": [vp], "brov_delay_depth": [vp], "brov_delay_reset": [vp], "brov_delay_last_host": [vp, dp, dp],
+        "brov_delay_queue_host": [vp, dp], "brov_delay_predict_host": [vp, dp, dp], "brov_delay_predicted_host": [vp, dp],
+        "brov_delay_last_seconds": [vp, dp, dp],
     })
     _bind(L, {"brov_thruster_default_matrix": [dp]}, None)
 
@@ -613,6 +617,73 @@ class BatchSolver(_Handle):
         K = np.empty((6, 6))
         _load().brov_thruster_default_matrix(_dp(K))
         return K
+
+    # ---- delay stage between the commands and the plant, and the predictor ahead of the solve (brov_delay_*) ---------------------------------
+    def set_delay(self, delay=None, comp=0, dt_pred=None, observer_applied=False):
+        """the plant steps from now on are given the record commanded delay[b] steps earlier (zeros before the first); the queue and the stage's
+        step count start afresh.
+            delay             scalar or [B] in 0 ... 8 (None: 0), plant steps between a command and its arrival
+            comp              0 ... 8, one number for the batch: every solve starts from the controller's state carried through the last `comp`
+                              commanded inputs by its own model, and the closed loops start their windows comp rows ahead
+            dt_pred           the predictor's step (None: the options' Ts)
+            observer_applied  BatchEkf.update_from_solver reads the applied thrusts in place of the commanded ones"""
+        d = None if delay is None else np.ascontiguousarray(np.broadcast_to(np.asarray(delay, dtype=np.int32), (self.B,)))
+        self._chk(self._L.brov_delay_set_host(self._h, None if d is None else d.ctypes.data_as(C.POINTER(C.c_int32)), int(comp),
+                                              0.0 if dt_pred is None else float(dt_pred), int(bool(observer_applied))), "set_delay")
+
+    def delay_off(self):
+        """every launch as it was without the stage; the queue stays readable"""
+        self._chk(self._L.brov_delay_off(self._h), "delay_off")
+
+    def delay_enabled(self):
+        return bool(self._L.brov_delay_enabled(self._h))
+
+    def delay_comp(self):
+        return int(self._L.brov_delay_comp(self._h))
+
+    def delay_depth(self):
+        """D: slots of the queue, max(max delay, comp) + 1"""
+        return int(self._L.brov_delay_depth(self._h))
+
+    def delay_reset(self):
+        """zeroes the queue and the stage's step count"""
+        self._chk(self._L.brov_delay_reset(self._h), "delay_reset")
+
+    def delay_last(self):
+        """(u0 [B, 4], thrust [B, 6]): what the last plant step behind the stage was given"""
+        u, t = np.empty((self.B, NU)), np.empty((self.B, 6))
+        self._chk(self._L.brov_delay_last_host(self._h, _dp(u), _dp(t)), "delay_last")
+        return u, t
+
+    def delay_queue(self):
+        """[B, D, 4]: the u0 of the last D commanded records, oldest first (zeros for steps before the first)"""
+        q = np.empty((self.B, self.delay_depth(), NU))
+        self._chk(self._L.brov_delay_queue_host(self._h, _dp(q)), "delay_queue")
+        return q
+
+    def delay_predict(self, y=None):
+        """[B, 12]: the predictor alone from y [B, 12] (None: what the controller knows of the state); moves nothing"""
+        out = np.empty((self.B, NX))
+        self._chk(self._L.brov_delay_predict_host(self._h, _dp(_arr_opt(y, (self.B, NX))), _dp(out)), "delay_predict")
+        return out
+
+    def delay_predicted(self):
+        """[B, 12]: the state the last solve started from (comp > 0)"""
+        out = np.empty((self.B, NX))
+        self._chk(self._L.brov_delay_predicted_host(self._h, _dp(out)), "delay_predicted")
+        return out
+
+    def delay_last_seconds(self):
+        """(shift, predict): durations of the last launch of the stage's two kernels (HIP events); None where none was launched yet"""
+        out = []
+        for k in range(2):
+            sec = C.c_double(0.0)
+            args = (C.byref(sec), None) if k == 0 else (None, C.byref(sec))
+            rc = self._L.brov_delay_last_seconds(self._h, *args)
+            if rc != -1:                       # (BROV_ERR_ARG: that kernel has not been launched yet)
+                self._chk(rc, "delay_last_seconds")
+            out.append(sec.value if rc == 0 else None)
+        return tuple(out)
 
     # ---- ocean current on the plant: a world-frame water velocity, drag on the velocity through the water (brov_current_*) ------------------
     def set_current(self, constant=None, table=None, gain=None, gauss_markov=None):

@@ -248,6 +248,47 @@ int brov_thruster_get_stats_host(brov_solver* s, int32_t* clip_ticks /*[B][6]*/,
 int brov_thruster_reset_stats(brov_solver* s);
 int brov_thruster_last_seconds(brov_solver* s, double* seconds);                  /* the plant kernel's last launch behind the stage, HIP events */
 
+/* ---- delay stage between the controller's commands and the plant, and a controller that predicts through it.  Without it the command solved
+ * at tick k acts on the vehicle at tick k.  No real loop is like that: the input is applied after the solve, the transport to the thruster
+ * manager and the ESCs.  With the stage on, every plant step (brov_plant_step and every tick of brov_closed_loop / _ex / _dob / _track) is
+ * given the record commanded delay[b] plant steps earlier.  Per instance the stage keeps a ring of the last D commanded records, u0[4] and
+ * thrust[6], D = max(max_b delay[b], comp) + 1, zero-filled when the stage is set or reset and indexed by the stage's OWN step count n (plant
+ * steps since it was set or reset; brov_plant_wrench_seek does not disturb it).  Step n, c(n) = the solver's record (brov_results_device):
+ *     a(n) = delay[b] == 0 ? c(n) : (n < delay[b] ? 0 : c(n - delay[b]))          read first, then c(n) is written into slot n mod D
+ * and the plant kernel in force -- whatever the wrench mode, the thruster stage, the current and the sensor stage make it -- reads u0 and thrust
+ * of a(n) in place of c(n).  Copies only: bit-reproducible.  The u log and the tracker keep the COMMANDED input; the one-launch closed loop
+ * and the *_ticks kernels know no delay, so the loops take their launch-per-tick branch; a brov_fleet refuses such a solver.
+ * comp > 0 (one number for the batch: the controller is designed for one nominal delay, delay[b] sweeps the real one against it): ahead of every
+ * solve that takes its initial state from the solver (brov_solve, brov_solve_phase phases 0 and 2, brov_solve_ticks, every closed loop) the
+ * predictor computes, per instance,
+ *     x^ = Phi(... Phi(Phi(y, c(n - comp)), c(n - comp + 1)) ..., c(n - 1))
+ * Phi = one explicit RK4 step over dt_pred (one substep) of the controller's own model: its stage-0 parameters as they stand (a handed-off
+ * disturbance estimate included) and, 6-disturbance variant, its roll / pitch moments; y = what the controller knows of the state (the measured
+ * state while the sensor stage is on); the inputs are the u0 of the queue, oldest first, zeros for steps before the first.  The solve starts
+ * from x^.  brov_tick_host with its own x0 is refused while comp > 0.  The closed loops start tick k's shared reference window at row
+ * line0 + k + comp -- the OCP starts comp ticks ahead --; the tracker still scores the true state after tick k against row line0 + k + 1.
+ * A caller who sets windows by hand (brov_set_yref_*, brov_set_yref_from_traj) shifts them by comp rows itself.
+ * observer_applied != 0: brov_ekf_update_from_solver reads the thrusts of the APPLIED records a(n) in place of the commanded ones.
+ * Stage off (the default, and after brov_delay_off): every launch is the one of a solver without the stage.
+ * Out of scope: thruster lag and other dynamics acting on the delayed value, sensor latency, per-instance comp, a non-zero initial fill of
+ * the queue, the fleet, the one-launch *_ticks kernels.
+ * Refused with BROV_ERR_ARG and a text in brov_last_error() that starts with the call's name (nothing changes, nothing is waited for): a NULL
+ * handle, a delay or comp outside [0, BROV_DELAY_MAX], a non-finite dt_pred. */
+#define BROV_DELAY_MAX 8
+int brov_delay_set_host(brov_solver* s, const int32_t* delay /*[B]; NULL: all 0*/, int32_t comp, double dt_pred /*<= 0: the options' Ts*/,
+                        int32_t observer_applied);                    /* switches the stage on, zeroes the ring and the step count */
+int brov_delay_off(brov_solver* s);
+int brov_delay_enabled(const brov_solver* s);                         /* 0 for NULL */
+int brov_delay_comp(const brov_solver* s);                            /* plant steps the solves predict ahead; 0 while off and for NULL */
+int brov_delay_depth(const brov_solver* s);                           /* D of the last brov_delay_set_host (1 before any); 0 for NULL */
+int brov_delay_reset(brov_solver* s);                                 /* zeroes the ring and the step count */
+int brov_delay_last_host(brov_solver* s, double* u0_applied /*[B][4]*/, double* thrust_applied /*[B][6]*/);   /* a(n) of the last plant step; one may be NULL */
+int brov_delay_queue_host(brov_solver* s, double* u0 /*[B][D][4]*/);  /* the u0 of the last D commanded records, oldest first */
+/* the predictor alone, from y [B][12] (NULL: the controller's state) into xhat [B][12]; moves nothing */
+int brov_delay_predict_host(brov_solver* s, const double* y, double* xhat);
+int brov_delay_predicted_host(brov_solver* s, double* xhat /*[B][12]*/);   /* what the last solve started from (refused before a solve has predicted) */
+int brov_delay_last_seconds(brov_solver* s, double* shift_s, double* predict_s);   /* last launch of either kernel, HIP events; one may be NULL */
+
 /* ---- sensor stage between the plant and the controller: noisy, biased, quantised, slow and dropped measurements.  Without it the solve, the
  * observer (brov_ekf_update_from_solver) and the estimator (brov_rls_update_from_ekf) read the plant's true state.  While the stage is on they
  * read the MEASURED state ymeas [B][12] instead; the plant, the logs and the tracker keep the true state x0.  The fresh sample of channel c of
