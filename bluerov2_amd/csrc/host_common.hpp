@@ -146,7 +146,8 @@ SolverView solver_view(const brov_solver* s);
 // own state, brov_x0_device(); read by the observer's and the estimator's *_from_solver / *_from_ekf updates
 const double* solver_measured_state(const brov_solver* s);
 // [B] the records whose thrusts brov_ekf_update_from_solver feeds the observer: the commanded ones, brov_results_device(), unless the solver's
-// delay stage is on with observer_applied set (brov_delay_set_host): then what the last plant step was given
+// delay stage is on with observer_applied set (brov_delay_set_host): then what the last plant step was given; the rotor stage with its
+// observer_applied set (brov_rotor_set_host) comes first: its applied records, the lagged ones
 const brov_result* solver_observer_results(const brov_solver* s);
 
 // ---- a device buffer that lives as long as a scope: freed on every way out, unless release() hands it on ---------------------------------

@@ -908,9 +908,46 @@ extern "C" int brov_delay_last_seconds(brov_solver* s, double* shift_s, double* 
     HIPCHK(hipSetDevice(s->device));
     return s->plant.dl.last_seconds(shift_s, predict_s, sensor_ctx(s, "brov_delay_last_seconds"));
 }
+// ---- rotor stage between the delay and the thruster stage (rotor_kernel.hip): thin forwards to its host side, rotor_source.hpp, with
+// sensor_wait: a shift runs on whatever stream a plant step was given ----------------------------------------------------------------------------
+extern "C" int brov_rotor_coeffs(double tau, double h, double* alpha, double* beta) { return RotorSource::coeffs(tau, h, alpha, beta); }
+extern "C" int brov_rotor_set_host(brov_solver* s, const double* tau, double h, const double* cmd_lo, const double* cmd_hi, int32_t observer_applied) {
+    if (!s) return no_solver("brov_rotor_set_host");
+    return s->plant.ro.set_host(tau, h, s->opts.Ts, cmd_lo, cmd_hi, observer_applied, sensor_ctx(s, "brov_rotor_set_host"));
+}
+extern "C" int brov_rotor_off(brov_solver* s) { return s ? s->plant.ro.set_off() : no_solver("brov_rotor_off"); }
+extern "C" int brov_rotor_enabled(const brov_solver* s) { return s && s->plant.ro.on ? 1 : 0; }
+extern "C" int brov_rotor_reset(brov_solver* s) { return s ? s->plant.ro.reset(sensor_ctx(s, "brov_rotor_reset")) : no_solver("brov_rotor_reset"); }
+extern "C" int brov_rotor_set_state_host(brov_solver* s, const double* r) {
+    return s ? s->plant.ro.set_state_host(r, sensor_ctx(s, "brov_rotor_set_state_host")) : no_solver("brov_rotor_set_state_host");
+}
+extern "C" int brov_rotor_get_state_host(brov_solver* s, double* r) {
+    return s ? s->plant.ro.get_state_host(r, sensor_ctx(s, "brov_rotor_get_state_host")) : no_solver("brov_rotor_get_state_host");
+}
+extern "C" int brov_rotor_last_host(brov_solver* s, double* u0_applied, double* thrust_applied) {
+    if (!s) return no_solver("brov_rotor_last_host");
+    return s->plant.ro.last_host(u0_applied, thrust_applied, sensor_ctx(s, "brov_rotor_last_host"));
+}
+extern "C" int brov_rotor_get_stats_host(brov_solver* s, double* lag_sq, int64_t* steps) {
+    return s ? s->plant.ro.get_stats_host(lag_sq, steps, sensor_ctx(s, "brov_rotor_get_stats_host")) : no_solver("brov_rotor_get_stats_host");
+}
+extern "C" int brov_rotor_get_coeffs_host(brov_solver* s, double* alpha, double* beta, double* h) {
+    if (!s) return no_solver("brov_rotor_get_coeffs_host");
+    return s->plant.ro.get_coeffs_host(alpha, beta, h, sensor_ctx(s, "brov_rotor_get_coeffs_host"));
+}
+extern "C" int brov_rotor_eval_host(brov_solver* s, const double* commanded, const double* state, double* applied, double* state_out) {
+    if (!s) return no_solver("brov_rotor_eval_host");
+    return s->plant.ro.eval_host(commanded, state, applied, state_out, s->last_stream, sensor_ctx(s, "brov_rotor_eval_host"));
+}
+extern "C" int brov_rotor_last_seconds(brov_solver* s, double* seconds) {
+    if (!s) return no_solver("brov_rotor_last_seconds");
+    HIPCHK(hipSetDevice(s->device));
+    return s->plant.ro.last_seconds(seconds, sensor_ctx(s, "brov_rotor_last_seconds"));
+}
 // ---- the end of the forwards: from here on the plant is asked as one object ------------------------------------------------------------------
 extern "C" int brov_plant_step(brov_solver* s, double dt, int substeps, void* stream) {
     if (!s || !(dt > 0.0) || substeps < 1) return BROV_ERR_ARG;
+    if (int rc = s->plant.dt_ok(dt, call_ctx(s, "brov_plant_step"))) return rc;
     if (int rc = s->plant.steps_ok(1, call_ctx(s, "brov_plant_step"))) return rc;
     HIPCHK(hipSetDevice(s->device));
     if (int rc = order_behind_last(s, (hipStream_t)stream)) return rc;
@@ -1086,6 +1123,7 @@ static int loop_args_ok(brov_solver* s, const brov_ekf* e, const brov_rls* r, in
     }
     if ((e && brov_ekf_batch(e) != s->B) || (r && brov_rls_batch(r) != s->B)) { g_err = std::string(who) + ": batch sizes differ"; return BROV_ERR_ARG; }
     if (r && rls_mode != BROV_RLS_APPLY_DISTURBANCE && rls_mode != BROV_RLS_APPLY_MODEL) { g_err = std::string(who) + ": unknown rls_mode"; return BROV_ERR_ARG; }
+    if (int rc = s->plant.dt_ok(dt, call_ctx(s, who))) return rc;
     return s->plant.steps_ok(ticks, call_ctx(s, who));
 }
 // the statuses of the step just enqueued on `st` into a DEVICE log row (null: not logged)
@@ -1672,9 +1710,11 @@ extern "C" double* brov_x0_device(brov_solver* s) { return s ? s->x0 : nullptr; 
 namespace brov {
 // what the controller knows of the state: the measured state while the sensor stage is on, else the plant's own (for the observer and the estimator)
 const double* solver_measured_state(const brov_solver* s) { return s ? s->plant.controller_state() : nullptr; }
-// the records whose thrusts the observer is fed: the commanded ones, unless the delay stage is on with observer_applied set
+// the records whose thrusts the observer is fed: the commanded ones, unless the rotor stage (the last to rewrite the record) or the delay
+// stage is on with observer_applied set
 const brov_result* solver_observer_results(const brov_solver* s) {
     if (!s) return nullptr;
+    if (s->plant.ro.on && s->plant.ro.observer_applied) return s->plant.ro.applied;
     return s->plant.dl.on && s->plant.dl.observer_applied ? s->plant.dl.applied : s->res;
 }
 void launch_copy_stage0_par(const double* par, double* pp, int B, int N1, hipStream_t st) {   // for SolverPlant::ensure_params

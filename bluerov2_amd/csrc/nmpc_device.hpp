@@ -220,4 +220,17 @@ void launch_delay_shift(const brov_result* res, brov_result* applied, const int3
 void launch_delay_predict(const double* y, const double* par, int par_stride, const double* prp, int rp_stride, const double* ring, int D, long long n,
                           int comp, double dt_pred, double* xhat, int B, hipStream_t st);
 
+// rotor stage of the plant (rotor_kernel.hip; include/bluerov2_nmpc.h, brov_rotor_*): first-order dynamics of the six thrusters between the
+// commands and the plant, behind the delay stage and ahead of the thruster stage.  The only state is r [B][6].
+struct RotorPar {                 // shared by the batch and wave-uniform: passed by value in the kernel arguments
+    double lo[6], hi[6];          // limits of the commands ahead of the dynamics
+};
+// one step of the stage: applied[b] = rec[b] with thrust = the mean thrusts m over the step and u0 = the allocation's left inverse of m; the
+// state advances, last [B][6] = m, lag_sq [B] += |c - m|^2; alpha, beta: [B][6] from the host; ulog: [B][4] the COMMANDED u0, or nullptr
+void launch_rotor_shift(const brov_result* rec, brov_result* applied, const RotorPar& P, const double* alpha, const double* beta, double* state,
+                        double* last, double* lag_sq, int B, double* ulog, hipStream_t st);
+// the stage alone: applied [B][6] and state_out [B][6] for the commands commanded [B][6] from the state state [B][6]; moves nothing
+void launch_rotor_eval(const RotorPar& P, const double* alpha, const double* beta, const double* commanded, const double* state, double* applied,
+                       double* state_out, int B, hipStream_t st);
+
 }  // namespace brov

@@ -149,6 +149,10 @@ def _protos(L):
         "brov_delay_comp": [vp], "brov_delay_depth": [vp], "brov_delay_reset": [vp], "brov_delay_last_host": [vp, dp, dp],
         "brov_delay_queue_host": [vp, dp], "brov_delay_predict_host": [vp, dp, dp], "brov_delay_predicted_host": [vp, dp],
         "brov_delay_last_seconds": [vp, dp, dp],
+        "brov_rotor_coeffs": [C.c_double, C.c_double, dp, dp], "brov_rotor_set_host": [vp, dp, C.c_double, dp, dp, C.c_int32],
+        "brov_rotor_off": [vp], "brov_rotor_enabled": [vp], "brov_rotor_reset": [vp], "brov_rotor_set_state_host": [vp, dp],
+        "brov_rotor_get_state_host": [vp, dp], "brov_rotor_last_host": [vp, dp, dp], "brov_rotor_get_stats_host": [vp, dp, C.POINTER(C.c_int64)],
+        "brov_rotor_get_coeffs_host": [vp, dp, dp, dp], "brov_rotor_eval_host": [vp, dp, dp, dp, dp], "brov_rotor_last_seconds": [vp, dp],
     })
     _bind(L, {"brov_thruster_default_matrix": [dp]}, None)
 
@@ -241,6 +245,16 @@ def thrust_allocation(u0):
     return np.stack([(-u0[..., 0] + u0[..., 1] + u0[..., 3]) / c, (-u0[..., 0] - u0[..., 1] - u0[..., 3]) / c,
                      (u0[..., 0] + u0[..., 1] - u0[..., 3]) / c, (u0[..., 0] - u0[..., 1] + u0[..., 3]) / c,
                      -u0[..., 2] / c, -u0[..., 2] / c], axis=-1)
+
+
+def rotor_coeffs(tau, h):
+    """(alpha, beta) = (exp(-h / tau), (1 - alpha) / (h / tau)) of the rotor stage for the time constant tau and the step h, as the library's
+    host code computes and uploads them (brov_rotor_coeffs; tau == 0: (0, 0)); needs no GPU"""
+    al, be = C.c_double(0.0), C.c_double(0.0)
+    rc = _load().brov_rotor_coeffs(float(tau), float(h), C.byref(al), C.byref(be))
+    if rc != 0:
+        raise ValueError(f"rotor_coeffs({tau}, {h}): tau must be finite and >= 0, h finite and > 0")
+    return al.value, be.value
 
 
 def current_from_angles(speed, horizontal, vertical):
@@ -684,6 +698,73 @@ class BatchSolver(_Handle):
                 self._chk(rc, "delay_last_seconds")
             out.append(sec.value if rc == 0 else None)
         return tuple(out)
+
+    # ---- rotor stage between the commands and the plant: first-order dynamics of the thrusters (brov_rotor_*) ---------------------------------
+    def set_rotors(self, tau=None, h=None, cmd_lo=None, cmd_hi=None, observer_applied=False):
+        """the plant steps from now on are given the mean thrust of rotors that follow their commands with r' = (c - r) / tau; the rotor state,
+        the statistics and the stage's step count start afresh.  The chain is delay -> rotors -> thruster stage -> model.
+            tau               scalar, [6] or [B, 6] seconds, >= 0 (None: 0.2, the reference's; 0: that rotor follows at once)
+            h                 the plant step the coefficients are computed for (None: the options' Ts); plant steps of another dt are refused
+            cmd_lo, cmd_hi    scalar or [6], limits of the commands ahead of the dynamics (None: none)
+            observer_applied  BatchEkf.update_from_solver reads the applied (lagged) thrusts in place of the commanded ones"""
+        t = None if tau is None else np.ascontiguousarray(np.broadcast_to(np.asarray(tau, dtype=np.float64), (self.B, 6)))
+        lo = None if cmd_lo is None else np.ascontiguousarray(np.broadcast_to(np.asarray(cmd_lo, dtype=np.float64), (6,)))
+        hi = None if cmd_hi is None else np.ascontiguousarray(np.broadcast_to(np.asarray(cmd_hi, dtype=np.float64), (6,)))
+        self._chk(self._L.brov_rotor_set_host(self._h, _dp(t), 0.0 if h is None else float(h), _dp(lo), _dp(hi), int(bool(observer_applied))),
+                  "set_rotors")
+
+    def rotor_off(self):
+        """every launch as it was without the stage; state and statistics stay readable"""
+        self._chk(self._L.brov_rotor_off(self._h), "rotor_off")
+
+    def rotor_enabled(self):
+        return bool(self._L.brov_rotor_enabled(self._h))
+
+    def rotor_reset(self):
+        """zeroes the rotor state, the statistics and the stage's step count"""
+        self._chk(self._L.brov_rotor_reset(self._h), "rotor_reset")
+
+    def rotor_state(self):
+        """[B, 6]: the thrust every rotor gives at the end of the last step"""
+        r = np.empty((self.B, 6))
+        self._chk(self._L.brov_rotor_get_state_host(self._h, _dp(r)), "rotor_state")
+        return r
+
+    def set_rotor_state(self, r):
+        self._chk(self._L.brov_rotor_set_state_host(self._h, _dp(_arr(r, (self.B, 6)))), "set_rotor_state")
+
+    def rotor_last(self):
+        """(u0 [B, 4], thrust [B, 6]): what the last plant step behind the stage was given"""
+        u, t = np.empty((self.B, NU)), np.empty((self.B, 6))
+        self._chk(self._L.brov_rotor_last_host(self._h, _dp(u), _dp(t)), "rotor_last")
+        return u, t
+
+    def rotor_stats(self):
+        """dict(lag_sq [B]: running sum of |command - applied|^2; steps: steps of the stage since it was set or reset)"""
+        lag, steps = np.empty(self.B), C.c_int64(0)
+        self._chk(self._L.brov_rotor_get_stats_host(self._h, _dp(lag), C.byref(steps)), "rotor_stats")
+        return dict(lag_sq=lag, steps=int(steps.value))
+
+    def rotor_coeffs(self):
+        """dict(alpha [B, 6], beta [B, 6], h): the coefficients the stage uploaded and the step they hold for"""
+        al, be, h = np.empty((self.B, 6)), np.empty((self.B, 6)), C.c_double(0.0)
+        self._chk(self._L.brov_rotor_get_coeffs_host(self._h, _dp(al), _dp(be), C.byref(h)), "rotor_coeffs")
+        return dict(alpha=al, beta=be, h=h.value)
+
+    def rotor_eval(self, commanded, state=None):
+        """(applied [B, 6], new state [B, 6]) of the stage alone for `commanded` [B, 6] from `state` [B, 6] (None: the stage's own); moves nothing"""
+        c = _arr(commanded, (self.B, 6))
+        a, r = np.empty((self.B, 6)), np.empty((self.B, 6))
+        self._chk(self._L.brov_rotor_eval_host(self._h, _dp(c), _dp(_arr_opt(state, (self.B, 6))), _dp(a), _dp(r)), "rotor_eval")
+        return a, r
+
+    def rotor_last_seconds(self):
+        """duration of the last shift launch (HIP events); None where none was launched yet"""
+        sec = C.c_double(0.0)
+        rc = self._L.brov_rotor_last_seconds(self._h, C.byref(sec))
+        if rc != -1:                           # (BROV_ERR_ARG: no plant step behind the stage yet)
+            self._chk(rc, "rotor_last_seconds")
+        return sec.value if rc == 0 else None
 
     # ---- ocean current on the plant: a world-frame water velocity, drag on the velocity through the water (brov_current_*) ------------------
     def set_current(self, constant=None, table=None, gain=None, gauss_markov=None):

@@ -289,6 +289,48 @@ int brov_delay_predict_host(brov_solver* s, const double* y, double* xhat);
 int brov_delay_predicted_host(brov_solver* s, double* xhat /*[B][12]*/);   /* what the last solve started from (refused before a solve has predicted) */
 int brov_delay_last_seconds(brov_solver* s, double* shift_s, double* predict_s);   /* last launch of either kernel, HIP events; one may be NULL */
 
+/* ---- rotor stage between the commands and the plant: first-order dynamics of the six thrusters, r' = (c - r) / tau (the reference's vehicle:
+ * FirstOrder, timeConstant 0.2 s, i.e. four ticks of 50 ms, with a command clamp ahead of the dynamics).  Without it a command becomes force in
+ * the tick it is issued.  The chain is delay -> rotor -> thruster stage (clip / fault / K) -> model: with the stage on, every plant step
+ * (brov_plant_step and every tick of brov_closed_loop / _ex / _dob / _track) runs rotor_shift_kernel behind the delay stage's shift and ahead
+ * of the plant kernel in force, which reads the applied record in place of the one it was given.  Per instance b and thruster i, with the
+ * state r (zero when the stage is set or reset), the command t = thrust[i] of the record received and the coefficients alpha, beta:
+ *     c  = t < cmd_lo[i] ? cmd_lo[i] : (t > cmd_hi[i] ? cmd_hi[i] : t)
+ *     if c is not finite: c = r                          (a non-finite command moves nothing and is never stored)
+ *     d  = r + (-c);   m = c + beta * d;   r' = c + alpha * d            every operation rounded on its own
+ * alpha = exp(-h / tau), beta = (1 - alpha) / (h / tau) from the exact solution over the step h, computed on the HOST (brov_rotor_coeffs) and
+ * uploaded.  m is the MEAN thrust over the step and what the plant is given under a zero-order hold: force enters the model linearly, so the
+ * impulse of every step is exact.  tau = 0 has the pair (0, 0), and such a pair copies m = r' = c.  The applied record is the one received
+ * with thrust = m and u0 = the allocation's left inverse of m (rc = the model's rotor constant):
+ *     u0[0] = rc (-m0 - m1 + m2 + m3) / 4,  u0[1] = rc (m0 - m1 + m2 - m3) / 4,  u0[3] = rc (m0 - m1 - m2 + m3) / 4,  u0[2] = -rc (m4 + m5) / 2
+ * (operation order: rotor_kernel.hip), so the plant without the thruster stage and the observer, which read u0, see the lagged forces.  An
+ * instance whose six tau are 0 and whose commands pass unchanged (finite, inside the limits) has its whole record copied bit for bit.
+ * Bit-reproducible against tests/rotor_restatement.py.  The u log and the tracker keep the COMMANDED input; the thruster stage's clip_ticks
+ * and lost_sq count the lagged thrusts m as its "commanded".  Bookkeeping per step: last = m, lag_sq[b] += sum_i (c_i - m_i)^2, the stage's
+ * own step count.  The coefficients hold for ONE step length: while the stage is on, brov_plant_step and every closed loop whose dt is not
+ * bit-equal to h are refused with BROV_ERR_ARG and step nothing.  observer_applied != 0: brov_ekf_update_from_solver reads the applied records
+ * (ahead of the delay stage's flag).  The one-launch closed loop and the *_ticks kernels know no rotors, so the loops take their
+ * launch-per-tick branch; a brov_fleet refuses such a solver.  Stage off (the default, and after brov_rotor_off): every launch is the one of
+ * a solver without the stage.  Before any brov_rotor_set_host the configuration is tau = 0 everywhere, no limits, h = 0.
+ * Out of scope: quadratic speed-to-thrust conversion, slew-rate limits, the plugin's propeller efficiency, a lead compensator, the fleet.
+ * Refused with BROV_ERR_ARG and a text in brov_last_error() that starts with the call's name (nothing changes, nothing is waited for): a NULL
+ * handle, a negative or non-finite tau, a non-finite h, a NaN limit, cmd_lo[i] > cmd_hi[i], a non-finite state. */
+int brov_rotor_coeffs(double tau, double h, double* alpha, double* beta);   /* pure host function, needs no device; tau == 0: (0, 0); BROV_ERR_ARG for tau < 0 or not finite, h not finite or <= 0 */
+int brov_rotor_set_host(brov_solver* s, const double* tau /*[B][6]; NULL: 0.2 everywhere, the reference's*/, double h /*<= 0: the options' Ts*/,
+                        const double* cmd_lo /*[6]; NULL: -inf*/, const double* cmd_hi /*[6]; NULL: +inf*/,
+                        int32_t observer_applied);                    /* switches the stage on, zeroes the state, the statistics and the step count */
+int brov_rotor_off(brov_solver* s);
+int brov_rotor_enabled(const brov_solver* s);                         /* 0 for NULL */
+int brov_rotor_reset(brov_solver* s);                                 /* zeroes the state, the statistics and the step count */
+int brov_rotor_set_state_host(brov_solver* s, const double* r /*[B][6], finite*/);
+int brov_rotor_get_state_host(brov_solver* s, double* r /*[B][6]*/);
+int brov_rotor_last_host(brov_solver* s, double* u0_applied /*[B][4]*/, double* thrust_applied /*[B][6]*/);   /* what the last plant step was given; one may be NULL */
+int brov_rotor_get_stats_host(brov_solver* s, double* lag_sq /*[B]*/, int64_t* steps);   /* either may be NULL */
+int brov_rotor_get_coeffs_host(brov_solver* s, double* alpha /*[B][6]*/, double* beta /*[B][6]*/, double* h);   /* the uploaded values; any may be NULL, not all */
+/* the stage alone: applied [B][6] and state_out [B][6] for the commands commanded [B][6] from state [B][6] (NULL: the stage's own); moves nothing */
+int brov_rotor_eval_host(brov_solver* s, const double* commanded, const double* state, double* applied, double* state_out);
+int brov_rotor_last_seconds(brov_solver* s, double* seconds);         /* the last shift launch, HIP events */
+
 /* ---- sensor stage between the plant and the controller: noisy, biased, quantised, slow and dropped measurements.  Without it the solve, the
  * observer (brov_ekf_update_from_solver) and the estimator (brov_rls_update_from_ekf) read the plant's true state.  While the stage is on they
  * read the MEASURED state ymeas [B][12] instead; the plant, the logs and the tracker keep the true state x0.  The fresh sample of channel c of
