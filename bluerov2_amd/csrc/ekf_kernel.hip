@@ -528,6 +528,9 @@ __global__ __launch_bounds__(64, 2) void ekf_update_kernel_sp(EkfArgs A) {
         load_row(v_ye, ye);
 #pragma unroll
         for (int k = 0; k < EN; k++) { dp = fma(bufY[k * EN + l], ye[k], dp); ds = fma(bufY[k * EN + 16 + ls], ye[k], ds); }
+        // !ok: the gain is zero but the innovation may hold a NaN (a NaN acceleration), and 0 x NaN = NaN -- the correction is selected,
+        // not multiplied, to zero: the estimate is the prediction
+        dp = ok ? dp : 0.0; ds = ok ? ds : 0.0;
         const double xp_ = v_xp[l] + dp, xs_ = v_xp[16 + ls] + ds;
         v_xn[l] = xp_;
         if (sec) v_xn[16 + l] = xs_;
@@ -601,6 +604,16 @@ __global__ __launch_bounds__(64, 2) void ekf_update_kernel_sp(EkfArgs A) {
         pg[16 * EN + l] = Pn.p[16];
         pg[17 * EN + l] = Pn.p[17];
         if (sec) { pg[(16 + l) * EN + 16] = Pn.s[16]; pg[(16 + l) * EN + 17] = Pn.s[17]; }
+        if (!ok) {
+            // the kept covariance is the prediction F G + Q, whose 16 x 16 block and corner are symmetric only up to a rounding (every entry
+            // has its own sum): its upper triangle is mirrored over the lower one -- exactly symmetric.  Off the path of a filter that
+            // updates; the fence puts these stores behind the ones above, which wrote the same addresses from other lanes of the wave.
+            __threadfence();
+#pragma unroll
+            for (int j = 1; j < 16; j++)
+                if (j > l) pg[j * EN + l] = Pn.p[j];
+            if (l == 0) pg[17 * EN + 16] = Pn.s[17];
+        }
     }
     // ---- outputs: world-frame disturbance with the MEASURED attitude (:540-545), NMPC parameters (:334-337)
     __syncthreads();

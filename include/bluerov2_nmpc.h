@@ -649,7 +649,8 @@ int brov_ekf_update_host(brov_ekf* e, const double* thrust /*[B][6]*/, const dou
                          const double* acc /*[B][6]*/, void* stream);
 int brov_ekf_update_device(brov_ekf* e, const double* thrust, const double* y12, const double* acc, void* stream);
 /* outputs of the last tick: world-frame disturbance (:540-545), NMPC parameters p[0..3] (:334-337), per-instance status
- * (0 ok; 1 innovation covariance not positive definite or NaN: estimate and covariance left at the prediction;
+ * (0 ok; 1 innovation covariance not positive definite or NaN: estimate and covariance left at the prediction x_pred,
+ *  F P F' + Q -- the covariance exactly symmetric -- and wf, mpc_p made from that estimate;
  *  2 non-finite estimate, e.g. a NaN measurement: propagated as the reference would) */
 int brov_ekf_get_outputs_host(brov_ekf* e, double* wf /*[B][6] or NULL*/, double* mpc_p /*[B][4] or NULL*/,
                               int* status /*[B] or NULL*/);

@@ -1,7 +1,9 @@
 """GPU parity of the batched EKF disturbance observer against the CPU oracle, through the
 C ABI (brov_ekf_*).  Tolerances: the filter differentiates by forward differences with d = 1e-6 (last-bit differences of
 sin/cos and of FMA contraction are amplified by ~1e10 ulp in F and H) and inverts an innovation covariance of condition
-~1e9-1e10 explicitly, exactly as the reference does; two correct FP64 implementations agree to ~1e-6 of the innovation."""
+~1e9-1e10 explicitly, exactly as the reference does; two correct FP64 implementations agree to ~1e-6 of the innovation.
+Anything tighter than 1e-6 is tests/test_gpu_ekf_exact.py's: the same kernel against the filter at 60 digits, in parameter regimes
+(fd_step 2^-7, R 1) where two correct evaluations agree to 1e-13, held to four times the double implementations' own error."""
 import os
 
 import numpy as np
@@ -197,6 +199,14 @@ def test_failure_is_flagged_per_instance(ba, orc):
     orc.update(xo, Po, thrust, np.nan_to_num(y12), np.nan_to_num(acc))
     np.testing.assert_allclose(xg[ok], xo[ok], rtol=1e-6, atol=1e-6)
     assert st[1] == 1 and np.isfinite(Pg[1]).all()      # kept at the prediction
+    # ... the estimate too (the header's promise for status 1), and the outputs made from it: the oracle's RK4 map and Jacobian at the state
+    # the tick started from (tests/test_gpu_ekf_exact.py holds both to the 60-digit prediction)
+    tau = c["K"] @ thrust[1]
+    F = orc.jac_F(x[1], tau)
+    np.testing.assert_allclose(xg[1], orc.rk4(x[1], tau), rtol=1e-6, atol=1e-6)
+    np.testing.assert_allclose(Pg[1], F @ P[1] @ F.T + np.diag(c["Q"]), rtol=1e-5, atol=1e-7)
+    wfg, mpg, _ = e.outputs()
+    assert np.isfinite(wfg[1]).all() and np.isfinite(mpg[1]).all()
     assert st[3] == 2 and not np.isfinite(xg[3]).all()   # NaN measurement: propagated, flagged
     assert not st[ok].any()
 
