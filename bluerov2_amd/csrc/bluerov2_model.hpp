@@ -108,6 +108,16 @@ struct NoWorldWrench {};
 // A world wrench (possibly zero) AND an ocean current: a WORLD-frame water velocity (vx, vy, vz) in m/s, constant over a control tick (the
 // reference's underwater_current_plugin, bluerov2_environ/worlds/ocean_waves.world).  The third tag of model_f: the plant of plant_current.hip.
 struct WorldWrenchCurrent { WorldWrench ww; double vx, vy, vz; };
+// ... AND the Coriolis and centripetal forces the OCP model drops (brov_coriolis_*): the fourth tag of model_f, the plant of plant_coriolis.hip.
+// terms: BROV_CORIOLIS_* bit mask; xa, ya, za: the instance's true added masses p[4..6]; ka, ma: the stage's roll / pitch added inertia.
+struct CoriolisStage { int terms; double xa, ya, za, ka, ma; };
+struct WorldWrenchCurrentCoriolis { WorldWrenchCurrent wc; CoriolisStage cs; };
+// c = [X Y Z N], the stage's force at the body velocities nu = (u v w p q r) and the velocity through the water nr: plant_stages.hpp, which a
+// file that instantiates the fourth tag includes
+__device__ __forceinline__ void coriolis_force(const CoriolisStage& cs, const double (&nu)[6], const double (&nr)[3], double (&c)[4]);
+// the wrench-and-current part of either tag that has one
+__device__ __forceinline__ const WorldWrenchCurrent& current_part(const WorldWrenchCurrent& w) { return w; }
+__device__ __forceinline__ const WorldWrenchCurrent& current_part(const WorldWrenchCurrentCoriolis& w) { return w.wc; }
 
 // xdot = f(x,u,p), WW = NoWorldWrench: the model of the OCP; also returns the stage point record.
 // WW = WorldWrench: the same model under an additional world-frame wrench, the plant of brov_plant_step with a wrench mode in force
@@ -119,11 +129,15 @@ struct WorldWrenchCurrent { WorldWrench ww; double vx, vy, vz; };
 // WW = WorldWrenchCurrent: the world wrench as above, and the water moves: the current is projected like the force, c = R^T vc, and the two
 // damping terms of rows 6, 7, 8 are evaluated at the velocity through the water, v - c.  Quasi-static drag only: the state stays the velocity
 // over ground, and no other row sees the current (profiles/current_isa.txt: the other two instantiations unchanged).
+// WW = WorldWrenchCurrentCoriolis: the third tag, and the rigid-body and added-mass Coriolis forces of rows X, Y, Z, N (coriolis_force,
+// plant_stages.hpp) at this stage point's velocities -- the added-mass group at the velocity through the water -- enter where the model's own
+// disturbances do: dx, dy, dz, dn (profiles/coriolis_isa.txt: the other three instantiations unchanged).
 template <class WW>
 __device__ __forceinline__ void model_f(const double (&x)[NX], const Wrench& w, const ModelPar& m, const WW& ww, double (&f)[NX],
                                         StagePoint& sp) {
-    static_assert(std::is_same_v<WW, WorldWrench> || std::is_same_v<WW, NoWorldWrench> || std::is_same_v<WW, WorldWrenchCurrent>,
-                  "a world wrench, a world wrench with a current, or the tag for none");
+    static_assert(std::is_same_v<WW, WorldWrench> || std::is_same_v<WW, NoWorldWrench> || std::is_same_v<WW, WorldWrenchCurrent> ||
+                      std::is_same_v<WW, WorldWrenchCurrentCoriolis>,
+                  "a world wrench, a world wrench with a current, the two under the Coriolis stage, or the tag for none");
     sincos_pio2(x[3], &sp.sph, &sp.cph);
     sincos_pio2(x[4], &sp.sth, &sp.cth);
     sincos_pio2(x[5], &sp.sps, &sp.cps);
@@ -144,16 +158,23 @@ __device__ __forceinline__ void model_f(const double (&x)[NX], const Wrench& w, 
         dn += (r02 * ww.tx + r12 * ww.ty + r22 * ww.tz);
     }
     double ur = sp.vu, vr = sp.vv, wr = sp.vw;   // velocity through the water: over ground, unless there is a current
-    if constexpr (std::is_same_v<WW, WorldWrenchCurrent>) {
-        dx += (r00 * ww.ww.fx + r10 * ww.ww.fy + r20 * ww.ww.fz);
-        dy += (r01 * ww.ww.fx + r11 * ww.ww.fy + r21 * ww.ww.fz);
-        dz += (r02 * ww.ww.fx + r12 * ww.ww.fy + r22 * ww.ww.fz);
-        k3 += (r00 * ww.ww.tx + r10 * ww.ww.ty + r20 * ww.ww.tz);
-        k4 += (r01 * ww.ww.tx + r11 * ww.ww.ty + r21 * ww.ww.tz);
-        dn += (r02 * ww.ww.tx + r12 * ww.ww.ty + r22 * ww.ww.tz);
-        ur -= (r00 * ww.vx + r10 * ww.vy + r20 * ww.vz);
-        vr -= (r01 * ww.vx + r11 * ww.vy + r21 * ww.vz);
-        wr -= (r02 * ww.vx + r12 * ww.vy + r22 * ww.vz);
+    if constexpr (std::is_same_v<WW, WorldWrenchCurrent> || std::is_same_v<WW, WorldWrenchCurrentCoriolis>) {
+        const WorldWrenchCurrent& wc = current_part(ww);
+        dx += (r00 * wc.ww.fx + r10 * wc.ww.fy + r20 * wc.ww.fz);
+        dy += (r01 * wc.ww.fx + r11 * wc.ww.fy + r21 * wc.ww.fz);
+        dz += (r02 * wc.ww.fx + r12 * wc.ww.fy + r22 * wc.ww.fz);
+        k3 += (r00 * wc.ww.tx + r10 * wc.ww.ty + r20 * wc.ww.tz);
+        k4 += (r01 * wc.ww.tx + r11 * wc.ww.ty + r21 * wc.ww.tz);
+        dn += (r02 * wc.ww.tx + r12 * wc.ww.ty + r22 * wc.ww.tz);
+        ur -= (r00 * wc.vx + r10 * wc.vy + r20 * wc.vz);
+        vr -= (r01 * wc.vx + r11 * wc.vy + r21 * wc.vz);
+        wr -= (r02 * wc.vx + r12 * wc.vy + r22 * wc.vz);
+    }
+    if constexpr (std::is_same_v<WW, WorldWrenchCurrentCoriolis>) {
+        const double nu[6] = {sp.vu, sp.vv, sp.vw, sp.wp, sp.wq, sp.wr}, nr[3] = {ur, vr, wr};
+        double c[4];
+        coriolis_force(ww.cs, nu, nr, c);   // evaluated afresh at every stage
+        dx += c[0]; dy += c[1]; dz += c[2]; dn += c[3];
     }
     f[0] = r00 * sp.vu + r01 * sp.vv + r02 * sp.vw;
     f[1] = r10 * sp.vu + r11 * sp.vv + r12 * sp.vw;
@@ -192,7 +213,7 @@ __device__ __forceinline__ void erk4_step(const double (&x)[NX], const Wrench& w
 }
 
 // x <- the state one control period dt later, in `substeps` ERK4 steps with input and wrenches held.  The plant of plant_kernel
-// and plant_thruster_kernel (plant_wrench.hip), plant_current_kernel (plant_current.hip) and fleet_plant_kernel (fleet_kernel.hip).  NOT of plant_wrench_kernel (plant_wrench.hip) and plant_step_wave
+// and plant_thruster_kernel (plant_wrench.hip), plant_current_kernel (plant_current.hip), plant_coriolis_kernel (plant_coriolis.hip) and fleet_plant_kernel (fleet_kernel.hip).  NOT of plant_wrench_kernel (plant_wrench.hip) and plant_step_wave
 // (qp/fused.hpp), which restate erk4_step's statements for the reasons given there: a change to the step is made here AND in those two.
 template <class WW>
 __device__ __forceinline__ void plant_erk4(double (&x)[NX], const Wrench& w, const ModelPar& m, const WW& ww, double dt, int substeps) {

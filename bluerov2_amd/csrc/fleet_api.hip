@@ -303,6 +303,11 @@ static int plant_modes_ok(const brov_fleet* f, const char* who) {
                       "the vehicles in still water";
         return BROV_ERR_ARG;
     }
+    if (brov_coriolis_terms(f->s) != 0) {
+        g_fleet_err = std::string(who) + ": the Coriolis stage of the solver's plant is on (brov_coriolis_set); the fleet's plant integrates "
+                      "the OCP model, which has no such forces";
+        return BROV_ERR_ARG;
+    }
     if (brov_sensor_enabled(f->s) == 1) {
         g_fleet_err = std::string(who) + ": the sensor stage of the solver is on (brov_sensor_set_host); the fleet hands every candidate its "
                       "vehicle's true state";

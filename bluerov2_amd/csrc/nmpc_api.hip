@@ -838,6 +838,32 @@ extern "C" int brov_current_last_seconds(brov_solver* s, double* seconds) {
     HIPCHK(hipSetDevice(s->device));
     return s->plant.cu.last_seconds(seconds, call_ctx(s, "brov_current_last_seconds"));
 }
+// ---- Coriolis stage of the plant (plant_coriolis.hip): thin forwards to its host side, coriolis_source.hpp ------------------------------------
+extern "C" int brov_coriolis_set(brov_solver* s, int terms, double ka, double ma) {
+    return s ? s->plant.co.set(terms, ka, ma, call_ctx(s, "brov_coriolis_set")) : no_solver("brov_coriolis_set");
+}
+extern "C" int brov_coriolis_off(brov_solver* s) { return s ? s->plant.co.set_off() : no_solver("brov_coriolis_off"); }
+extern "C" int brov_coriolis_terms(const brov_solver* s) { return s ? s->plant.co.terms() : 0; }
+extern "C" int brov_coriolis_get(const brov_solver* s, int* terms, double* ka, double* ma) {
+    if (!s) return no_solver("brov_coriolis_get");
+    return s->plant.co.get(terms, ka, ma, call_ctx(const_cast<brov_solver*>(s), "brov_coriolis_get"));
+}
+extern "C" int brov_coriolis_eval_host(brov_solver* s, const double* x, const double* vc, double* c) {
+    if (!s) return no_solver("brov_coriolis_eval_host");
+    if (!x || !c) return call_ctx(s, "brov_coriolis_eval_host").refuse("null argument");
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(sync_last(s));
+    s->plant.ensure_params(s->last_stream);   // the plant parameters the next step would use
+    return s->plant.co.eval_host(x, vc, c, s->plant.pplant, s->last_stream, call_ctx(s, "brov_coriolis_eval_host"));
+}
+extern "C" int brov_coriolis_last_host(brov_solver* s, double* c) {
+    return s ? s->plant.co.last_host(c, call_ctx(s, "brov_coriolis_last_host")) : no_solver("brov_coriolis_last_host");
+}
+extern "C" int brov_coriolis_last_seconds(brov_solver* s, double* seconds) {
+    if (!s) return no_solver("brov_coriolis_last_seconds");
+    HIPCHK(hipSetDevice(s->device));
+    return s->plant.co.last_seconds(seconds, call_ctx(s, "brov_coriolis_last_seconds"));
+}
 // ---- sensor stage between plant and controller (sensor_kernel.hip): thin forwards to its host side, sensor_source.hpp, with sensor_wait ---------
 static CallCtx sensor_ctx(brov_solver* s, const char* who) { return call_ctx(s, who, sensor_wait); }
 extern "C" int brov_sensor_set_host(brov_solver* s, uint64_t seed, const double* sigma, const double* bias, const double* quant, const int32_t* period,

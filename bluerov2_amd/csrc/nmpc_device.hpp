@@ -188,6 +188,21 @@ void launch_plant_current(double* x0, const brov_result* res, const double* ppla
                           long long tick, double* wlog /*[B][6] or nullptr*/, hipStream_t st);
 void launch_current_eval(const CurrentGen& cg, int B, long long tick, double* out /*[B][3]*/, hipStream_t st);
 
+// Coriolis stage of the plant (plant_coriolis.hip; include/bluerov2_nmpc.h, brov_coriolis_*): the rigid-body and added-mass Coriolis forces on
+// rows X, Y, Z, N, a pure function of (this record, the instance's plant parameters, its state, the water's velocity).  No state.
+struct CoriolisGen {
+    int terms = 0;                   // BROV_CORIOLIS_* bit mask, 0: off
+    double ka = 0.0, ma = 1.2481;    // roll / pitch added inertia, shared by the batch
+    double* last = nullptr;          // [B][4] the force at the start state of the last plant step under the stage
+};
+// one plant step under the stage (terms not 0): launch_plant_current's step -- behind the thruster stage where th_on, under the world wrench
+// of g where its mode is not OFF and in the current of cg, which may be OFF here -- with the stage's force at every RK stage; co.last <- the force at the start
+void launch_plant_coriolis(double* x0, const brov_result* res, const double* pplant, const double* prp, int rp_stride, int B, double dt, int substeps,
+                           double* xlog, double* ulog, bool th_on, const ThrusterPar& T, const ThrusterDev& D, const WrenchGen& g, const CurrentGen& cg,
+                           const CoriolisGen& co, long long tick, double* wlog /*[B][6] or nullptr*/, hipStream_t st);
+// the force alone: out [B][4] for the states x [B][12] in water moving with vc [B][3] (nullptr: still), added masses from pplant [B][16]
+void launch_coriolis_eval(const CoriolisGen& co, const double* pplant, int B, const double* x, const double* vc, double* out, hipStream_t st);
+
 // sensor stage between the plant and the controller (sensor_kernel.hip; include/bluerov2_nmpc.h, brov_sensor_*): the measured state the
 // solve, the observer and the estimator read in place of the plant's true state.  A fresh sample is a pure function of (these records,
 // instance, measurement index, channel, true value); the only state is the measured state itself, which a held channel keeps.

@@ -1,11 +1,13 @@
 // plant_stages.hpp -- the device side of the plant's stateless stages ahead of the model, shared by the plant kernels of plant_wrench.hip and
-// plant_current.hip: the world-frame wrench generator (brov_plant_wrench_*) and the thruster stage with its accounting (brov_thruster_*).
+// plant_current.hip and plant_coriolis.hip: the world-frame wrench generator (brov_plant_wrench_*), the thruster stage with its accounting
+// (brov_thruster_*) and the Coriolis stage's force (brov_coriolis_*), which model_f calls under its fourth tag.
 // Written with explicitly rounded operations under `fp contract(off)` (hipcc otherwise contracts a product and a sum into an FMA, also across
 // inlined calls), so that every kernel that inlines them and the numpy restatements of tests/ agree bit for bit.  Device code.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "nmpc_device.hpp"
+#include "bluerov2_model.hpp"   // kMass, sincos_pio2, CoriolisStage
 #include "rounded_ops.hpp"   // splitmix64_finalise, rn_mul, rn_add
 
 namespace brov {
@@ -90,6 +92,56 @@ __device__ __forceinline__ void thruster_account(const ThrusterPar& T, const Thr
         D.last[(size_t)b * 6 + i] = a[i];
     }
     D.lost_sq[b] = rn_add(D.lost_sq[b], sq);
+}
+
+// ---- the Coriolis stage (brov_coriolis_*): the Coriolis and centripetal forces of the vehicle the reference's observer is written for
+// (BLUEROV2_DOB::f(), bluerov2_dob.cpp:651-677; dynamics_C(), :894-906), which the OCP model drops.  Rows X, Y, Z, N of -C_RB(nu) nu (m = kMass,
+// CG at the origin) and of -C_A(nu_r) nu_r for the diagonal added mass (Xa, Ya, Za, ka, ma, .), at nu = (u v w p q r) and the velocity
+// through the water nr = (ur vr wr):
+//   RIGID:  cX = m ((r v) - (q w))      cY = m ((p w) - (r u))      cZ = m ((q u) - (p v))      cN = 0
+//   ADDED:  ax = Xa ur, ay = Ya vr, az = Za wr;  bx = ka p, by = ma q
+//           aX = (ay r) - (az q)        aY = (az p) - (ax r)        aZ = (ax q) - (ay p)        aN = ((ax vr) - (ay ur)) + ((bx q) - (by p))
+//   both:   one add per channel, rigid + added
+// every product and every difference rounded on its own, in the order written: coriolis_eval_kernel, model_f under its fourth tag and the
+// numpy restatement of tests/coriolis_restatement.py agree bit for bit on the same inputs.  No state.  Both groups are computed and the
+// terms SELECT among them: with a branch per group in each of the four inlined stages plant_coriolis_kernel needed 255 VGPRs and 48 AGPRs
+// (occupancy 1); branch-free it needs 242 and none.
+__device__ __forceinline__ void coriolis_force(const CoriolisStage& cs, const double (&nu)[6], const double (&nr)[3], double (&c)[4]) {
+#pragma clang fp contract(off)
+    const double u = nu[0], v = nu[1], w = nu[2], p = nu[3], q = nu[4], r = nu[5];
+    const bool rigid = cs.terms & BROV_CORIOLIS_RIGID, added = cs.terms & BROV_CORIOLIS_ADDED;
+    double g[4], a[4];
+    g[0] = rn_mul(kMass, rn_add(rn_mul(r, v), -rn_mul(q, w)));
+    g[1] = rn_mul(kMass, rn_add(rn_mul(p, w), -rn_mul(r, u)));
+    g[2] = rn_mul(kMass, rn_add(rn_mul(q, u), -rn_mul(p, v)));
+    g[3] = 0.0;
+    const double ax = rn_mul(cs.xa, nr[0]), ay = rn_mul(cs.ya, nr[1]), az = rn_mul(cs.za, nr[2]);
+    const double bx = rn_mul(cs.ka, p), by = rn_mul(cs.ma, q);
+    a[0] = rn_add(rn_mul(ay, r), -rn_mul(az, q));
+    a[1] = rn_add(rn_mul(az, p), -rn_mul(ax, r));
+    a[2] = rn_add(rn_mul(ax, q), -rn_mul(ay, p));
+    a[3] = rn_add(rn_add(rn_mul(ax, nr[1]), -rn_mul(ay, nr[0])), rn_add(rn_mul(bx, q), -rn_mul(by, p)));
+#pragma unroll
+    for (int i = 0; i < 4; i++) c[i] = (rigid && added) ? rn_add(g[i], a[i]) : (added ? a[i] : (rigid ? g[i] : 0.0));   // no terms: zeros
+}
+
+// the velocity through the water for coriolis_force where nothing but a state and a world-frame water velocity vc is at hand (the evaluation
+// kernel, the `last` rows of the plant kernel): nr = x[6..9) - R^T vc with the attitude of x, R as model_f writes it from sincos_pio2, every
+// product and sum rounded on its own, rows summed left to right.  (model_f's own projection is written for speed, with contractions.)
+__device__ __forceinline__ void water_velocity(const double (&x)[NX], const double (&vc)[3], double (&nr)[3]) {
+#pragma clang fp contract(off)
+    double sph, cph, sth, cth, sps, cps;
+    sincos_pio2(x[3], &sph, &cph);
+    sincos_pio2(x[4], &sth, &cth);
+    sincos_pio2(x[5], &sps, &cps);
+    const double r00 = rn_mul(cps, cth), r01 = rn_add(rn_mul(rn_mul(cps, sth), sph), -rn_mul(sps, cph)),
+                 r02 = rn_add(rn_mul(sps, sph), rn_mul(rn_mul(cps, cph), sth));
+    const double r10 = rn_mul(sps, cth), r11 = rn_add(rn_mul(cps, cph), rn_mul(rn_mul(sph, sth), sps)),
+                 r12 = rn_add(rn_mul(rn_mul(sth, sps), cph), -rn_mul(cps, sph));
+    const double r20 = -sth, r21 = rn_mul(cth, sph), r22 = rn_mul(cth, cph);
+    nr[0] = rn_add(x[6], -rn_add(rn_add(rn_mul(r00, vc[0]), rn_mul(r10, vc[1])), rn_mul(r20, vc[2])));
+    nr[1] = rn_add(x[7], -rn_add(rn_add(rn_mul(r01, vc[0]), rn_mul(r11, vc[1])), rn_mul(r21, vc[2])));
+    nr[2] = rn_add(x[8], -rn_add(rn_add(rn_mul(r02, vc[0]), rn_mul(r12, vc[1])), rn_mul(r22, vc[2])));
 }
 
 }  // namespace brov

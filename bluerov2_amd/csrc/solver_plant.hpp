@@ -1,9 +1,10 @@
 // solver_plant.hpp -- the simulated plant of a brov_solver as one object: its true parameters, the world wrench it is under (WrenchSource),
-// the delay between the controller's commands and it (DelaySource), the rotors that answer them (RotorSource), the thruster stage ahead of it (ThrusterSource), the water it moves in (CurrentSource), the sensor stage behind it (SensorSource), its step counter, and what the solver's entry
+// the delay between the controller's commands and it (DelaySource), the rotors that answer them (RotorSource), the thruster stage ahead of it (ThrusterSource), the water it moves in (CurrentSource), the Coriolis forces on it (CoriolisSource), the sensor stage behind it (SensorSource), its step counter, and what the solver's entry
 // points ask of them: which state the controller sees, whether the next n steps may run, whether the loop's own kernels can integrate it, and
 // the one place that picks the plant kernel.  What it shares with the controller stays the solver's: non-owning pointers, given once at
-// create.  The public brov_plant_* / brov_delay_* / brov_rotor_* / brov_thruster_* / brov_current_* / brov_sensor_* forwards stay in nmpc_api.hip.  Host code only, header only.
+// create.  The public brov_plant_* / brov_delay_* / brov_rotor_* / brov_thruster_* / brov_current_* / brov_coriolis_* / brov_sensor_* forwards stay in nmpc_api.hip.  Host code only, header only.
 #pragma once
+#include "coriolis_source.hpp"
 #include "current_source.hpp"
 #include "delay_source.hpp"
 #include "rotor_source.hpp"
@@ -34,15 +35,16 @@ struct SolverPlant {
     WrenchSource wr;               // world-frame wrench (brov_plant_wrench_*), its buffers allocated on first use; it stores the step counter
     ThrusterSource th;             // thruster stage (brov_thruster_*): limits, faults and propulsion matrix, its buffers allocated on first use
     CurrentSource cu;              // ocean current (brov_current_*): a world-frame water velocity, its buffers allocated on first use
+    CoriolisSource co;             // Coriolis stage (brov_coriolis_*): the forces the OCP model drops, its buffers allocated on first use
     SensorSource sn;               // sensor stage (brov_sensor_*): the measured state, its buffers allocated on first use
     DelaySource dl;                // delay stage (brov_delay_*): the queue of commanded records and the predictor, its buffers allocated on first use
     RotorSource ro;                // rotor stage (brov_rotor_*): first-order dynamics of the thrusters behind the delay, its buffers allocated on first use
 
     void init(int B_, int N_, double* x0_, const brov_result* res_, const double* par_, double* const* par_rp_, const bool* dist6_) {
         B = B_; N = N_; x0 = x0_; res = res_; par = par_; par_rp = par_rp_; dist6 = dist6_;
-        wr.B = th.B = cu.B = sn.B = dl.B = ro.B = (size_t)B_;
+        wr.B = th.B = cu.B = co.B = sn.B = dl.B = ro.B = (size_t)B_;
     }
-    void destroy() { wr.destroy(); th.destroy(); cu.destroy(); sn.destroy(); dl.destroy(); ro.destroy(); }
+    void destroy() { wr.destroy(); th.destroy(); cu.destroy(); co.destroy(); sn.destroy(); dl.destroy(); ro.destroy(); }
 
     long long tick() const { return wr.tick; }   // plant steps so far (brov_plant_wrench_seek sets it): the wrench's tick, the sensor's index
     // may the next `n` steps run?  The wrench's generator, then the current's draws, then the sensor's index
@@ -54,7 +56,7 @@ struct SolverPlant {
     // may a step of length `dt` run?  The rotor stage's coefficients hold for one step length alone
     int dt_ok(double dt, const CallCtx& c) const { return ro.dt_ok(dt, c); }
     // no stage in force: the *_ticks kernels, which integrate the plant themselves and know none of them, can run the loop in one launch
-    bool plain() const { return wr.off() && !th.on && cu.off() && !sn.on && !dl.on && !ro.on; }
+    bool plain() const { return wr.off() && !th.on && cu.off() && !co.on && !sn.on && !dl.on && !ro.on; }
 
     // what the controller knows of the state: the measured state while the sensor stage is on, else the true one
     const double* controller_state() const { return sn.on ? sn.ymeas : x0; }
@@ -81,14 +83,21 @@ struct SolverPlant {
     int rp_stride() const { return prp_plant_set ? 2 : (N + 1) * 2; }
 
     // one plant step at the counter's tick on `st`, with optional DEVICE logs of this tick: the one place that picks the plant kernel (thruster
-    // stage off and both modes OFF: as it always was; a current in force: its kernel, which knows the other two).  Sensor stage on: a regular refresh behind it at the counter's new value (the caller has asked steps_ok)
+    // stage off and both modes OFF: as it always was; a current in force: its kernel, which knows the other two; the Coriolis stage on: its
+    // kernel, which knows the other three).  Sensor stage on: a regular refresh behind it at the counter's new value (the caller has asked steps_ok)
     void step(double dt, int substeps, double* xlog, double* ulog, double* wlog, hipStream_t st) {
         // delay stage on: its step ahead of the plant kernel, which then reads the applied records; the `u` log is the stage's, the commanded input
         const brov_result* rec = res;
         if (dl.on) { dl.shift(res, ulog, st); rec = dl.applied; ulog = nullptr; }
         // rotor stage on: behind the delay, ahead of the thruster stage; it lags the record that arrives and logs the commanded input likewise
         if (ro.on) { ro.shift(rec, ulog, st); rec = ro.applied; ulog = nullptr; }
-        if (!cu.off()) {
+        if (co.on) {
+            if (th.on) (void)th.timer.start(st);     // the thruster stage's timing and step count, as its own step() keeps them ...
+            if (!cu.off()) (void)cu.timer.start(st);   // ... and the current's, as its own
+            co.step(x0, rec, pplant, rp(), rp_stride(), dt, substeps, xlog, ulog, th.on, th.par, th.dev, wr.gen, cu.gen, wr.tick, wlog, st);
+            if (!cu.off()) (void)cu.timer.stop(st);
+            if (th.on) { (void)th.timer.stop(st); th.steps++; }
+        } else if (!cu.off()) {
             if (th.on) (void)th.timer.start(st);   // the thruster stage's timing and step count, as its own step() keeps them
             cu.step(x0, rec, pplant, rp(), rp_stride(), dt, substeps, xlog, ulog, th.on, th.par, th.dev, wr.gen, wr.tick, wlog, st);
             if (th.on) { (void)th.timer.stop(st); th.steps++; }

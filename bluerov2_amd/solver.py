@@ -22,6 +22,7 @@ MAX_N_LDS = 128  # BROV_MAX_N_LDS (LDS-resident kernels)
 PATH_AUTO, PATH_STREAMING, PATH_FUSED, PATH_WINDOWED = 0, 1, 2, 3
 WRENCH_OFF, WRENCH_CONSTANT, WRENCH_PERIODIC, WRENCH_TABLE = 0, 1, 2, 3   # BROV_WRENCH_*
 CURRENT_OFF, CURRENT_CONSTANT, CURRENT_TABLE, CURRENT_GAUSS_MARKOV = 0, 1, 2, 3   # BROV_CURRENT_*
+CORIOLIS_RIGID, CORIOLIS_ADDED = 1, 2   # BROV_CORIOLIS_*: a bit mask
 
 # nominal hydrodynamic parameters the nodes pass every tick (bluerov2_dob.cpp:340-353); p[0:4] = disturbance
 P_NOMINAL = np.array([0, 0, 0, 0, 1.7182, 0, 5.468, 0.4006, -11.7391, -20, -31.8678, -5, -18.18, -21.66, -36.99, -1.55])
@@ -145,6 +146,9 @@ def _protos(L):
         "brov_current_gauss_markov_host": [vp, C.c_uint64, dp, dp, dp, dp, dp, C.c_double], "brov_current_off": [vp], "brov_current_mode": [vp],
         "brov_current_eval_host": [vp, C.c_int64, dp], "brov_current_get_state_host": [vp, dp], "brov_current_set_state_host": [vp, dp],
         "brov_current_last_host": [vp, dp], "brov_current_last_seconds": [vp, dp],
+        "brov_coriolis_set": [vp, C.c_int, C.c_double, C.c_double], "brov_coriolis_off": [vp], "brov_coriolis_terms": [vp],
+        "brov_coriolis_get": [vp, C.POINTER(C.c_int), dp, dp], "brov_coriolis_eval_host": [vp, dp, dp, dp], "brov_coriolis_last_host": [vp, dp],
+        "brov_coriolis_last_seconds": [vp, dp],
         "brov_delay_set_host": [vp, C.POINTER(C.c_int32), C.c_int32, C.c_double, C.c_int32], "brov_delay_off": [vp], "brov_delay_enabled": [vp],
         "brov_delay_comp": [vp], "brov_delay_depth": [vp], "brov_delay_reset": [vp], "brov_delay_last_host": [vp, dp, dp],
         "brov_delay_queue_host": [vp, dp], "brov_delay_predict_host": [vp, dp, dp], "brov_delay_predicted_host": [vp, dp],
@@ -833,6 +837,45 @@ class BatchSolver(_Handle):
         """duration of the last plant kernel launched under a current (HIP events)"""
         sec = C.c_double(0.0)
         self._chk(self._L.brov_current_last_seconds(self._h, C.byref(sec)), "current_last_seconds")
+        return sec.value
+
+    # ---- Coriolis stage of the plant: the rigid-body and added-mass Coriolis forces the OCP model drops (brov_coriolis_*) ----------------------
+    def set_coriolis(self, rigid=True, added=False, ka=0.0, ma=1.2481):
+        """the plant steps from now on integrate the vehicle the reference's observer is written for: rows X, Y, Z, N of
+            rigid=  -C_RB(nu) nu, the rigid-body products m (r v - q w), ...: exactly what the EKF's model has
+            added=  -C_A(nu_r) nu_r of the diagonal added mass (the plant's true p[4..6] and the roll / pitch added inertia ka, ma), at the
+                    velocity through the water
+        evaluated afresh at every RK stage; the controller, the predictor, the observer and the estimator keep their models"""
+        terms = (CORIOLIS_RIGID if rigid else 0) | (CORIOLIS_ADDED if added else 0)
+        self._chk(self._L.brov_coriolis_set(self._h, terms, float(ka), float(ma)), "set_coriolis")
+
+    def coriolis_off(self):
+        """the plant kernels as they always were"""
+        self._chk(self._L.brov_coriolis_off(self._h), "coriolis_off")
+
+    def coriolis_terms(self):
+        """the CORIOLIS_* bit mask in force, 0 while off"""
+        return int(self._L.brov_coriolis_terms(self._h))
+
+    def coriolis_eval(self, x, vc=None):
+        """[B, 4]: the stage's force [X Y Z N] at the states x [B, 12], in water moving with the world-frame velocities vc ([3] for all or
+        [B, 3]; None: still water), evaluated by the device with the plant parameters the next step would use (moves nothing)"""
+        x = _arr(x, (self.B, 12))
+        v = None if vc is None else np.ascontiguousarray(np.broadcast_to(np.asarray(vc, dtype=np.float64), (self.B, 3)))
+        c = np.empty((self.B, 4))
+        self._chk(self._L.brov_coriolis_eval_host(self._h, _dp(x), _dp(v), _dp(c)), "coriolis_eval")
+        return c
+
+    def coriolis_last(self):
+        """[B, 4]: the stage's force at the start state of the last plant step under it"""
+        c = np.empty((self.B, 4))
+        self._chk(self._L.brov_coriolis_last_host(self._h, _dp(c)), "coriolis_last")
+        return c
+
+    def coriolis_last_seconds(self):
+        """duration of the last plant kernel launched under the Coriolis stage (HIP events)"""
+        sec = C.c_double(0.0)
+        self._chk(self._L.brov_coriolis_last_seconds(self._h, C.byref(sec)), "coriolis_last_seconds")
         return sec.value
 
     # ---- sensor stage between plant and controller: noise, bias, quantisation, slow and dropped fixes (brov_sensor_*) ------------------

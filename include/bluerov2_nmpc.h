@@ -413,6 +413,41 @@ int brov_current_set_state_host(brov_solver* s, const double* v /*[B][3]*/);   /
 int brov_current_last_host(brov_solver* s, double* v /*[B][3]*/);              /* of the last plant step under a current (zeros before the first) */
 int brov_current_last_seconds(brov_solver* s, double* seconds);                /* plant_current_kernel's last launch, HIP events */
 
+/* ---- Coriolis and centripetal forces on the plant: the vehicle the reference's observer is written for.  The OCP model, which the plant
+ * integrates, drops the Coriolis products of the linear axes; BLUEROV2_DOB::f() (bluerov2_dob.cpp:651-677) has the rigid-body ones, and the
+ * reference's simulated world is a Fossen model with C_RB + C_A (dynamics_C(), :894-906).  With the stage on, the plant adds rows X, Y, Z, N of
+ * -C_RB(nu) nu and / or -C_A(nu_r) nu_r for a diagonal added mass and the CG at the origin.  At an RK stage point with body velocities
+ * (u, v, w, p, q, r), the velocity through the water (ur, vr, wr) (= (u, v, w) without a current), m = 11.26 and the instance's TRUE plant
+ * parameters Xa, Ya, Za = p[4..6]:
+ *   BROV_CORIOLIS_RIGID   cX = m ((r v) - (q w))     cY = m ((p w) - (r u))     cZ = m ((q u) - (p v))     cN = 0
+ *   BROV_CORIOLIS_ADDED   ax = Xa ur, ay = Ya vr, az = Za wr;  bx = ka p, by = ma q
+ *                         aX = (ay r) - (az q)       aY = (az p) - (ax r)       aZ = (ax q) - (ay p)
+ *                         aN = ((ax vr) - (ay ur)) + ((bx q) - (by p))
+ *   both (3)              one add per channel, rigid + added
+ * every product and every difference rounded on its own, in the order written.  The forces enter where the model's own disturbances do (dx, dy,
+ * dz, dn, ahead of the mass scaling) and are evaluated afresh at every RK stage.  The RIGID group is exactly what the EKF's f() has.  Nothing
+ * else changes: the inertias stay the model's; the controller, the delay stage's predictor, the EKF and the RLS keep their models.  The roll and
+ * pitch rows of C_A are deliberately left out.  ka, ma: the roll / pitch added inertia (the reference: 0 and 1.2481).
+ * With the stage on brov_plant_step and every loop built on it (brov_closed_loop / _ex / _dob / _track) launch plant_coriolis_kernel, behind
+ * the delay, rotor and thruster stages, under the wrench mode and in the current in force, with their statistics and logs as ever; the
+ * one-launch closed loop does not know the stage, so the loops take their launch-per-tick branch.  Off (default): every launch is the one of a
+ * solver without the stage.  Out of scope and refused while the stage is on: brov_fleet_step, brov_closed_loop_fleet,
+ * brov_closed_loop_fleet_dob.
+ * Refused with BROV_ERR_ARG and a text in brov_last_error() that starts with the call's name (nothing changes, nothing is waited for): a NULL
+ * handle or array, terms outside 1 ... 3, ka or ma non-finite or negative. */
+#define BROV_CORIOLIS_RIGID 1
+#define BROV_CORIOLIS_ADDED 2
+int brov_coriolis_set(brov_solver* s, int terms /*1..3*/, double ka, double ma);
+int brov_coriolis_off(brov_solver* s);
+int brov_coriolis_terms(const brov_solver* s);                                 /* the bit mask in force; 0 for NULL or off */
+int brov_coriolis_get(const brov_solver* s, int* terms, double* ka, double* ma);   /* as last set (terms 0 while off; before any set: 0, 0, 1.2481) */
+/* the force alone, c = [X Y Z N] per instance, at the states x in water moving with the world-frame velocities vc (NULL: still water), with
+ * the terms in force (off: zeros) and the plant parameters the next plant step would use.  vc is projected with the state's attitude as the
+ * model does, every operation rounded on its own.  Moves nothing */
+int brov_coriolis_eval_host(brov_solver* s, const double* x /*[B][12]*/, const double* vc /*[B][3] or NULL*/, double* c /*[B][4]*/);
+int brov_coriolis_last_host(brov_solver* s, double* c /*[B][4]*/);            /* at the start state of the last plant step under the stage (zeros before the first) */
+int brov_coriolis_last_seconds(brov_solver* s, double* seconds);               /* plant_coriolis_kernel's last launch, HIP events */
+
 /* iterate (warm start) access; any pointer may be NULL to skip that block */
 int brov_set_iterate_host(brov_solver* s, const double* x, const double* u, const double* pi, const double* lam);
 int brov_get_iterate_host(brov_solver* s, double* x, double* u, double* pi, double* lam);
