@@ -1,6 +1,6 @@
 // coriolis_source.hpp -- the host side of the plant's Coriolis stage (plant_coriolis.hip: coriolis_eval_kernel, plant_coriolis_kernel; the
 // public names are brov_coriolis_* of include/bluerov2_nmpc.h): the terms in force, the stage's two coefficients, its device buffers and the
-// timing of the last plant step under it.  Its owner is a brov_solver, whose entry points check their own handle and forward here with the
+// timing of the last plant step under it.  Its owner is a brov_solver or, at batch V, a brov_fleet, whose entry points check their own handle and forward here with the
 // owner's call context (CallCtx, host_common.hpp): its wait, for what may still read or write the buffers, is called once the arguments have
 // passed, so a refused call changes nothing and waits for nothing.  Host code only, header only.
 #pragma once
@@ -61,6 +61,11 @@ struct CoriolisSource : PlantStage {   // on: terms are in force (off: the plant
         return BROV_OK;
     }
     int last_seconds(double* seconds, const CallCtx& c) { return PlantStage::last_seconds(seconds, "no plant step under the Coriolis stage yet", c); }
+    // an owner's reset (brov_fleet_reset), behind its wait: `last` to zeros; terms and coefficients stay
+    int rewind(std::string& err) {
+        if (last) BROV_HIPCHK(err, hipMemset(last, 0, B * 4 * sizeof(double)));
+        return BROV_OK;
+    }
 
     // one plant step under the stage on `st` (the owner has checked that it is on), timed; behind the thruster stage where th_on, g / cg: the
     // world wrench and the current in force, which may be OFF

@@ -1,6 +1,6 @@
 // current_source.hpp -- the host side of the plant's ocean current (plant_current.hip: current_eval_kernel, plant_current_kernel; the public
 // names are brov_current_* of include/bluerov2_nmpc.h): the generator in force, its device buffers -- the Gauss-Markov state among them --
-// and the timing of the last plant step under a current.  Its owner is a brov_solver, whose entry points check their own handle and forward
+// and the timing of the last plant step under a current.  Its owner is a brov_solver or, at batch V, a brov_fleet, whose entry points check their own handle and forward
 // here with the owner's call context (CallCtx, host_common.hpp): its wait, for what may still read or write the buffers, is called once the
 // arguments have passed, so a refused call changes nothing and waits for nothing.  Host code only, header only.
 #pragma once
@@ -127,6 +127,12 @@ struct CurrentSource : PlantStage {   // on: a mode is in force (off: the plant 
         return BROV_OK;
     }
     int last_seconds(double* seconds, const CallCtx& c) { return PlantStage::last_seconds(seconds, "no plant step under a current yet", c); }
+    // an owner's reset (brov_fleet_reset), behind its wait: the Gauss-Markov state back to its mean, `last` to zeros; mode and settings stay
+    int rewind(std::string& err) {
+        if (state && mean) BROV_HIPCHK(err, hipMemcpy(state, mean, B * 3 * sizeof(double), hipMemcpyDeviceToDevice));
+        if (last) BROV_HIPCHK(err, hipMemset(last, 0, B * 3 * sizeof(double)));
+        return BROV_OK;
+    }
 
     // one plant step under the current on `st` (the owner has checked the mode), timed; behind the thruster stage where th_on, g.mode OFF: no
     // world wrench on top

@@ -1,7 +1,8 @@
 // fleet_api.hip -- host side of the fleet planning loop (include/bluerov2_nmpc.h, brov_fleet_*; kernels: fleet_kernel.hip).  A brov_fleet is
 // laid over a brov_solver of batch B = V * C and owns what the solver has no place for: the V vehicle states, the input each vehicle was
 // given last, the winners of the last select, the vehicles' true parameters, the world-frame wrench every vehicle is under (brov_vehicle_wrench_*:
-// the solver's generator at batch V, instance index v) and what a disturbance observer of batch V is fed from (brov_vehicle_observe).  It
+// the solver's generator at batch V, instance index v), the water the vehicles move in (brov_vehicle_current_*, brov_vehicle_coriolis_*: the
+// solver's two stages at batch V; kernel: fleet_water_kernel.hip) and what a disturbance observer of batch V is fed from (brov_vehicle_observe).  It
 // reaches the solver through its public calls (brov_order_stream, brov_set_yref_candidates, brov_solve, the DEVICE pointers) and solver_view()
 // of host_common.hpp, the observer through brov_ekf_update_device and brov_ekf_mpc_p_device.  The inter-vehicle clearance term
 // (brov_clearance_*; kernels: clearance_kernel.hip) lives here too: its plan, buffers and statistics are the fleet's, and a step with the term on
@@ -15,6 +16,8 @@
 #include <vector>
 
 #include "clearance_kernel.hpp"
+#include "coriolis_source.hpp"
+#include "current_source.hpp"
 #include "fleet_kernel.hpp"
 #include "host_common.hpp"
 #include "nmpc_device.hpp"
@@ -39,6 +42,10 @@ struct brov_fleet {
     // world-frame wrench of the vehicles (brov_vehicle_wrench_*) at batch V, its buffers reserved at create.  Its counter: steps since the last
     // reset.  Its eval buffer also holds the wrench of the tick in flight where no log row takes it
     WrenchSource wr;
+    // the water the vehicles move in (brov_vehicle_current_*, brov_vehicle_coriolis_*): the solver's two stages at batch V, ticked by wr.tick
+    CurrentSource cu;
+    CoriolisSource co;
+    double* co_pp = nullptr;           // [V][16] brov_vehicle_coriolis_eval_host while pplant is unset: the parameters the plant would read
     double* vprev = nullptr;           // [V][6] velocities at the last brov_vehicle_observe (zeros after reset)
     double *y12 = nullptr, *thrust = nullptr, *acc = nullptr;   // [V][12], [V][6], [V][6] the observer's inputs
     // the inter-vehicle clearance term (brov_clearance_*), its buffers reserved at create; off by default
@@ -77,6 +84,8 @@ extern "C" void brov_fleet_destroy(brov_fleet* f) {
     (void)hipStreamSynchronize(f->last_stream);
     f->mem.free_all();
     f->wr.destroy();
+    f->cu.destroy();
+    f->co.destroy();
     f->timer.destroy();
     f->cl.timer.destroy();
     if (f->ev_done) (void)hipEventDestroy(f->ev_done);
@@ -141,6 +150,8 @@ extern "C" int brov_fleet_reset(brov_fleet* f) {
     HIPCHK(hipMemcpy2D(f->xv, 12 * sizeof(double), brov_x0_device(f->s), (size_t)f->C * 12 * sizeof(double), 12 * sizeof(double), (size_t)f->V,
                        hipMemcpyDeviceToDevice));
     f->wr.tick = 0;
+    if (int rc = f->cu.rewind(g_fleet_err)) return rc;
+    if (int rc = f->co.rewind(g_fleet_err)) return rc;
     std::vector<double> xv((size_t)f->V * 12);
     HIPCHK(hipMemcpy(xv.data(), f->xv, xv.size() * sizeof(double), hipMemcpyDeviceToHost));
     return clearance_hold(f, xv.data());
@@ -179,7 +190,8 @@ extern "C" int brov_fleet_create(brov_fleet** out, brov_solver* s, int candidate
     if (rc == BROV_OK) rc = f->mem.alloc(&f->cl.last_d2, V, g_fleet_err);
     if (rc == BROV_OK) rc = f->mem.alloc(&f->cl.min_d2, V, g_fleet_err);
     if (rc == BROV_OK) rc = f->mem.alloc(&f->cl.below, V, g_fleet_err);
-    f->wr.B = V;
+    if (rc == BROV_OK) rc = f->mem.alloc(&f->co_pp, V * 16, g_fleet_err);
+    f->wr.B = f->cu.B = f->co.B = V;
     if (rc == BROV_OK) rc = f->wr.reserve(call_ctx(f, "brov_fleet_create"));   // eager: a step reads the eval buffer without a host wait
     if (rc != BROV_OK) { g_fleet_err = "brov_fleet_create: " + g_fleet_err; brov_fleet_destroy(f); return rc; }
     if (f->timer.create() != hipSuccess || f->cl.timer.create() != hipSuccess || hipEventCreateWithFlags(&f->ev_done, hipEventDisableTiming) != hipSuccess) {
@@ -274,8 +286,63 @@ extern "C" int brov_vehicle_wrench_eval_host(brov_fleet* f, int64_t tick, double
     return f ? f->wr.eval_host(tick, w, f->last_stream, call_ctx(f, "brov_vehicle_wrench_eval_host")) : no_fleet("brov_vehicle_wrench_eval_host");
 }
 
+// ---- the water the vehicles move in: the solver's current (plant_current.hip's generator) and Coriolis stage (plant_coriolis.hip's force) at
+// batch V, thin forwards to their one host side, current_source.hpp and coriolis_source.hpp; the tick is the fleet's step counter ----------------
+extern "C" int brov_vehicle_current_constant_host(brov_fleet* f, const double* v) {
+    return f ? f->cu.constant_host(v, call_ctx(f, "brov_vehicle_current_constant_host")) : no_fleet("brov_vehicle_current_constant_host");
+}
+extern "C" int brov_vehicle_current_table_host(brov_fleet* f, const double* tab, int rows, const double* gain) {
+    return f ? f->cu.table_host(tab, rows, gain, call_ctx(f, "brov_vehicle_current_table_host")) : no_fleet("brov_vehicle_current_table_host");
+}
+extern "C" int brov_vehicle_current_gauss_markov_host(brov_fleet* f, uint64_t seed, const double* mean, const double* mu, const double* amp,
+                                                      const double* lo, const double* hi, double step) {
+    if (!f) return no_fleet("brov_vehicle_current_gauss_markov_host");
+    return f->cu.gauss_markov_host(seed, mean, mu, amp, lo, hi, step, call_ctx(f, "brov_vehicle_current_gauss_markov_host"));
+}
+extern "C" int brov_vehicle_current_off(brov_fleet* f) { return f ? f->cu.set_off() : no_fleet("brov_vehicle_current_off"); }
+extern "C" int brov_vehicle_current_mode(const brov_fleet* f) { return f ? f->cu.mode() : BROV_CURRENT_OFF; }
+extern "C" int brov_vehicle_current_eval_host(brov_fleet* f, int64_t tick, double* v) {
+    return f ? f->cu.eval_host(tick, v, f->last_stream, call_ctx(f, "brov_vehicle_current_eval_host")) : no_fleet("brov_vehicle_current_eval_host");
+}
+extern "C" int brov_vehicle_current_get_state_host(brov_fleet* f, double* v) {
+    if (!f) return no_fleet("brov_vehicle_current_get_state_host");
+    return f->cu.get_state_host(f->wr.tick, v, f->last_stream, call_ctx(f, "brov_vehicle_current_get_state_host"));
+}
+extern "C" int brov_vehicle_current_set_state_host(brov_fleet* f, const double* v) {
+    return f ? f->cu.set_state_host(v, call_ctx(f, "brov_vehicle_current_set_state_host")) : no_fleet("brov_vehicle_current_set_state_host");
+}
+extern "C" int brov_vehicle_current_last_host(brov_fleet* f, double* v) {
+    return f ? f->cu.last_host(v, call_ctx(f, "brov_vehicle_current_last_host")) : no_fleet("brov_vehicle_current_last_host");
+}
+extern "C" int brov_vehicle_coriolis_set(brov_fleet* f, int terms, double ka, double ma) {
+    return f ? f->co.set(terms, ka, ma, call_ctx(f, "brov_vehicle_coriolis_set")) : no_fleet("brov_vehicle_coriolis_set");
+}
+extern "C" int brov_vehicle_coriolis_off(brov_fleet* f) { return f ? f->co.set_off() : no_fleet("brov_vehicle_coriolis_off"); }
+extern "C" int brov_vehicle_coriolis_terms(const brov_fleet* f) { return f ? f->co.terms() : 0; }
+extern "C" int brov_vehicle_coriolis_get(const brov_fleet* f, int* terms, double* ka, double* ma) {
+    if (!f) return no_fleet("brov_vehicle_coriolis_get");
+    return f->co.get(terms, ka, ma, call_ctx(const_cast<brov_fleet*>(f), "brov_vehicle_coriolis_get"));
+}
+extern "C" int brov_vehicle_coriolis_eval_host(brov_fleet* f, const double* x, const double* vc, double* c) {
+    if (!f) return no_fleet("brov_vehicle_coriolis_eval_host");
+    if (!x || !c) return call_ctx(f, "brov_vehicle_coriolis_eval_host").refuse("null argument");
+    HIPCHK(hipSetDevice(f->device));
+    const double* pp = f->pplant;   // the parameters the next step of the fleet's plant would read
+    if (!f->pplant_set) {           // stage 0 of candidate 0 of every group, as they stand once the solver's stream has drained
+        if (int rc = wait_all(f, "brov_vehicle_coriolis_eval_host")) return rc;
+        HIPCHK(hipMemcpy2D(f->co_pp, 16 * sizeof(double), solver_view(f->s).par, (size_t)f->C * (f->N + 1) * 16 * sizeof(double), 16 * sizeof(double),
+                           (size_t)f->V, hipMemcpyDeviceToDevice));
+        pp = f->co_pp;
+    }
+    return f->co.eval_host(x, vc, c, pp, f->last_stream, call_ctx(f, "brov_vehicle_coriolis_eval_host"));
+}
+extern "C" int brov_vehicle_coriolis_last_host(brov_fleet* f, double* c) {
+    return f ? f->co.last_host(c, call_ctx(f, "brov_vehicle_coriolis_last_host")) : no_fleet("brov_vehicle_coriolis_last_host");
+}
+
 // what the plant of the fleet does not model: the vehicles' wrench is the fleet's (brov_vehicle_wrench_*), indexed
-// by the vehicle; the solver's is indexed by the instance v * C + c.  Nor does its broadcast of the vehicles' states know the solver's
+// by the vehicle; the solver's is indexed by the instance v * C + c, and so are the solver's current and Coriolis stage, which mean nothing
+// here either: the vehicles' water is the fleet's (brov_vehicle_current_*, brov_vehicle_coriolis_*).  Nor does its broadcast of the vehicles' states know the solver's
 // sensor stage (brov_sensor_*): the candidates would be solved at a measured state nothing refreshes
 static int plant_modes_ok(const brov_fleet* f, const char* who) {
     if (brov_plant_wrench_mode(f->s) != BROV_WRENCH_OFF) {
@@ -332,8 +399,10 @@ static int clearance_on(brov_fleet* f, const double* x, const brov_result* rec, 
     return BROV_OK;
 }
 
-// select + plant + broadcast on `st` (ordered by the caller, who has checked the wrench tick), with optional DEVICE log rows of this tick.
-// Under a wrench mode the wrench of the tick is evaluated into wlog's row (or the source's eval buffer): the plant's input and the log row are one.
+// select + plant + broadcast on `st` (ordered by the caller, who has checked the wrench and the current tick), with optional DEVICE log rows of
+// this tick.  Under a wrench mode the wrench of the tick is evaluated into wlog's row (or the source's eval buffer): the plant's input and the
+// log row are one.  In moving water (a current mode in force or the Coriolis stage on) the plant is fleet_plant_water_kernel, which evaluates
+// the current itself; else every launch is the one of a fleet without the two stages.
 static int step_on(brov_fleet* f, const brov_result* rec, double dt, int substeps, double* xlog, double* ulog, int32_t* stlog, int32_t* winlog,
                    double* wlog, hipStream_t st) {
     if (!rec) rec = brov_results_device(f->s);
@@ -348,14 +417,15 @@ static int step_on(brov_fleet* f, const brov_result* rec, double dt, int substep
     else { a.pp = solver_view(f->s).par; a.pp_stride = (long long)f->C * (f->N + 1) * 16; }   // stage 0 of candidate 0, as it stands now
     a.dt = dt; a.substeps = substeps; a.u_hold = f->u_hold; a.status = f->status;
     a.xlog = xlog; a.ulog = ulog; a.stlog = stlog; a.winlog = winlog;
-    if (f->wr.off()) {
-        launch_fleet_plant(a, st);
-    } else {
-        double* wv = wlog ? wlog : f->wr.eval;
+    const bool water = !f->cu.off() || f->co.on;
+    double* wv = f->wr.off() ? nullptr : (wlog ? wlog : f->wr.eval);
+    if (wv) {
         launch_wrench_eval(f->wr.gen, f->V, f->wr.tick, wv, st);
         HIPCHK(hipGetLastError());
-        launch_fleet_plant_wrench(a, wv, st);
     }
+    if (water) launch_fleet_plant_water(a, wv, f->cu.gen, f->co.gen, f->wr.tick, st);
+    else if (wv) launch_fleet_plant_wrench(a, wv, st);
+    else launch_fleet_plant(a, st);
     HIPCHK(hipGetLastError());
     launch_fleet_bcast(f->xv, f->V, f->C, brov_x0_device(f->s), st);
     HIPCHK(hipGetLastError());
@@ -375,6 +445,7 @@ extern "C" int brov_fleet_step(brov_fleet* f, const brov_result* rec, double dt,
     }
     if (int rc = plant_modes_ok(f, "brov_fleet_step")) return rc;
     if (int rc = f->wr.steps_ok(1, call_ctx(f, "brov_fleet_step"))) return rc;
+    if (int rc = f->cu.steps_ok(f->wr.tick, 1, call_ctx(f, "brov_fleet_step"))) return rc;
     HIPCHK(hipSetDevice(f->device));
     hipStream_t st = (hipStream_t)stream;
     if (int rc = order_both(f, st, "brov_fleet_step")) return rc;
@@ -467,6 +538,7 @@ static int fleet_loop(brov_fleet* f, brov_ekf* e, const char* who, int ticks, do
         if (int rc = apply_ok(f, who)) return rc;
     }
     if (int rc = f->wr.steps_ok(ticks, call_ctx(f, who))) return rc;
+    if (int rc = f->cu.steps_ok(f->wr.tick, ticks, call_ctx(f, who))) return rc;
     const SolverView sv = solver_view(f->s);
     if (!sv.cand_set) {
         g_fleet_err = pre + "no candidate parameters (brov_set_candidate_params_host)";

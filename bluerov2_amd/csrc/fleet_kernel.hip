@@ -14,10 +14,11 @@
 // 104 bytes), then the winner's record once.
 //
 // fleet_plant_kernel / fleet_plant_wrench_kernel: one lane per vehicle; where its input comes from and what it records is its own
-// (fleet_plant_vehicle), the step between is plant_erk4 (bluerov2_model.hpp), the function plant_kernel calls, without / with a WorldWrench.
+// (fleet_plant_vehicle, fleet_plant_device.hpp, shared with the plant in moving water of fleet_water_kernel.hip), the step between is plant_erk4 (bluerov2_model.hpp), the function plant_kernel calls, without / with a WorldWrench.
 #include <hip/hip_runtime.h>
 
 #include "fleet_kernel.hpp"
+#include "fleet_plant_device.hpp"   // fleet_plant_vehicle: gather, plant_erk4, record
 #include "nmpc_device.hpp"
 #include "bluerov2_model.hpp"
 #include "select_device.hpp"
@@ -46,37 +47,6 @@ __global__ __launch_bounds__(kFleetSelectBlock) void fleet_select_kernel(const b
     if (winner_rec && lane < kResultWords) {   // the record as 13 words, one per lane; zeros without a winner
         result_word(winner_rec + v, lane) = bi >= 0 ? result_word(g + (bi >= 0 ? bi : 0), lane) : 0ULL;
     }
-}
-
-// the plant step of vehicle v: the input from the winner or the zero-order hold, the status rule, plant_erk4 under `ww`, state / held input /
-// status and the log rows of this tick
-template <class WW>
-__device__ __forceinline__ void fleet_plant_vehicle(const FleetPlantArgs& A, int v, const WW& ww) {
-    const int win = A.winner[v];
-    const brov_result* __restrict__ g = A.res + (size_t)v * A.C;
-    const double* usrc;
-    int status = BROV_STATUS_SUCCESS;
-    if (win >= 0) {
-        usrc = g[win].u0;
-    } else {
-        // zero-order hold: the input applied last (zeros after a reset); the status is candidate 0's, or NAN where candidate 0 reported
-        // success with a cost that is not finite
-        usrc = A.u_hold + (size_t)v * NU;
-        const int s0 = g[0].status;
-        status = s0 != BROV_STATUS_SUCCESS ? s0 : BROV_STATUS_NAN;
-    }
-    double x[NX], u[NU];
-    ModelPar m;
-    Wrench w;
-    plant_inputs(A.xv + (size_t)v * NX, usrc, A.pp + (size_t)v * A.pp_stride, nullptr, 0, x, u, m, w);
-    plant_erk4(x, w, m, ww, A.dt, A.substeps);
-    store_row(A.xv + (size_t)v * NX, x);
-    store_row(A.u_hold + (size_t)v * NU, u);
-    A.status[v] = status;
-    log_row(A.xlog, v, x);
-    log_row(A.ulog, v, u);
-    if (A.stlog) A.stlog[v] = status;
-    if (A.winlog) A.winlog[v] = win;
 }
 
 __global__ __launch_bounds__(128) void fleet_plant_kernel(FleetPlantArgs A) {

@@ -31,6 +31,13 @@ void launch_fleet_plant(const FleetPlantArgs& a, hipStream_t st);
 // the same step under the world-frame wrench wv[v][0..5] (DEVICE [V][6]), held over the tick
 void launch_fleet_plant_wrench(const FleetPlantArgs& a, const double* wv, hipStream_t st);
 
+// the same step in moving water (fleet_water_kernel.hip): under wv (nullptr: no world wrench), in the current of cg at `tick` (which may be
+// OFF where the Coriolis stage is on) and with the Coriolis stage of co where its terms are not 0; the vehicle v is the generators' instance
+// index.  cg.last / co.last <- the current applied / the stage's force at the start state; Gauss-Markov mode: the state advances
+struct CurrentGen;
+struct CoriolisGen;
+void launch_fleet_plant_water(const FleetPlantArgs& a, const double* wv, const CurrentGen& cg, const CoriolisGen& co, long long tick, hipStream_t st);
+
 // what the disturbance observer is fed per vehicle: y12[v] = xv[v], thrust[v] = allocation of u_hold[v] / kRotor, acc[v] = (v - vprev[v]) / dt;
 // vprev[v] := the velocities of xv[v]
 void launch_fleet_observe_inputs(int V, double dt, const double* xv, const double* u_hold, double* vprev, double* thrust, double* y12, double* acc,

@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from .solver import RESULT_DTYPE, _Handle, _Wrench, _arr, _bind, _dp, _load
+from .solver import RESULT_DTYPE, _Handle, _Wrench, _arr, _arr_opt, _bind, _dp, _load
 
 
 def _protos(L):
@@ -27,6 +27,15 @@ def _protos(L):
         "brov_closed_loop_fleet_dob": [vp, vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, dp, dp, ip, ip, dp, dp],
     })
     _bind(L, {"brov_vehicle_wrench_tick": [vp]}, C.c_int64)
+    _bind(L, {
+        "brov_vehicle_current_constant_host": [vp, dp], "brov_vehicle_current_table_host": [vp, dp, C.c_int, dp],
+        "brov_vehicle_current_gauss_markov_host": [vp, C.c_uint64, dp, dp, dp, dp, dp, C.c_double], "brov_vehicle_current_off": [vp],
+        "brov_vehicle_current_mode": [vp], "brov_vehicle_current_eval_host": [vp, C.c_int64, dp], "brov_vehicle_current_get_state_host": [vp, dp],
+        "brov_vehicle_current_set_state_host": [vp, dp], "brov_vehicle_current_last_host": [vp, dp],
+        "brov_vehicle_coriolis_set": [vp, C.c_int, C.c_double, C.c_double], "brov_vehicle_coriolis_off": [vp], "brov_vehicle_coriolis_terms": [vp],
+        "brov_vehicle_coriolis_get": [vp, C.POINTER(C.c_int), dp, dp], "brov_vehicle_coriolis_eval_host": [vp, dp, dp, dp],
+        "brov_vehicle_coriolis_last_host": [vp, dp],
+    })
     _bind(L, {
         "brov_clearance_set": [vp, C.c_double, C.c_double, C.c_int], "brov_clearance_off": [vp], "brov_clearance_enabled": [vp],
         "brov_clearance_set_plan_host": [vp, dp], "brov_clearance_get_plan_host": [vp, dp],
@@ -58,7 +67,7 @@ class Fleet(_Handle):
         self.V = solver.B // self.C
 
     def reset(self):
-        """held inputs to zero, every vehicle's state := x0 of its candidate 0, tick counter to zero"""
+        """held inputs to zero, every vehicle's state := x0 of its candidate 0, tick counter to zero, a Gauss-Markov current to its mean"""
         self._chk(self._L.brov_fleet_reset(self._h), "reset")
 
     def set_state(self, xv):
@@ -139,6 +148,100 @@ class Fleet(_Handle):
     def wrench_tick(self):
         """the tick counter: fleet steps since the last reset or seek (step and every closed-loop tick add one)"""
         return self._wrench.get("tick")
+
+    # ---- the water the vehicles move in (brov_vehicle_current_*, brov_vehicle_coriolis_*) ---------------------------------------------------
+    def _rows(self, v, shape, name):
+        """v broadcast to `shape` as a contiguous float64 array (None stays None); a shape that does not broadcast is a ValueError"""
+        if v is None:
+            return None
+        try:
+            return np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), shape))
+        except ValueError:
+            raise ValueError(f"{name} must be {list(shape)} (or broadcast to it), got {list(np.shape(v))}") from None
+
+    def set_current(self, constant=None, table=None, gain=None, gauss_markov=None):
+        """the fleet steps from now on run in moving water, BatchSolver.set_current at batch V with the vehicle as instance: exactly one of
+            constant=      [3] for all or [V, 3], world-frame (vx, vy, vz) in m/s
+            table=         [rows, 3], one row per fleet step (wrench_tick()), the last row repeated; gain= [V] scales it per vehicle: one
+                           body of water and V vehicles in it
+            gauss_markov=  dict(mean [3] or [V, 3], mu, amp: scalar or [3]; optional seed=0, lo=-5, hi=5: scalar or [3], step=0.05)"""
+        if (constant is not None) + (table is not None) + (gauss_markov is not None) != 1:
+            raise ValueError("set_current takes exactly one of constant=, table=, gauss_markov=")
+        if gain is not None and table is None:
+            raise ValueError("gain= goes with table=")
+        if constant is not None:
+            self._chk(self._L.brov_vehicle_current_constant_host(self._h, _dp(self._rows(constant, (self.V, 3), "constant"))), "set_current")
+        elif table is not None:
+            tab = np.ascontiguousarray(table, dtype=np.float64)
+            if tab.ndim != 2 or tab.shape[1] != 3 or tab.shape[0] < 1:
+                raise ValueError("current table must be [rows][3]")
+            self._chk(self._L.brov_vehicle_current_table_host(self._h, _dp(tab), tab.shape[0], _dp(_arr_opt(gain, (self.V,)))), "set_current")
+        else:
+            kw = dict(seed=0, mean=None, mu=None, amp=None, lo=None, hi=None, step=0.05)
+            unknown = set(gauss_markov) - set(kw)
+            if unknown:
+                raise ValueError(f"unknown Gauss-Markov current parameters {sorted(unknown)}")
+            kw.update(gauss_markov)
+            if kw["mean"] is None or kw["mu"] is None or kw["amp"] is None:
+                raise ValueError("gauss_markov= needs mean, mu and amp")
+            r = self._rows
+            self._chk(self._L.brov_vehicle_current_gauss_markov_host(
+                self._h, int(kw["seed"]) & 0xFFFFFFFFFFFFFFFF, _dp(r(kw["mean"], (self.V, 3), "mean")), _dp(r(kw["mu"], (3,), "mu")),
+                _dp(r(kw["amp"], (3,), "amp")), _dp(r(kw["lo"], (3,), "lo")), _dp(r(kw["hi"], (3,), "hi")), float(kw["step"])), "set_current")
+
+    def current_off(self):
+        """still water; with the Coriolis stage off too, the plant kernels as they always were"""
+        self._chk(self._L.brov_vehicle_current_off(self._h), "current_off")
+
+    def current_mode(self):
+        return int(self._L.brov_vehicle_current_mode(self._h))
+
+    def _current_out(self, fn, name, *args):
+        v = np.empty((self.V, 3))
+        self._chk(fn(self._h, *args, _dp(v)), name)
+        return v
+
+    def current(self, tick):
+        """[V, 3]: the constant / table current of every vehicle at `tick`, evaluated by the device generator (moves nothing)"""
+        return self._current_out(self._L.brov_vehicle_current_eval_host, "current", int(tick))
+
+    def current_state(self):
+        """[V, 3]: the current the next fleet step applies (Gauss-Markov mode: the state)"""
+        return self._current_out(self._L.brov_vehicle_current_get_state_host, "current_state")
+
+    def set_current_state(self, v):
+        """Gauss-Markov mode: the state, [3] for all or [V, 3]"""
+        self._chk(self._L.brov_vehicle_current_set_state_host(self._h, _dp(self._rows(v, (self.V, 3), "the current state"))), "set_current_state")
+
+    def current_last(self):
+        """[V, 3]: the current the last fleet step applied (zeros before the first and after reset())"""
+        return self._current_out(self._L.brov_vehicle_current_last_host, "current_last")
+
+    def set_coriolis(self, terms, ka=0.0, ma=1.2481):
+        """the fleet's plant from now on adds the Coriolis and centripetal forces of `terms` (CORIOLIS_RIGID, CORIOLIS_ADDED or both) at every
+        RK stage, with the vehicles' true added masses (set_plant_params) and the roll / pitch added inertia ka, ma"""
+        self._chk(self._L.brov_vehicle_coriolis_set(self._h, int(terms), float(ka), float(ma)), "set_coriolis")
+
+    def coriolis_off(self):
+        self._chk(self._L.brov_vehicle_coriolis_off(self._h), "coriolis_off")
+
+    def coriolis_terms(self):
+        """the CORIOLIS_* bit mask in force, 0 while off"""
+        return int(self._L.brov_vehicle_coriolis_terms(self._h))
+
+    def coriolis_eval(self, x, vc=None):
+        """[V, 4]: the stage's force [X Y Z N] at the states x [V, 12] in water moving with vc ([3] for all or [V, 3]; None: still water),
+        with the parameters the next fleet step would read (moves nothing)"""
+        x = _arr(x, (self.V, 12))
+        c = np.empty((self.V, 4))
+        self._chk(self._L.brov_vehicle_coriolis_eval_host(self._h, _dp(x), _dp(self._rows(vc, (self.V, 3), "vc")), _dp(c)), "coriolis_eval")
+        return c
+
+    def coriolis_last(self):
+        """[V, 4]: the stage's force at the start state of the last fleet step under it (zeros before the first and after reset())"""
+        c = np.empty((self.V, 4))
+        self._chk(self._L.brov_vehicle_coriolis_last_host(self._h, _dp(c)), "coriolis_last")
+        return c
 
     def observe(self, ekf, dt=0.05, stream=0):
         """one tick of the observer `ekf` (BatchEkf of batch V) on the vehicles' states, the inputs they were given and (v - v_prev) / dt"""

@@ -392,8 +392,8 @@ int brov_sensor_last_seconds(brov_solver* s, double* seconds); /* the measure ke
  *                              set with brov_current_set_state_host.  One lane per instance, no atomics: bit-reproducible.
  * With a mode in force brov_plant_step and every loop built on it (brov_closed_loop / _ex / _dob / _track) launch plant_current_kernel, behind
  * the thruster stage and under the wrench mode in force, with their statistics and logs as ever; the one-launch closed loop knows no current,
- * so the loops take their launch-per-tick branch.  Out of scope and refused while a mode is in force: brov_fleet_step, brov_closed_loop_fleet,
- * brov_closed_loop_fleet_dob.
+ * so the loops take their launch-per-tick branch.  This current is indexed by the INSTANCE: brov_fleet_step, brov_closed_loop_fleet and
+ * brov_closed_loop_fleet_dob refuse a solver with a mode in force; the water a fleet's vehicles move in is set with brov_vehicle_current_*.
  * Refused with BROV_ERR_ARG and a text in brov_last_error() that starts with the call's name (nothing changes, nothing is waited for): a NULL
  * handle or array, a non-finite value, lo[i] > hi[i], step < 0, rows < 1, a negative tick. */
 #define BROV_CURRENT_OFF 0
@@ -431,8 +431,8 @@ int brov_current_last_seconds(brov_solver* s, double* seconds);                /
  * With the stage on brov_plant_step and every loop built on it (brov_closed_loop / _ex / _dob / _track) launch plant_coriolis_kernel, behind
  * the delay, rotor and thruster stages, under the wrench mode and in the current in force, with their statistics and logs as ever; the
  * one-launch closed loop does not know the stage, so the loops take their launch-per-tick branch.  Off (default): every launch is the one of a
- * solver without the stage.  Out of scope and refused while the stage is on: brov_fleet_step, brov_closed_loop_fleet,
- * brov_closed_loop_fleet_dob.
+ * solver without the stage.  This stage is indexed by the INSTANCE: brov_fleet_step, brov_closed_loop_fleet and brov_closed_loop_fleet_dob
+ * refuse a solver with the stage on; the stage of a fleet's vehicles is set with brov_vehicle_coriolis_*.
  * Refused with BROV_ERR_ARG and a text in brov_last_error() that starts with the call's name (nothing changes, nothing is waited for): a NULL
  * handle or array, terms outside 1 ... 3, ka or ma non-finite or negative. */
 #define BROV_CORIOLIS_RIGID 1
@@ -884,7 +884,7 @@ int  brov_fleet_create(brov_fleet** out, brov_solver* s, int candidates);   /* B
 void brov_fleet_destroy(brov_fleet* f);                                      /* does not destroy the solver */
 int  brov_fleet_vehicles(const brov_fleet* f);
 int  brov_fleet_candidates(const brov_fleet* f);
-int  brov_fleet_reset(brov_fleet* f);                    /* u_hold = 0; v_prev = 0; xv := x0 of candidate 0 of every group; tick counter 0; plan and clearance statistics as new (done by create) */
+int  brov_fleet_reset(brov_fleet* f);                    /* u_hold = 0; v_prev = 0; xv := x0 of candidate 0 of every group; tick counter 0; Gauss-Markov current := its mean; plan and clearance statistics as new (done by create) */
 int  brov_fleet_set_state_host(brov_fleet* f, const double* xv /*[V][12]*/);   /* also broadcast into the solver's x0 */
 int  brov_fleet_get_state_host(brov_fleet* f, double* xv /*[V][12]*/);
 int  brov_fleet_set_plant_params_host(brov_fleet* f, const double* p /*[V][16]; NULL: stage-0 parameters of candidate 0 of each group, re-read at every step*/);
@@ -925,6 +925,22 @@ int brov_vehicle_wrench_seek(brov_fleet* f, int64_t tick);     /* tick >= 0 */
 int64_t brov_vehicle_wrench_tick(const brov_fleet* f);
 /* the wrench of every vehicle at `tick`, HOST [V][6]; moves neither the counter nor a state; zeros while OFF */
 int brov_vehicle_wrench_eval_host(brov_fleet* f, int64_t tick, double* w /*[V][6]*/);
+/* The water the vehicles move in: the ocean current (brov_current_*) and the Coriolis stage (brov_coriolis_*) at batch V, owned by the fleet,
+ * with the vehicle v as the instance index: vehicle v is in the current, and draws the Gauss-Markov noise, of instance v of a solver of batch V
+ * under the same settings, whatever C.  Semantics, argument checks and refusals are those of the solver's two families (BROV_ERR_ARG, a text
+ * in brov_fleet_last_error() that starts with the call's name; nothing changes, nothing is waited for).  The plant tick is the fleet's step
+ * counter, the one brov_vehicle_wrench_tick reads; a Gauss-Markov step or loop that would draw at a tick >= 2^22 is refused before anything
+ * is enqueued.  A TABLE current with a per-vehicle gain is the case of ONE body of water and V vehicles in it: one time series, scaled by what
+ * each vehicle sees of it.  The added masses of the Coriolis stage are the vehicle's true parameters p[4..6] (brov_fleet_set_plant_params_host),
+ * or, without them, the stage-0 parameters of candidate 0 the fleet's plant reads.
+ * With a current mode in force or the Coriolis stage on, brov_fleet_step and the fleet's loops launch fleet_plant_water_kernel in place of
+ * their plant kernel: the current is evaluated inside it (no launch more per tick), the wrench mode in force stays on top.  With both off (the
+ * default) every launch is the one of a fleet without them.  brov_fleet_reset sets the Gauss-Markov state back to its mean, as it sets the
+ * counter to 0, and zeroes what the two _last_host calls return; modes and settings stay in force, as the wrench's do.  The observer
+ * (brov_vehicle_observe, brov_vehicle_apply_estimate) sees the water only through the vehicles' motion.  The solver's OWN current and Coriolis
+ * stage are indexed by the instance v * C + c and stay refused by the fleet's step and loops.
+ * The two families are declared in bluerov2_nmpc_water.h, which this header includes here: every caller of this header has them. */
+#include "bluerov2_nmpc_water.h"
 /* The observer's tick behind a fleet step, brov_ekf_batch(e) == V: measurement = xv, thrusts = the reference's allocation of the input every
  * vehicle was GIVEN in the last step (the winner's u0 or the held input) with the OCP model's rotor constant, acceleration = (v - v_prev) / dt
  * with v_prev kept in the fleet (zeros after brov_fleet_reset); then brov_ekf_update_device on `stream`.  `dt` is the time between two
