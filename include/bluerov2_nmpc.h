@@ -999,6 +999,12 @@ int brov_clearance_last_seconds(brov_fleet* f, double* seconds);      /* the dis
 int brov_clearance_dev_set_slices(brov_fleet* f, int slices);
 int brov_clearance_dev_slices(const brov_fleet* f);                   /* the count in force; 0 for NULL */
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * The reference's second disturbance observer: the 21-dimensional error-state Kalman filter over IMU and GPS of the bluerov2_states
+ * nodelet, brov_eskf_* (DESIGN.md section 4.4b).  Declared in bluerov2_nmpc_eskf.h, which this header includes here.
+ * ------------------------------------------------------------------------------------------------------------------- */
+#include "bluerov2_nmpc_eskf.h"
+
 #ifdef __cplusplus
 }
 #endif

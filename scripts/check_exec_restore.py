@@ -91,17 +91,34 @@ def listing(path):
 
 def scan(lines):
     ins = []      # (line number, text) of instructions / labels, comments stripped
+    addr = {}     # a disassembly also gives addresses: index in ins -> address of a label, or the target address of a branch
     for n, ln in enumerate(lines, 1):
         t = ln.split("//")[0].split(";")[0].strip()
         m = re.match(r"^(?:[0-9a-f]+ )?<(\w+)>:$", t) or re.match(r"^([.\w$]+):", t)
         if m:
+            ma = re.match(r"^([0-9a-f]+) <", t)
+            if ma:
+                addr[len(ins)] = int(ma.group(1), 16)
             ins.append((n, "LABEL " + m.group(1)))
         elif t and not t.startswith("."):
+            ma = re.search(r"//\s*([0-9A-Fa-f]+):\s*([0-9A-Fa-f]{8})\b", ln) if t.startswith("s_cbranch_execz") else None
+            if ma:      # SOPP: the target is the next instruction's address plus four times the signed 16-bit immediate
+                imm = int(ma.group(2), 16) & 0xFFFF
+                addr[len(ins)] = int(ma.group(1), 16) + 4 + 4 * (imm - 0x10000 if imm & 0x8000 else imm)
             ins.append((n, t))
-    label_all = {}   # the disassembler numbers its labels per function (L43 exists many times): a branch means the nearest one
+    # The disassembler numbers its labels per code object (L43 exists many times): a branch means the label of that name AT ITS TARGET ADDRESS
+    # where the listing gives addresses -- in a long kernel the nearest label of that name can belong to the neighbouring code object --, and
+    # the nearest one of those, or of all of that name in a listing without addresses (compiler assembly: its labels are unique anyway)
+    label_all = {}
     for k, (_, t) in enumerate(ins):
         if t.startswith("LABEL "):
             label_all.setdefault(t[6:], []).append(k)
+
+    def target(name, k):
+        cands = label_all.get(name, [])
+        if k in addr:
+            cands = [j for j in cands if addr.get(j) == addr[k]] or cands
+        return min(cands, key=lambda j: abs(j - k), default=None)
     func, hits = "?", []
     for k, (n, t) in enumerate(ins):
         if t.startswith("LABEL ") and not re.match(r"^LABEL (\.L|L\d+$)", t):
@@ -118,7 +135,7 @@ def scan(lines):
             ms = re.match(r"^s_\w+_saveexec_b64 (s\[\d+:\d+\])", tb)
             if ms or tb.startswith("LABEL ") or not tb.startswith("s_") or re.match(r"^s_(cbranch|branch|endpgm|setpc)", tb):
                 break
-        tgt = min(label_all.get(m.group(1), []), key=lambda j: abs(j - k), default=None)
+        tgt = target(m.group(1), k)
         if not ms or tgt is None:
             continue
         saved, bad = ms.group(1), []
