@@ -8,10 +8,10 @@ from .solver import (BatchSolver, SolverOptions, RESULT_DTYPE, P_NOMINAL, build_
                      NoDeviceError, thrust_allocation, PATH_AUTO, PATH_STREAMING, PATH_FUSED, PATH_WINDOWED,
                      WRENCH_OFF, WRENCH_CONSTANT, WRENCH_PERIODIC, WRENCH_TABLE,
                      CURRENT_OFF, CURRENT_CONSTANT, CURRENT_TABLE, CURRENT_GAUSS_MARKOV, current_from_angles, rotor_coeffs,
-                     CORIOLIS_RIGID, CORIOLIS_ADDED)
+                     CORIOLIS_RIGID, CORIOLIS_ADDED, ImuParams, IMU_GPSV_ELAPSED)
 
 from .ekf import BatchEkf, EkfParams  # noqa: F401,E402
-from .eskf import BatchEskf, EskfParams  # noqa: F401,E402
+from .eskf import BatchEskf, EskfParams, closed_loop_eskf  # noqa: F401,E402
 from .rls import BatchRls, RlsParams, APPLY_DISTURBANCE, APPLY_MODEL  # noqa: F401,E402
 from .track import BatchTrack, TrackParams, TRACK_STATS_DTYPE  # noqa: F401,E402
 from .fleet import Fleet  # noqa: F401,E402
@@ -20,4 +20,5 @@ from .group import SolverGroup, GATHER_RECORDS, GATHER_PACKED, rccl_version, uni
 __all__ = ["SolverGroup", "GATHER_RECORDS", "GATHER_PACKED", "rccl_version", "unique_id", "BatchEkf", "EkfParams", "BatchEskf", "EskfParams", "BatchRls", "RlsParams", "BatchTrack", "TrackParams", "TRACK_STATS_DTYPE", "Fleet", "APPLY_DISTURBANCE", "APPLY_MODEL", "BatchSolver", "SolverOptions", "RESULT_DTYPE", "P_NOMINAL", "build_library", "library_path",
            "NoDeviceError", "thrust_allocation", "PATH_AUTO", "PATH_STREAMING", "PATH_FUSED", "PATH_WINDOWED",
            "WRENCH_OFF", "WRENCH_CONSTANT", "WRENCH_PERIODIC", "WRENCH_TABLE",
-           "CURRENT_OFF", "CURRENT_CONSTANT", "CURRENT_TABLE", "CURRENT_GAUSS_MARKOV", "current_from_angles", "rotor_coeffs", "CORIOLIS_RIGID", "CORIOLIS_ADDED"]
+           "CURRENT_OFF", "CURRENT_CONSTANT", "CURRENT_TABLE", "CURRENT_GAUSS_MARKOV", "current_from_angles", "rotor_coeffs", "CORIOLIS_RIGID", "CORIOLIS_ADDED",
+           "ImuParams", "IMU_GPSV_ELAPSED", "closed_loop_eskf"]

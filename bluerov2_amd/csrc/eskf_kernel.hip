@@ -4,7 +4,8 @@
 // body-frame disturbance force the "patty" DOB node and the consolidated controller's DOMPC mode take from /disturbance.  The formulas stand in
 // the header; tests/eskf_exact.py restates them at 60 digits.
 //
-// One kernel body, eskf_tick_kernel<UPDATE>: predict only, or predict followed by update.  Layout: one filter per 32 lanes (two per wave, one
+// One kernel body (eskf_tick_body.inc), in eskf_tick_kernel<UPDATE>: predict only, or predict followed by update; and in eskf_tick_masked_kernel:
+// per filter the one or the other, by a flag (the filter at its sensors' rates, include/bluerov2_nmpc_imu.h).  Layout: one filter per 32 lanes (two per wave, one
 // wave per block), lane i < 21 owns ROW i of P in registers, P also lies in LDS (441 doubles per filter) where the other lanes read it:
 //   * F = I + six 3 x 3 blocks.  B = P F' only mixes COLUMNS 0..8 of a row: the lane's own registers.  F B only mixes ROWS 0..8: nine lanes read
 //     up to seven rows of B out of LDS, the others keep theirs.  0.6 k multiply-adds per filter where the dense products have 18.5 k.
@@ -112,273 +113,14 @@ __device__ __forceinline__ void eskf_mirror(double* Pm, double (&row)[SN], int i
 
 template <bool UPDATE>
 __global__ __launch_bounds__(64, 2) void eskf_tick_kernel(EskfArgs A) {
-    __shared__ double sm[kEskfFilters * kEskfLds];
-    const EskfConst& c = *A.c;
-    const int f = threadIdx.x >> 5, l = threadIdx.x & 31;
-    const int inst0 = blockIdx.x * kEskfFilters + f;
-    const bool live = inst0 < A.B;
-    const int inst = live ? inst0 : A.B - 1;       // a dead half-wave repeats the last filter and writes nothing
-    const int i = l < SN ? l : SN - 1;             // lanes 21..31 repeat row 20: the same values to the same LDS addresses
-    double* Pm = sm + f * kEskfLds;
-    double* U = Pm + SN * SN;
-    double* dxs = U + SY * SY;
-    double* xs = dxs + SN;
-    double* ys = xs + SX;
-    const double dt = c.dt;
-
-    // ---- P -> LDS, 32 lanes wide; the nominal state and the IMU sample into every lane
-    double* pg = A.P + (size_t)inst * (SN * SN);
-#pragma unroll
-    for (int m = 0; m < (SN * SN + 31) / 32; m++) {
-        const int e = m * 32 + l;
-        if (e < SN * SN) Pm[e] = pg[e];
-    }
-    double x[SX], a[3], w[3];
-    {
-        const double* xg = A.x + (size_t)inst * SX;
-#pragma unroll
-        for (int j = 0; j < SX; j++) x[j] = xg[j];
-        const double* ig = A.imu + (size_t)inst * 6;
-#pragma unroll
-        for (int k = 0; k < 3; k++) { a[k] = ig[k] - x[13 + k]; w[k] = ig[3 + k] - x[10 + k]; }
-    }
-    __syncthreads();
-    double row[SN];
-#pragma unroll
-    for (int j = 0; j < SN; j++) row[j] = Pm[i * SN + j];
-
-    // ---- predict: the nominal state (Eskf.cpp:109-133) ...
-    double q[4], M1[9], M2[9], E[9];
-    {
-        double q0[4], R[9], qe[4];
-        q_unit(&x[6], q0);
-        q_rot(q0, R);
-        const double Ra[3] = {R[0] * a[0] + R[1] * a[1] + R[2] * a[2], R[3] * a[0] + R[4] * a[1] + R[5] * a[2], R[6] * a[0] + R[7] * a[1] + R[8] * a[2]};
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const double g = x[16 + k];
-            x[k] = x[k] + x[3 + k] * dt + 0.5 * Ra[k] * dt * dt + 0.5 * g * dt * dt;
-            x[3 + k] = x[3 + k] + Ra[k] * dt + g * dt;
-        }
-        q_exp(w[0] * dt, w[1] * dt, w[2] * dt, qe);
-        q_mul_unit(q0, qe, q);
-        // ... and the blocks of F (:150-157), from the NEW attitude
-        q_rot(q, R);
-#pragma unroll
-        for (int r = 0; r < 3; r++) {
-            M1[r * 3 + 0] = -(R[r * 3 + 1] * a[2] - R[r * 3 + 2] * a[1]) * dt;
-            M1[r * 3 + 1] = -(R[r * 3 + 2] * a[0] - R[r * 3 + 0] * a[2]) * dt;
-            M1[r * 3 + 2] = -(R[r * 3 + 0] * a[1] - R[r * 3 + 1] * a[0]) * dt;
-#pragma unroll
-            for (int k = 0; k < 3; k++) M2[r * 3 + k] = -R[r * 3 + k] * dt;
-        }
-        q_exp(-(w[0] * dt), -(w[1] * dt), -(w[2] * dt), qe);
-        q_rot(qe, E);
-    }
-    // ---- B = P F': columns 0..8 of the lane's own row
-    {
-        double t0[3], t1[3], t2[3];
-#pragma unroll
-        for (int r = 0; r < 3; r++) {
-            t0[r] = fma(dt, row[3 + r], row[r]);
-            double s = fma(dt, row[15 + r], row[3 + r]), e = -dt * row[9 + r];
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                s = fma(M1[r * 3 + k], row[6 + k], s);
-                s = fma(M2[r * 3 + k], row[12 + k], s);
-                e = fma(E[r * 3 + k], row[6 + k], e);
-            }
-            t1[r] = s; t2[r] = e;
-        }
-#pragma unroll
-        for (int r = 0; r < 3; r++) { row[r] = t0[r]; row[3 + r] = t1[r]; row[6 + r] = t2[r]; }
-    }
-    __syncthreads();   // every lane has its row of P out of LDS
-#pragma unroll
-    for (int j = 0; j < SN; j++) Pm[i * SN + j] = row[j];      // (lanes 21..31: what lane 20 writes)
-    __syncthreads();
-    // ---- P_pred = F B + diag(Q): rows 0..8; the coefficients of the lane's row of F are selected, not indexed
-    if (i < 9) {
-        const int grp = i / 3, r = i - 3 * grp;
-        double ca[3], cb[3];
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const double m1 = r == 0 ? M1[k] : (r == 1 ? M1[3 + k] : M1[6 + k]);
-            const double m2 = r == 0 ? M2[k] : (r == 1 ? M2[3 + k] : M2[6 + k]);
-            const double ee = r == 0 ? E[k] : (r == 1 ? E[3 + k] : E[6 + k]);
-            ca[k] = grp == 1 ? m1 : (grp == 2 ? ee : 0.0);
-            cb[k] = grp == 1 ? m2 : 0.0;
-        }
-        const double d = grp == 2 ? -dt : dt;
-        const int rd = grp == 0 ? 3 + r : (grp == 1 ? 15 + r : 9 + r);
-#pragma unroll
-        for (int j = 0; j < SN; j++) {
-            double s = grp == 2 ? 0.0 : row[j];
-            s = fma(d, Pm[rd * SN + j], s);
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                s = fma(ca[k], Pm[(6 + k) * SN + j], s);
-                s = fma(cb[k], Pm[(12 + k) * SN + j], s);
-            }
-            row[j] = s;
-        }
-    }
-    {
-        const double qi = c.Q[i];
-#pragma unroll
-        for (int j = 0; j < SN; j++) row[j] += (j == i) ? qi : 0.0;
-    }
-    eskf_mirror(Pm, row, i);
-#pragma unroll
-    for (int k = 0; k < 4; k++) x[6 + k] = q[k];
-
-    bool ok = true;
-    if constexpr (UPDATE) {
-        // ---- innovation (:203-272), every lane
-        {
-            double y[SY], qm[4], R[9], Rm[9];
-            q_unit(A.qm + (size_t)inst * 4, qm);
-            q_rot(q, R);
-            q_rot(qm, Rm);
-            const double* gp = A.gps_p + (size_t)inst * 3;
-            const double* gv = A.gps_v + (size_t)inst * 3;
-            const double* tg = A.thrust + (size_t)inst * 6;
-            double th[6];
-#pragma unroll
-            for (int k = 0; k < 6; k++) th[k] = tg[k];
-            const double qc[4] = {q[0], -q[1], -q[2], -q[3]};
-            double dq[4], att[3];
-            q_mul_unit(qc, qm, dq);
-            q_log(dq, att);
-            const double mrb[3] = {c.mass * a[0] + c.mzg * w[1], c.mass * a[1] - c.mzg * w[0], c.mass * a[2]};
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                y[k] = gp[k] - x[k];
-                y[3 + k] = gv[k] - x[3 + k];
-                y[6 + k] = att[k];
-                const double vB = R[k] * x[3] + R[3 + k] * x[4] + R[6 + k] * x[5];          // R' v
-                const double gB = -c.g * Rm[6 + k];                                        // R(q_meas)' (0, 0, -g)
-                const double ma = c.am[k] * (a[k] + gB);
-                const double d3 = (-c.Dl[k] - c.Dnl[k] * fabs(vB)) * vB;
-                const double g3 = -c.wb * R[6 + k];   // (m g - b) [sin th, -cos th sin ph, -cos th cos ph] = -(m g - b) (row 2 of R)
-                double tau = 0.0;
-#pragma unroll
-                for (int m = 0; m < 6; m++) tau += c.K3[k * 6 + m] * th[m];
-                y[9 + k] = tau - (mrb[k] - x[19 + k] + ma + d3 + g3);
-            }
-            // the predicted state and the innovation wait in LDS (every lane of the filter writes the same values) while the registers hold
-            // the rows of S and of the gain
-#pragma unroll
-            for (int j = 0; j < SX; j++) xs[j] = x[j];
-#pragma unroll
-            for (int b = 0; b < SY; b++) ys[b] = y[b];
-        }
-        // ---- S = H P H' + diag(R12): lane a < 12 gathers row a; elimination without row exchanges, the pivot row through LDS
-        double ipk[SY];
-        {
-            const int as = l < SY ? l : SY - 1;      // lanes 12..31 repeat row 11: the same values to the same addresses
-            const int ha = eskf_hsel(as);
-            const double sa = eskf_hsgn(as), r12 = c.R12[as];
-            double srow[SY];
-#pragma unroll
-            for (int b = 0; b < SY; b++) srow[b] = (sa * eskf_hsgn(b)) * Pm[ha * SN + eskf_hsel(b)] + ((b == as) ? r12 : 0.0);
-            // step k: every lane puts its row as it stands into LDS (rows <= k are final: the factor), the pivot row comes back to all, rows
-            // below it are updated -- selected, not branched: straight-line code between the barriers
-#pragma unroll
-            for (int k = 0; k < SY; k++) {
-#pragma unroll
-                for (int j = k; j < SY; j++) U[as * SY + j] = srow[j];
-                __syncthreads();
-                const double pk = U[k * SY + k];
-                ok = ok && (pk > 0.0) && (pk < 1e300);
-                ipk[k] = 1.0 / pk;
-                const double fk = srow[k] * ipk[k];
-#pragma unroll
-                for (int j = k + 1; j < SY; j++) {
-                    const double t = fma(-fk, U[k * SY + j], srow[j]);
-                    srow[j] = (as > k) ? t : srow[j];
-                }
-            }
-        }
-        // ---- row i of the gain: S z = (P H')[i,:]', two substitutions; dx_i; row i of P - Kal (P H')'
-        double dxi = 0.0;
-        if (ok) {
-            double z[SY], t[SY];
-#pragma unroll
-            for (int b = 0; b < SY; b++) {
-                double s = eskf_hsgn(b) * row[eskf_hsel(b)];
-#pragma unroll
-                for (int k = 0; k < b; k++) s = fma(-U[k * SY + b], t[k], s);
-                z[b] = s; t[b] = s * ipk[b];
-            }
-#pragma unroll
-            for (int b = SY - 1; b >= 0; b--) {
-                double s = z[b];
-#pragma unroll
-                for (int j = b + 1; j < SY; j++) s = fma(-U[b * SY + j], z[j], s);
-                z[b] = s * ipk[b];
-            }
-#pragma unroll
-            for (int b = 0; b < SY; b++) dxi = fma(z[b], ys[b], dxi);
-#pragma unroll
-            for (int b = 0; b < SY; b++) {
-                const double zb = -eskf_hsgn(b) * z[b];
-#pragma unroll
-                for (int j = 0; j < SN; j++) row[j] = fma(zb, Pm[eskf_hsel(b) * SN + j], row[j]);
-            }
-        }
-        dxs[i] = dxi;
-        eskf_mirror(Pm, row, i);   // (its first barrier also puts dxs in front of the reads below)
-        // ---- inject (:320-332)
-#pragma unroll
-        for (int j = 0; j < SX; j++) x[j] = xs[j];
-        if (ok) {
-            const double q[4] = {x[6], x[7], x[8], x[9]};
-            double dx[SN];
-#pragma unroll
-            for (int j = 0; j < SN; j++) dx[j] = dxs[j];
-            double qe[4], qn[4];
-            q_exp(dx[6], dx[7], dx[8], qe);
-            q_mul_unit(q, qe, qn);
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                x[k] += dx[k];
-                x[3 + k] += c.vel_inject * dx[3 + k];
-                x[19 + k] += dx[18 + k];
-            }
-#pragma unroll
-            for (int k = 0; k < 4; k++) x[6 + k] = qn[k];
-            if (c.inject) {
-#pragma unroll
-                for (int k = 0; k < 9; k++) x[10 + k] += dx[9 + k];
-            }
-        }
-    }
-    // ---- out: P 32 lanes wide out of LDS, the state and the outputs by lane 0
-    if (live) {
-#pragma unroll
-        for (int m = 0; m < (SN * SN + 31) / 32; m++) {
-            const int e = m * 32 + l;
-            if (e < SN * SN) pg[e] = Pm[e];
-        }
-        if (l == 0) {
-            double* xg = A.x + (size_t)inst * SX;
-            bool fin = true;
-#pragma unroll
-            for (int j = 0; j < SX; j++) { xg[j] = x[j]; fin = fin && (fabs(x[j]) < 1e300); }
-            const double qf[4] = {x[6], x[7], x[8], x[9]};
-            double R[9];
-            q_rot(qf, R);
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                A.xi[(size_t)inst * 3 + k] = x[19 + k];
-                A.xw[(size_t)inst * 3 + k] = R[k * 3] * x[19] + R[k * 3 + 1] * x[20] + R[k * 3 + 2] * x[21];
-            }
-            double* mp = A.mp + (size_t)inst * 4;
-            mp[0] = x[19] * c.inv_cc; mp[1] = x[20] * c.inv_cc; mp[2] = x[21] * c.inv_rc; mp[3] = 0.0;
-            A.status[inst] = !ok ? 1 : (fin ? 0 : 2);
-        }
-    }
+#include "eskf_tick_body.inc"
+}
+// fix [B]: 0 the predict-only tick, else the update tick, per filter; bit for bit what the two kernels above give (see eskf_tick_body.inc)
+__global__ __launch_bounds__(64, 2) void eskf_tick_masked_kernel(EskfArgs A, const int* __restrict__ fix) {
+    constexpr bool UPDATE = true;
+#define ESKF_TICK_MASKED
+#include "eskf_tick_body.inc"
+#undef ESKF_TICK_MASKED
 }
 
 // the filter's inputs from the controller's view of the plant (one lane per filter): attitude quaternion and R from the Euler angles,
@@ -432,6 +174,31 @@ __global__ void eskf_inputs_from_solver_kernel(int B, double dt, double gps_dt, 
     th[5] = (-u2) * inv_rc;
 }
 
+// the filter's inputs from the solver's IMU/GPS stage (one lane per filter): the stage's last sample and its flags into the observer's own
+// buffers -- what the tick reads and brov_eskf_get_inputs_host returns --, thrust as eskf_inputs_from_solver_kernel has it
+__global__ void eskf_inputs_from_imu_kernel(int B, double inv_rc, const double* __restrict__ s_imu, const double* __restrict__ s_gp,
+                                            const double* __restrict__ s_gv, const double* __restrict__ s_qm, const int32_t* __restrict__ s_fix,
+                                            const brov_result* __restrict__ res, double* __restrict__ imu, double* __restrict__ gps_p,
+                                            double* __restrict__ gps_v, double* __restrict__ qm, double* __restrict__ thrust, int* __restrict__ fix) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+#pragma unroll
+    for (int k = 0; k < 6; k++) imu[(size_t)b * 6 + k] = s_imu[(size_t)b * 6 + k];
+#pragma unroll
+    for (int k = 0; k < 3; k++) { gps_p[(size_t)b * 3 + k] = s_gp[(size_t)b * 3 + k]; gps_v[(size_t)b * 3 + k] = s_gv[(size_t)b * 3 + k]; }
+#pragma unroll
+    for (int k = 0; k < 4; k++) qm[(size_t)b * 4 + k] = s_qm[(size_t)b * 4 + k];
+    fix[b] = s_fix[b];
+    const double u0 = res[b].u0[0], u1 = res[b].u0[1], u2 = res[b].u0[2], u3 = res[b].u0[3];
+    double* th = thrust + (size_t)b * 6;
+    th[0] = (-u0 + u1 + u3) * inv_rc;
+    th[1] = (-u0 - u1 - u3) * inv_rc;
+    th[2] = (u0 + u1 - u3) * inv_rc;
+    th[3] = (u0 - u1 + u3) * inv_rc;
+    th[4] = (-u2) * inv_rc;
+    th[5] = (-u2) * inv_rc;
+}
+
 // p[0..3] of every stage of instance b := mpc_p of instance b (bluerov2_dob_patty.cpp:352-358); p[4..15] stay
 __global__ void eskf_apply_kernel(int B, int stages, const double* __restrict__ mp, double* __restrict__ par) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -462,6 +229,7 @@ struct brov_eskf {
     double *x = nullptr, *P = nullptr, *imu = nullptr, *gps_p = nullptr, *gps_v = nullptr, *qm = nullptr, *thrust = nullptr, *xi = nullptr,
            *xw = nullptr, *mp = nullptr, *vprev = nullptr, *pprev = nullptr;
     int* status = nullptr;
+    int* fix = nullptr;  // [B] the flags of the last masked tick that copied them (brov_imu_eskf_tick_host, brov_imu_eskf_tick_from_solver)
     bool first = true;   // no previous velocity and position yet: the next update_from_solver takes them equal to the current ones
     hipStream_t last_stream = nullptr;
     KernelTimer timer;   // around the last tick
@@ -573,7 +341,7 @@ extern "C" int brov_eskf_create(brov_eskf** out, int device, int B, const brov_e
     const size_t nb = (size_t)B;
     if (al(&e->x, nb * 22) || al(&e->P, nb * 441) || al(&e->imu, nb * 6) || al(&e->gps_p, nb * 3) || al(&e->gps_v, nb * 3) || al(&e->qm, nb * 4) ||
         al(&e->thrust, nb * 6) || al(&e->xi, nb * 3) || al(&e->xw, nb * 3) || al(&e->mp, nb * 4) || al(&e->vprev, nb * 3) || al(&e->pprev, nb * 3) ||
-        al(&e->status, nb) || al(&e->cdev, 1)) {
+        al(&e->status, nb) || al(&e->fix, nb) || al(&e->cdev, 1)) {
         g_eskf_err = "brov_eskf_create: " + g_eskf_err;
         brov_eskf_destroy(e);
         return rc;
@@ -583,7 +351,7 @@ extern "C" int brov_eskf_create(brov_eskf** out, int device, int B, const brov_e
         good = good && hipMemset(q, 0, nb * 3 * sizeof(double)) == hipSuccess;
     good = good && hipMemset(e->imu, 0, nb * 6 * sizeof(double)) == hipSuccess && hipMemset(e->thrust, 0, nb * 6 * sizeof(double)) == hipSuccess &&
            hipMemset(e->qm, 0, nb * 4 * sizeof(double)) == hipSuccess && hipMemset(e->mp, 0, nb * 4 * sizeof(double)) == hipSuccess &&
-           hipMemset(e->status, 0, nb * sizeof(int)) == hipSuccess;
+           hipMemset(e->status, 0, nb * sizeof(int)) == hipSuccess && hipMemset(e->fix, 0, nb * sizeof(int)) == hipSuccess;
     if (!good) {
         (void)hipGetLastError();
         g_eskf_err = "brov_eskf_create: device initialisation failed";
@@ -619,14 +387,16 @@ extern "C" int brov_eskf_get_state_host(brov_eskf* e, double* x, double* P) {
     return BROV_OK;
 }
 
+// fix: null, the kernel `update` names for every filter; else [B] DEVICE, the masked kernel
 static int launch_tick(brov_eskf* e, bool update, const double* imu, const double* gps_p, const double* gps_v, const double* qm, const double* thrust,
-                       hipStream_t st) {
+                       hipStream_t st, const int* fix = nullptr) {
     EskfArgs a;
     a.c = e->cdev; a.B = e->B; a.x = e->x; a.P = e->P; a.imu = imu; a.gps_p = gps_p; a.gps_v = gps_v; a.qm = qm; a.thrust = thrust;
     a.xi = e->xi; a.xw = e->xw; a.mp = e->mp; a.status = e->status;
     HIPCHK(e->timer.start(st));
     const int blocks = (e->B + kEskfFilters - 1) / kEskfFilters;
-    if (update) hipLaunchKernelGGL(eskf_tick_kernel<true>, dim3(blocks), dim3(64), 0, st, a);
+    if (fix) hipLaunchKernelGGL(eskf_tick_masked_kernel, dim3(blocks), dim3(64), 0, st, a, fix);
+    else if (update) hipLaunchKernelGGL(eskf_tick_kernel<true>, dim3(blocks), dim3(64), 0, st, a);
     else hipLaunchKernelGGL(eskf_tick_kernel<false>, dim3(blocks), dim3(64), 0, st, a);
     HIPCHK(hipGetLastError());
     HIPCHK(e->timer.stop(st));
@@ -669,6 +439,28 @@ extern "C" int brov_eskf_update_host(brov_eskf* e, const double* imu, const doub
     return launch_tick(e, true, e->imu, e->gps_p, e->gps_v, e->qm, e->thrust, st);
 }
 
+extern "C" int brov_imu_eskf_tick_device(brov_eskf* e, const double* imu, const double* gps_p, const double* gps_v, const double* q_meas,
+                                     const double* thrust, const int32_t* fix, void* stream) {
+    if (!e || !imu || !gps_p || !gps_v || !q_meas || !thrust || !fix) return refuse("brov_imu_eskf_tick_device", "null argument");
+    HIPCHK(hipSetDevice(e->device));
+    return launch_tick(e, true, imu, gps_p, gps_v, q_meas, thrust, (hipStream_t)stream, fix);
+}
+
+extern "C" int brov_imu_eskf_tick_host(brov_eskf* e, const double* imu, const double* gps_p, const double* gps_v, const double* q_meas,
+                                   const double* thrust, const int32_t* fix, void* stream) {
+    if (!e || !imu || !gps_p || !gps_v || !q_meas || !thrust || !fix) return refuse("brov_imu_eskf_tick_host", "null argument");
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t nb = (size_t)e->B * sizeof(double);
+    HIPCHK(hipMemcpyAsync(e->imu, imu, nb * 6, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(e->gps_p, gps_p, nb * 3, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(e->gps_v, gps_v, nb * 3, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(e->qm, q_meas, nb * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(e->thrust, thrust, nb * 6, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(e->fix, fix, (size_t)e->B * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    return launch_tick(e, true, e->imu, e->gps_p, e->gps_v, e->qm, e->thrust, st, e->fix);
+}
+
 extern "C" int brov_eskf_get_outputs_host(brov_eskf* e, double* xi, double* xi_world, double* mpc_p, int* status) {
     if (!e) return refuse("brov_eskf_get_outputs_host", "null handle");
     HIPCHK(hipSetDevice(e->device));
@@ -696,6 +488,7 @@ extern "C" int brov_eskf_get_inputs_host(brov_eskf* e, double* imu, double* gps_
 extern "C" const double* brov_eskf_x_device(const brov_eskf* e) { return e ? e->x : nullptr; }
 extern "C" const double* brov_eskf_P_device(const brov_eskf* e) { return e ? e->P : nullptr; }
 extern "C" const double* brov_eskf_mpc_p_device(const brov_eskf* e) { return e ? e->mp : nullptr; }
+extern "C" const double* brov_imu_eskf_xi_world_device(const brov_eskf* e) { return e ? e->xw : nullptr; }
 
 extern "C" int brov_eskf_update_from_solver(brov_eskf* e, brov_solver* s, void* stream) {
     if (!e || !s || brov_batch(s) != e->B) return refuse("brov_eskf_update_from_solver", "batch sizes differ");
@@ -709,6 +502,23 @@ extern "C" int brov_eskf_update_from_solver(brov_eskf* e, brov_solver* s, void* 
     HIPCHK(hipGetLastError());
     e->first = false;
     return launch_tick(e, true, e->imu, e->gps_p, e->gps_v, e->qm, e->thrust, st);
+}
+
+// the tick at the sensors' rates: the sample of the solver's IMU/GPS stage; predict only where no fix was due at its index, else the masked tick
+extern "C" int brov_imu_eskf_tick_from_solver(brov_eskf* e, brov_solver* s, void* stream) {
+    if (!e || !s || brov_batch(s) != e->B) return refuse("brov_imu_eskf_tick_from_solver", "batch sizes differ");
+    const ImuView v = solver_imu_view(s);
+    if (!v.on) return refuse("brov_imu_eskf_tick_from_solver", "the IMU stage of the solver is off (brov_imu_set_host)");
+    if (v.h != e->par.dt) return refuse("brov_imu_eskf_tick_from_solver", "the filter's dt is not the step h the solver's IMU stage samples");
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (brov_order_stream(s, stream) != BROV_OK) { g_eskf_err = "brov_imu_eskf_tick_from_solver: could not order behind the solver's last stream"; return BROV_ERR_HIP; }
+    if (e->last_stream != st) HIPCHK(hipStreamSynchronize(e->last_stream));
+    hipLaunchKernelGGL(eskf_inputs_from_imu_kernel, dim3((e->B + 255) / 256), dim3(256), 0, st, e->B, 1.0 / kRotor, v.imu, v.gps_p, v.gps_v, v.qm, v.fix,
+                       solver_observer_results(s), e->imu, e->gps_p, e->gps_v, e->qm, e->thrust, e->fix);
+    HIPCHK(hipGetLastError());
+    if (!v.fix_due) return launch_tick(e, false, e->imu, nullptr, nullptr, nullptr, nullptr, st);
+    return launch_tick(e, true, e->imu, e->gps_p, e->gps_v, e->qm, e->thrust, st, e->fix);
 }
 
 extern "C" int brov_eskf_apply_to_solver(brov_eskf* e, brov_solver* s, void* stream) {

@@ -380,6 +380,11 @@ static int plant_modes_ok(const brov_fleet* f, const char* who) {
                       "vehicle's true state";
         return BROV_ERR_ARG;
     }
+    if (brov_imu_enabled(f->s) == 1) {
+        g_fleet_err = std::string(who) + ": the IMU stage of the solver's plant is on (brov_imu_set_host); the fleet's plant steps the vehicles, "
+                      "which that stage never samples";
+        return BROV_ERR_ARG;
+    }
     if (brov_dist6_enabled(f->s) == 1) {
         g_fleet_err = std::string(who) + ": the 6-disturbance variant is on (brov_enable_dist6); the fleet's plant integrates the shipped model";
         return BROV_ERR_ARG;

@@ -149,6 +149,15 @@ const double* solver_measured_state(const brov_solver* s);
 // delay stage is on with observer_applied set (brov_delay_set_host): then what the last plant step was given; the rotor stage with its
 // observer_applied set (brov_rotor_set_host) comes first: its applied records, the lagged ones
 const brov_result* solver_observer_results(const brov_solver* s);
+// the solver's IMU/GPS stage (brov_imu_*) as brov_imu_eskf_tick_from_solver reads it: whether it is on, the step h it samples, whether a fix was due
+// at its last sample (else every flag is 0), and the DEVICE sample: imu [B][6], gps_p [B][3], gps_v [B][3], q_meas [B][4], fix [B]
+struct ImuView {
+    bool on = false, fix_due = false;
+    double h = 0.0;
+    const double *imu = nullptr, *gps_p = nullptr, *gps_v = nullptr, *qm = nullptr;
+    const int32_t* fix = nullptr;
+};
+ImuView solver_imu_view(const brov_solver* s);
 
 // ---- a device buffer that lives as long as a scope: freed on every way out, unless release() hands it on ---------------------------------
 template <typename T>

@@ -903,6 +903,47 @@ extern "C" int brov_sensor_last_seconds(brov_solver* s, double* seconds) {
     HIPCHK(hipSetDevice(s->device));
     return s->plant.sn.last_seconds(seconds, sensor_ctx(s, "brov_sensor_last_seconds"));
 }
+// ---- IMU/GPS stage behind the plant (imu_kernel.hip): thin forwards to its host side, imu_source.hpp, with sensor_wait: a refresh runs on
+// whatever stream a plant step was given ---------------------------------------------------------------------------------------------------
+extern "C" void brov_imu_default_params(brov_imu_params* p) {
+    if (p) *p = brov_imu_params{0.01, 9.81, 1, 0, 0};
+}
+extern "C" int brov_imu_set_host(brov_solver* s, const brov_imu_params* p, const double* sigma, const double* bias, const double* dropout) {
+    if (!s) return no_solver("brov_imu_set_host");
+    return s->plant.im.set_host(p, sigma, bias, dropout, s->x0, s->plant.tick(), s->last_stream, sensor_ctx(s, "brov_imu_set_host"));
+}
+extern "C" int brov_imu_off(brov_solver* s) { return s ? s->plant.im.set_off() : no_solver("brov_imu_off"); }
+extern "C" int brov_imu_enabled(const brov_solver* s) { return s && s->plant.im.on ? 1 : 0; }
+extern "C" int brov_imu_restart(brov_solver* s, void* stream) {
+    if (!s) return no_solver("brov_imu_restart");
+    if (!s->plant.im.on) { g_err = "brov_imu_restart: the IMU stage is off (brov_imu_set_host)"; return BROV_ERR_ARG; }
+    if (int rc = ImuSource::index_ok(s->plant.tick(), sensor_ctx(s, "brov_imu_restart"))) return rc;
+    HIPCHK(hipSetDevice(s->device));
+    if (int rc = order_behind_last(s, (hipStream_t)stream)) return rc;
+    s->plant.im.measure(s->x0, s->plant.tick(), true, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return BROV_OK;
+}
+extern "C" int brov_imu_eval_host(brov_solver* s, int64_t index, const double* x, const double* v_prev, const double* gps_p_last, const int32_t* m_last,
+                                  double* imu, double* gps_p, double* gps_v, double* q_meas, int32_t* fix) {
+    if (!s) return no_solver("brov_imu_eval_host");
+    return s->plant.im.eval_host(index, x, v_prev, gps_p_last, m_last, imu, gps_p, gps_v, q_meas, fix, s->last_stream,
+                                 sensor_ctx(s, "brov_imu_eval_host"));
+}
+extern "C" int brov_imu_get_host(brov_solver* s, double* imu, double* gps_p, double* gps_v, double* q_meas, int32_t* fix) {
+    return s ? s->plant.im.get_host(imu, gps_p, gps_v, q_meas, fix, sensor_ctx(s, "brov_imu_get_host")) : no_solver("brov_imu_get_host");
+}
+extern "C" int brov_imu_get_stats_host(brov_solver* s, int32_t* stats, int64_t* refreshes) {
+    return s ? s->plant.im.get_stats_host(stats, refreshes, sensor_ctx(s, "brov_imu_get_stats_host")) : no_solver("brov_imu_get_stats_host");
+}
+extern "C" int brov_imu_reset_stats(brov_solver* s) {
+    return s ? s->plant.im.reset_stats(sensor_ctx(s, "brov_imu_reset_stats")) : no_solver("brov_imu_reset_stats");
+}
+extern "C" int brov_imu_last_seconds(brov_solver* s, double* seconds) {
+    if (!s) return no_solver("brov_imu_last_seconds");
+    HIPCHK(hipSetDevice(s->device));
+    return s->plant.im.last_seconds(seconds, sensor_ctx(s, "brov_imu_last_seconds"));
+}
 // ---- delay stage between the controller's commands and the plant (delay_kernel.hip): thin forwards to its host side, delay_source.hpp, with
 // sensor_wait: the predictor runs on whatever stream a solve was given -----------------------------------------------------------------------
 extern "C" int brov_delay_set_host(brov_solver* s, const int32_t* delay, int32_t comp, double dt_pred, int32_t observer_applied) {
@@ -1243,6 +1284,51 @@ extern "C" int brov_closed_loop_dob(brov_solver* s, brov_ekf* e, brov_rls* r, in
     int rc = begin_logs(L, s, ticks, st, "brov_closed_loop_dob: ");
     if (rc == BROV_OK) rc = run_dob_ticks(s, e, r, rls_mode, ticks, line0, ncols, dt, substeps, L, st, "brov_closed_loop_dob");
     return L.deliver(finish_loop(st, rc, g_err, ""), g_err, "brov_closed_loop_dob: ");
+}
+
+// The loop with the error-state filter at its sensors' rates: per control tick the public calls of the header (bluerov2_nmpc_imu.h), on one
+// stream, one host wait at the end.  The logs' columns are those of declare_logs, the estimate three wide, and the fix flags behind them
+extern "C" int brov_closed_loop_eskf(brov_solver* s, brov_eskf* e, int ticks, int line0, int ncols, double dt, int imu_per_tick, double* u_log,
+                                     double* x_log, int32_t* st_log, double* w_log, double* est_log, int32_t* fix_log) {
+    const char* who = "brov_closed_loop_eskf";
+    if (!e) { g_err = "brov_closed_loop_eskf: bad argument (needs an observer)"; return BROV_ERR_ARG; }
+    if (imu_per_tick < 1) { g_err = "brov_closed_loop_eskf: bad argument (needs imu_per_tick >= 1)"; return BROV_ERR_ARG; }
+    const double h = dt / imu_per_tick;   // the plant steps of the loop: what the stages in force are asked about
+    if (int rc = loop_args_ok(s, nullptr, nullptr, 0, ticks, ncols, h, 1, who)) return rc;
+    if (brov_eskf_batch(e) != s->B) { g_err = "brov_closed_loop_eskf: batch sizes differ"; return BROV_ERR_ARG; }
+    if (!s->plant.im.on) { g_err = "brov_closed_loop_eskf: the IMU stage of the solver is off (brov_imu_set_host)"; return BROV_ERR_ARG; }
+    if (int rc = s->plant.steps_ok((long long)ticks * imu_per_tick, call_ctx(s, who))) return rc;
+    HIPCHK(hipSetDevice(s->device));
+    hipStream_t st = s->last_stream;
+    LoopLog L;
+    L.column(12, x_log, 1); L.column(4, u_log); L.column(1, st_log); L.column(6, w_log); L.column(3, est_log);
+    const int log_fix = L.column((size_t)imu_per_tick, fix_log);
+    int rc = begin_logs(L, s, ticks, st, "brov_closed_loop_eskf: ");
+    auto sub = [&](int code) {
+        if (code != BROV_OK) { g_err = std::string(who) + ": " + brov_eskf_last_error(); rc = code; }
+        return code == BROV_OK;
+    };
+    const size_t B = s->B;
+    for (int k = 0; k < ticks && rc == BROV_OK; k++) {
+        rc = brov_set_yref_from_traj(s, line0 + k, ncols, st);
+        if (rc == BROV_OK) rc = brov_solve_phase(s, st, 0);
+        if (rc != BROV_OK) break;
+        gather_status(s, L.row<int32_t>(LOG_ST, k), st);
+        for (int j = 0; j < imu_per_tick && rc == BROV_OK; j++) {
+            const bool last = j == imu_per_tick - 1;   // the tick's logs are its last plant step's
+            s->plant.ensure_params(st);
+            s->plant.step(h, 1, last ? L.row<double>(LOG_X, k) : nullptr, last ? L.row<double>(LOG_U, k) : nullptr,
+                          last ? L.row<double>(LOG_W, k) : nullptr, st);
+            if (!sub(brov_imu_eskf_tick_from_solver(e, s, st))) break;
+            if (int32_t* fx = L.row<int32_t>(log_fix, k))
+                if (hipMemcpyAsync(fx + (size_t)j * B, s->plant.im.out.fix, B * sizeof(int32_t), hipMemcpyDeviceToDevice, st) != hipSuccess) rc = BROV_ERR_HIP;
+        }
+        if (rc != BROV_OK) break;
+        if (double* est = L.row<double>(LOG_EST, k))
+            if (hipMemcpyAsync(est, brov_imu_eskf_xi_world_device(e), B * 3 * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess) rc = BROV_ERR_HIP;
+        if (rc == BROV_OK) sub(brov_eskf_apply_to_solver(e, s, st));
+    }
+    return L.deliver(finish_loop(st, rc, g_err, ""), g_err, "brov_closed_loop_eskf: ");
 }
 
 namespace brov {
@@ -1742,6 +1828,14 @@ const brov_result* solver_observer_results(const brov_solver* s) {
     if (!s) return nullptr;
     if (s->plant.ro.on && s->plant.ro.observer_applied) return s->plant.ro.applied;
     return s->plant.dl.on && s->plant.dl.observer_applied ? s->plant.dl.applied : s->res;
+}
+ImuView solver_imu_view(const brov_solver* s) {
+    ImuView v;
+    if (!s || !s->plant.im.on) return v;
+    const ImuSource& im = s->plant.im;
+    v.on = true; v.fix_due = im.fix_due; v.h = im.par.h;
+    v.imu = im.out.imu; v.gps_p = im.out.gps_p; v.gps_v = im.out.gps_v; v.qm = im.out.qm; v.fix = im.out.fix;
+    return v;
 }
 void launch_copy_stage0_par(const double* par, double* pp, int B, int N1, hipStream_t st) {   // for SolverPlant::ensure_params
     hipLaunchKernelGGL(copy_stage0_par_kernel, dim3((B * 16 + 255) / 256), dim3(256), 0, st, par, pp, B, N1);

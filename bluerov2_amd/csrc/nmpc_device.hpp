@@ -224,6 +224,28 @@ void launch_sensor_measure(const SensorPar& P, const SensorDev& D, int B, long l
 // the stage alone: fresh samples y [B][12] of the states x [B][12] at index m and the dropout verdicts [B]; moves nothing
 void launch_sensor_eval(const SensorPar& P, const SensorDev& D, int B, long long m, const double* x, double* y, int32_t* dropped, hipStream_t st);
 
+// IMU/GPS stage of the plant (imu_kernel.hip; include/bluerov2_nmpc_imu.h, brov_imu_*): what the error-state filter reads, made from the TRUE state
+struct ImuPar {                   // shared by the batch and wave-uniform: passed by value in the kernel arguments
+    double h, g;                  // the plant step the stage follows; gravity
+    int32_t gps_every, flags;     // a fix is due where index % gps_every == 0; BROV_IMU_*
+    unsigned long long seed;
+};
+struct ImuDev {                   // per instance
+    const double* sigma = nullptr;       // [B][12] accelerometer, gyro, GPS position, attitude
+    const double* bias = nullptr;        // [B][6] accelerometer, gyro
+    const double* dropout = nullptr;     // [B] probability that a due fix is dropped
+    double* vprev = nullptr;             // [B][3] v_I of the last sample
+    double* plast = nullptr;             // [B][3] gps_p of the last fix
+    int32_t* mlast = nullptr;            // [B] its index
+    int32_t* stats = nullptr;            // [B][3] samples, fixes taken, fixes dropped of the regular refreshes
+};
+struct ImuOut { double *imu, *gps_p, *gps_v, *qm; int32_t* fix; };   // [B][6], [B][3], [B][3], [B][4], [B]
+// one refresh from the true state x at index m, regular or forced (imu_measure_kernel)
+void launch_imu_measure(const ImuPar& P, const ImuDev& D, const ImuOut& O, int B, long long m, bool forced, const double* x, hipStream_t st);
+// the stage alone for given x, v_prev [B][3], gps_p_last [B][3], m_last [B] at index m; moves nothing
+void launch_imu_eval(const ImuPar& P, const ImuDev& D, const ImuOut& O, int B, long long m, const double* x, const double* vprev, const double* plast,
+                     const int32_t* mlast, hipStream_t st);
+
 // delay stage of the plant (delay_kernel.hip; include/bluerov2_nmpc.h, brov_delay_*): a ring [B][D][10] of the last D commanded records
 // (u0[4] | thrust[6]), indexed by the stage's own step count n.
 // step n of the stage: applied[b] = res[b] with u0 and thrust of step n - delay[b] (zeros before the first), res[b]'s own into slot n mod D;

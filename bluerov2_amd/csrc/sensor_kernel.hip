@@ -20,20 +20,7 @@
 
 namespace brov {
 
-__device__ __forceinline__ unsigned long long sensor_hash(unsigned long long seed, int b, int m, int c, int j) {
-    const unsigned long long k = ((unsigned long long)b << 32) | ((unsigned long long)m << 8) | ((unsigned long long)c << 2) | (unsigned long long)j;
-    return splitmix64_finalise((seed ^ 0x53454E534F52ULL) + (k + 1ULL) * 0x9E3779B97F4A7C15ULL);
-}
-
-__device__ __forceinline__ double sensor_noise(unsigned long long seed, int b, int m, int c) {
-    int S = 0;
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        const unsigned long long h = sensor_hash(seed, b, m, c, j);
-        S += (int)(h & 0xFFFF) + (int)((h >> 16) & 0xFFFF) + (int)((h >> 32) & 0xFFFF) + (int)(h >> 48);
-    }
-    return (double)(S - 393210) * 0x1.0p-16;   // exact: |S - 393210| < 2^19
-}
+// (sensor_hash and sensor_noise: rounded_ops.hpp, shared with the IMU/GPS stage of imu_kernel.hip, whose channel slots are 16..28)
 
 // is the fix of (b, m) dropped?
 __device__ __forceinline__ bool sensor_dropped(const SensorPar& P, const SensorDev& D, int b, int m) {

@@ -1,5 +1,5 @@
 // solver_plant.hpp -- the simulated plant of a brov_solver as one object: its true parameters, the world wrench it is under (WrenchSource),
-// the delay between the controller's commands and it (DelaySource), the rotors that answer them (RotorSource), the thruster stage ahead of it (ThrusterSource), the water it moves in (CurrentSource), the Coriolis forces on it (CoriolisSource), the sensor stage behind it (SensorSource), its step counter, and what the solver's entry
+// the delay between the controller's commands and it (DelaySource), the rotors that answer them (RotorSource), the thruster stage ahead of it (ThrusterSource), the water it moves in (CurrentSource), the Coriolis forces on it (CoriolisSource), the sensor stage behind it (SensorSource), the IMU/GPS stage beside that (ImuSource), its step counter, and what the solver's entry
 // points ask of them: which state the controller sees, whether the next n steps may run, whether the loop's own kernels can integrate it, and
 // the one place that picks the plant kernel.  What it shares with the controller stays the solver's: non-owning pointers, given once at
 // create.  The public brov_plant_* / brov_delay_* / brov_rotor_* / brov_thruster_* / brov_current_* / brov_coriolis_* / brov_sensor_* forwards stay in nmpc_api.hip.  Host code only, header only.
@@ -7,6 +7,7 @@
 #include "coriolis_source.hpp"
 #include "current_source.hpp"
 #include "delay_source.hpp"
+#include "imu_source.hpp"
 #include "rotor_source.hpp"
 #include "sensor_source.hpp"
 #include "thruster_source.hpp"
@@ -37,26 +38,31 @@ struct SolverPlant {
     CurrentSource cu;              // ocean current (brov_current_*): a world-frame water velocity, its buffers allocated on first use
     CoriolisSource co;             // Coriolis stage (brov_coriolis_*): the forces the OCP model drops, its buffers allocated on first use
     SensorSource sn;               // sensor stage (brov_sensor_*): the measured state, its buffers allocated on first use
+    ImuSource im;                  // IMU/GPS stage (brov_imu_*): what the error-state filter reads, from the true state, its buffers allocated on first use
     DelaySource dl;                // delay stage (brov_delay_*): the queue of commanded records and the predictor, its buffers allocated on first use
     RotorSource ro;                // rotor stage (brov_rotor_*): first-order dynamics of the thrusters behind the delay, its buffers allocated on first use
 
     void init(int B_, int N_, double* x0_, const brov_result* res_, const double* par_, double* const* par_rp_, const bool* dist6_) {
         B = B_; N = N_; x0 = x0_; res = res_; par = par_; par_rp = par_rp_; dist6 = dist6_;
-        wr.B = th.B = cu.B = co.B = sn.B = dl.B = ro.B = (size_t)B_;
+        wr.B = th.B = cu.B = co.B = sn.B = im.B = dl.B = ro.B = (size_t)B_;
     }
-    void destroy() { wr.destroy(); th.destroy(); cu.destroy(); co.destroy(); sn.destroy(); dl.destroy(); ro.destroy(); }
+    void destroy() { wr.destroy(); th.destroy(); cu.destroy(); co.destroy(); sn.destroy(); im.destroy(); dl.destroy(); ro.destroy(); }
 
     long long tick() const { return wr.tick; }   // plant steps so far (brov_plant_wrench_seek sets it): the wrench's tick, the sensor's index
     // may the next `n` steps run?  The wrench's generator, then the current's draws, then the sensor's index
     int steps_ok(long long n, const CallCtx& c) const {
         if (int rc = wr.steps_ok(n, c)) return rc;
         if (int rc = cu.steps_ok(wr.tick, n, c)) return rc;
-        return sn.steps_ok(wr.tick, n, c);
+        if (int rc = sn.steps_ok(wr.tick, n, c)) return rc;
+        return im.steps_ok(wr.tick, n, c);
     }
-    // may a step of length `dt` run?  The rotor stage's coefficients hold for one step length alone
-    int dt_ok(double dt, const CallCtx& c) const { return ro.dt_ok(dt, c); }
+    // may a step of length `dt` run?  The rotor stage's coefficients hold for one step length alone, and so does the IMU stage's differencing
+    int dt_ok(double dt, const CallCtx& c) const {
+        if (int rc = ro.dt_ok(dt, c)) return rc;
+        return im.dt_ok(dt, c);
+    }
     // no stage in force: the *_ticks kernels, which integrate the plant themselves and know none of them, can run the loop in one launch
-    bool plain() const { return wr.off() && !th.on && cu.off() && !co.on && !sn.on && !dl.on && !ro.on; }
+    bool plain() const { return wr.off() && !th.on && cu.off() && !co.on && !sn.on && !im.on && !dl.on && !ro.on; }
 
     // what the controller knows of the state: the measured state while the sensor stage is on, else the true one
     const double* controller_state() const { return sn.on ? sn.ymeas : x0; }
@@ -69,8 +75,16 @@ struct SolverPlant {
     // ... of a brov_tick_host that brought its own x0, the caller's measurement: where its kernel reads it in place, else x0, where it was copied
     const double* tick_state(bool x0_passed, const double* in_place) const { return sn.on && x0_passed && !in_place ? x0 : in_place; }
     // a caller rewrites the true state: the measured state follows it with a forced refresh at the counter's index, which must be one
-    int rewrite_ok(const CallCtx& c) const { return sn.on ? SensorSource::index_ok(wr.tick, c) : BROV_OK; }
-    bool rewritten(hipStream_t st) { if (sn.on) sn.measure(x0, wr.tick, true, st); return sn.on; }
+    // (the IMU stage restarts likewise)
+    int rewrite_ok(const CallCtx& c) const {
+        if (sn.on) { if (int rc = SensorSource::index_ok(wr.tick, c)) return rc; }
+        return im.on ? ImuSource::index_ok(wr.tick, c) : BROV_OK;
+    }
+    bool rewritten(hipStream_t st) {
+        if (sn.on) sn.measure(x0, wr.tick, true, st);
+        if (im.on) im.measure(x0, wr.tick, true, st);
+        return sn.on || im.on;
+    }
 
     // Without explicit plant parameters the plant is the controller's own model: stage-0 parameters, re-read whenever the controller's
     // parameters may have changed (setters, brov_params_device() hand-outs, the EKF's write-back).
@@ -106,6 +120,7 @@ struct SolverPlant {
         else launch_plant_wrench(x0, rec, pplant, rp(), rp_stride(), B, dt, substeps, xlog, ulog, wr.gen, wr.tick, wlog, st);
         wr.tick++;
         if (sn.on) sn.measure(x0, wr.tick, false, st);
+        if (im.on) im.measure(x0, wr.tick, false, st);
     }
     // the plain plant (the owner has asked) into a launch of P.ticks steps: what the kernel integrates it with; the counter moves on by those steps
     void into_ticks(DevParams& P, const PlantInLaunch& in) {

@@ -34,7 +34,12 @@ def _protos(L):
         "brov_eskf_get_outputs_host": [vp, dp, dp, dp, ip], "brov_eskf_get_inputs_host": [vp, dp, dp, dp, dp, dp],
         "brov_eskf_update_from_solver": [vp, vp, vp], "brov_eskf_apply_to_solver": [vp, vp, vp],
         "brov_eskf_last_update_seconds": [vp, dp],
+        "brov_imu_eskf_tick_host": [vp, dp, dp, dp, dp, dp, ip, vp], "brov_imu_eskf_tick_device": [vp, vp, vp, vp, vp, vp, vp, vp],
+        "brov_imu_eskf_tick_from_solver": [vp, vp, vp],
     })
+    _bind(L, {"brov_imu_eskf_xi_world_device": [vp]}, vp)
+    L.brov_closed_loop_eskf.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, dp, dp, ip, dp, dp, ip]
+    L.brov_closed_loop_eskf.restype = C.c_int
 
 
 def _eskf_lib():
@@ -89,6 +94,22 @@ class BatchEskf(_Handle):
         self._chk(self._L.brov_eskf_get_inputs_host(self._h, *(_dp(a) for a in out)), "inputs")
         return out
 
+    def tick(self, imu, gps_p, gps_v, q_meas, thrust, fix, stream=0):
+        """one launch for the batch: filter b does the update tick where fix[b] != 0 and the predict-only tick where it is 0, bit for bit;
+        what a filter without a fix has in gps_p, gps_v, q_meas and thrust reaches nothing"""
+        imu = _arr(imu, (self.B, 6)); gps_p = _arr(gps_p, (self.B, 3)); gps_v = _arr(gps_v, (self.B, 3))
+        q_meas = _arr(q_meas, (self.B, 4)); thrust = _arr(thrust, (self.B, 6)); fix = _arr(fix, (self.B,), np.int32)
+        self._chk(self._L.brov_imu_eskf_tick_host(self._h, _dp(imu), _dp(gps_p), _dp(gps_v), _dp(q_meas), _dp(thrust),
+                                              fix.ctypes.data_as(C.POINTER(C.c_int32)), C.c_void_p(stream)), "tick")
+
+    def tick_device(self, imu_ptr, gps_p_ptr, gps_v_ptr, q_meas_ptr, thrust_ptr, fix_ptr, stream=0):
+        self._chk(self._L.brov_imu_eskf_tick_device(self._h, *(C.c_void_p(p) for p in (imu_ptr, gps_p_ptr, gps_v_ptr, q_meas_ptr, thrust_ptr, fix_ptr)),
+                                                C.c_void_p(stream)), "tick_device")
+
+    def tick_from_solver(self, solver: BatchSolver, stream=0):
+        """the tick at the sensors' rates: the last sample of the solver's IMU/GPS stage (solver.set_imu) and its fix flags"""
+        self._chk(self._L.brov_imu_eskf_tick_from_solver(self._h, solver._h, C.c_void_p(stream)), "tick_from_solver")
+
     def update_from_solver(self, solver: BatchSolver, stream=0):
         self._chk(self._L.brov_eskf_update_from_solver(self._h, solver._h, C.c_void_p(stream)), "update_from_solver")
 
@@ -99,3 +120,20 @@ class BatchEskf(_Handle):
         s = C.c_double()
         self._chk(self._L.brov_eskf_last_update_seconds(self._h, C.byref(s)), "last_update_seconds")
         return s.value
+
+
+def closed_loop_eskf(solver: BatchSolver, eskf: BatchEskf, ticks, line0=0, ncols=16, dt=0.05, imu_per_tick=1, log=True):
+    """the control loop with the filter at its sensors' rates on the device (brov_closed_loop_eskf): ticks x (window -> RTI step ->
+    imu_per_tick x (plant step of dt / imu_per_tick -> tick_from_solver) -> apply_to_solver), one host wait.  Returns dict(u, x, status,
+    wrench, est [ticks, B, 3]: xi_world after each tick, fix [ticks, imu_per_tick, B]) or None"""
+    L, B = _eskf_lib(), solver.B
+    args = (solver._h, eskf._h, int(ticks), int(line0), int(ncols), float(dt), int(imu_per_tick))
+    if not log:
+        solver._chk(L.brov_closed_loop_eskf(*args, None, None, None, None, None, None), "closed_loop_eskf")
+        return None
+    ip = C.POINTER(C.c_int32)
+    ul, xl, sl = np.empty((ticks, B, 4)), np.empty((ticks + 1, B, 12)), np.empty((ticks, B), dtype=np.int32)
+    wl, el, fl = np.empty((ticks, B, 6)), np.empty((ticks, B, 3)), np.empty((ticks, int(imu_per_tick), B), dtype=np.int32)
+    solver._chk(L.brov_closed_loop_eskf(*args, _dp(ul), _dp(xl), sl.ctypes.data_as(ip), _dp(wl), _dp(el), fl.ctypes.data_as(ip)),
+                "closed_loop_eskf")
+    return dict(u=ul, x=xl, status=sl, wrench=wl, est=el, fix=fl)

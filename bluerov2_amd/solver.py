@@ -38,6 +38,14 @@ class NoDeviceError(RuntimeError):
     pass
 
 
+class ImuParams(C.Structure):
+    """brov_imu_params: the IMU/GPS stage's step h, gravity, the GPS divider, BROV_IMU_* flags and the noise seed"""
+    _fields_ = [("h", C.c_double), ("g", C.c_double), ("gps_every", C.c_int32), ("flags", C.c_int32), ("seed", C.c_uint64)]
+
+
+IMU_GPSV_ELAPSED = 1
+
+
 class _Opts(C.Structure):
     _fields_ = [("N", C.c_int32), ("qp_iter_max", C.c_int32), ("Ts", C.c_double), ("W", C.c_double * 16),
                 ("We", C.c_double * 12), ("lbu", C.c_double * 4), ("ubu", C.c_double * 4), ("qp_tol_mu", C.c_double),
@@ -142,6 +150,10 @@ def _protos(L):
         "brov_sensor_measure": [vp, vp], "brov_sensor_eval_host": [vp, C.c_int64, dp, dp, C.POINTER(C.c_int32)],
         "brov_sensor_get_measurement_host": [vp, dp], "brov_sensor_get_stats_host": [vp, C.POINTER(C.c_int32), dp, C.POINTER(C.c_int64)],
         "brov_sensor_reset_stats": [vp], "brov_sensor_last_seconds": [vp, dp],
+        "brov_imu_set_host": [vp, C.POINTER(ImuParams), dp, dp, dp], "brov_imu_off": [vp], "brov_imu_enabled": [vp], "brov_imu_restart": [vp, vp],
+        "brov_imu_eval_host": [vp, C.c_int64, dp, dp, dp, C.POINTER(C.c_int32), dp, dp, dp, dp, C.POINTER(C.c_int32)],
+        "brov_imu_get_host": [vp, dp, dp, dp, dp, C.POINTER(C.c_int32)], "brov_imu_get_stats_host": [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int64)],
+        "brov_imu_reset_stats": [vp], "brov_imu_last_seconds": [vp, dp],
         "brov_current_constant_host": [vp, dp], "brov_current_table_host": [vp, dp, C.c_int, dp],
         "brov_current_gauss_markov_host": [vp, C.c_uint64, dp, dp, dp, dp, dp, C.c_double], "brov_current_off": [vp], "brov_current_mode": [vp],
         "brov_current_eval_host": [vp, C.c_int64, dp], "brov_current_get_state_host": [vp, dp], "brov_current_set_state_host": [vp, dp],
@@ -158,7 +170,7 @@ def _protos(L):
         "brov_rotor_get_state_host": [vp, dp], "brov_rotor_last_host": [vp, dp, dp], "brov_rotor_get_stats_host": [vp, dp, C.POINTER(C.c_int64)],
         "brov_rotor_get_coeffs_host": [vp, dp, dp, dp], "brov_rotor_eval_host": [vp, dp, dp, dp, dp], "brov_rotor_last_seconds": [vp, dp],
     })
-    _bind(L, {"brov_thruster_default_matrix": [dp]}, None)
+    _bind(L, {"brov_thruster_default_matrix": [dp], "brov_imu_default_params": [C.POINTER(ImuParams)]}, None)
 
 
 def _dp(a):
@@ -934,6 +946,68 @@ class BatchSolver(_Handle):
         """duration of the measure kernel's last launch (HIP events)"""
         sec = C.c_double(0.0)
         self._chk(self._L.brov_sensor_last_seconds(self._h, C.byref(sec)), "sensor_last_seconds")
+        return sec.value
+
+    # ---- IMU/GPS stage behind the plant: what the error-state filter reads, at the sensors' own rates (brov_imu_*) ----------------------
+    def set_imu(self, h, gps_every=1, seed=0, sigma=None, bias=None, dropout=None, g=9.81, flags=0):
+        """from now on every plant step (whose dt must be exactly h) is followed by a sample of the IMU/GPS stage from the TRUE state: the
+        mean specific force of the step and the body rates, and, where the index is a multiple of gps_every and the fix is not dropped, a
+        position fix, its differenced velocity and an attitude (include/bluerov2_nmpc_imu.h has the formulas).  The stage restarts.
+            sigma    scalar, [12] or [B, 12]: accelerometer, gyro, GPS position, attitude (None: 0)
+            bias     scalar, [6] or [B, 6]: accelerometer, gyro (None: 0)
+            dropout  scalar or [B] in [0, 1]: probability that a due fix is dropped (None: 0)
+            flags    IMU_GPSV_ELAPSED: gps_v divides by the time since the last fix taken, not by the nominal period"""
+        def rows(v, shape):
+            return None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), shape))
+        par = ImuParams(float(h), float(g), int(gps_every), int(flags), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        self._chk(self._L.brov_imu_set_host(self._h, C.byref(par), _dp(rows(sigma, (self.B, 12))), _dp(rows(bias, (self.B, 6))),
+                                            _dp(rows(dropout, (self.B,)))), "set_imu")
+
+    def imu_off(self):
+        """no launch behind a plant step any more; the statistics stay readable"""
+        self._chk(self._L.brov_imu_off(self._h), "imu_off")
+
+    def imu_enabled(self):
+        return bool(self._L.brov_imu_enabled(self._h))
+
+    def imu_restart(self, stream=0):
+        """a forced restart at the current index: the acceleration is gravity alone, a fix is taken with gps_v = 0"""
+        self._chk(self._L.brov_imu_restart(self._h, C.c_void_p(stream)), "imu_restart")
+
+    def imu_eval(self, index, x, v_prev, gps_p_last, m_last):
+        """dict(imu [B, 6], gps_p [B, 3], gps_v [B, 3], q_meas [B, 4], fix [B] int32): the stage alone at `index` for the states `x` [B, 12],
+        the previous inertial velocity [B, 3], the last fix [B, 3] and its index [B] (< 0: none); without a fix the last three are zeros.
+        Moves nothing, touches no statistic"""
+        ml = _arr(m_last, (self.B,), np.int32)
+        o = dict(imu=np.empty((self.B, 6)), gps_p=np.empty((self.B, 3)), gps_v=np.empty((self.B, 3)), q_meas=np.empty((self.B, 4)),
+                 fix=np.zeros(self.B, dtype=np.int32))
+        ip = C.POINTER(C.c_int32)
+        self._chk(self._L.brov_imu_eval_host(self._h, int(index), _dp(_arr(x, (self.B, NX))), _dp(_arr(v_prev, (self.B, 3))),
+                                             _dp(_arr(gps_p_last, (self.B, 3))), ml.ctypes.data_as(ip), _dp(o["imu"]), _dp(o["gps_p"]),
+                                             _dp(o["gps_v"]), _dp(o["q_meas"]), o["fix"].ctypes.data_as(ip)), "imu_eval")
+        return o
+
+    def imu(self):
+        """dict(imu, gps_p, gps_v, q_meas, fix): the last sample and its flags as the stage holds them"""
+        o = dict(imu=np.empty((self.B, 6)), gps_p=np.empty((self.B, 3)), gps_v=np.empty((self.B, 3)), q_meas=np.empty((self.B, 4)),
+                 fix=np.zeros(self.B, dtype=np.int32))
+        self._chk(self._L.brov_imu_get_host(self._h, _dp(o["imu"]), _dp(o["gps_p"]), _dp(o["gps_v"]), _dp(o["q_meas"]),
+                                            o["fix"].ctypes.data_as(C.POINTER(C.c_int32))), "imu")
+        return o
+
+    def imu_stats(self):
+        """dict(samples, fixes, dropped: [B] int32 each, of the regular refreshes; refreshes: plant steps behind which the stage ran)"""
+        st, n = np.zeros((self.B, 3), dtype=np.int32), C.c_int64(0)
+        self._chk(self._L.brov_imu_get_stats_host(self._h, st.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n)), "imu_stats")
+        return dict(samples=st[:, 0].copy(), fixes=st[:, 1].copy(), dropped=st[:, 2].copy(), refreshes=int(n.value))
+
+    def imu_reset_stats(self):
+        self._chk(self._L.brov_imu_reset_stats(self._h), "imu_reset_stats")
+
+    def imu_last_seconds(self):
+        """duration of the stage's last refresh (HIP events)"""
+        sec = C.c_double(0.0)
+        self._chk(self._L.brov_imu_last_seconds(self._h, C.byref(sec)), "imu_last_seconds")
         return sec.value
 
     # ---- iterate ----------------------------------------------------------------------------------------------

@@ -1004,6 +1004,9 @@ int brov_clearance_dev_slices(const brov_fleet* f);                   /* the cou
  * nodelet, brov_eskf_* (DESIGN.md section 4.4b).  Declared in bluerov2_nmpc_eskf.h, which this header includes here.
  * ------------------------------------------------------------------------------------------------------------------- */
 #include "bluerov2_nmpc_eskf.h"
+/* The IMU/GPS stage of the solver's plant, brov_imu_*, and the filter at its sensors' own rates: the masked tick brov_imu_eskf_tick_*, the hand-off
+ * brov_imu_eskf_tick_from_solver and the loop brov_closed_loop_eskf (DESIGN.md sections 4.9h and 4.4c).  Declared in bluerov2_nmpc_imu.h. */
+#include "bluerov2_nmpc_imu.h"
 
 #ifdef __cplusplus
 }
