@@ -8,7 +8,8 @@ from .solver import (BatchSolver, SolverOptions, RESULT_DTYPE, P_NOMINAL, build_
                      NoDeviceError, thrust_allocation, PATH_AUTO, PATH_STREAMING, PATH_FUSED, PATH_WINDOWED,
                      WRENCH_OFF, WRENCH_CONSTANT, WRENCH_PERIODIC, WRENCH_TABLE,
                      CURRENT_OFF, CURRENT_CONSTANT, CURRENT_TABLE, CURRENT_GAUSS_MARKOV, current_from_angles, rotor_coeffs,
-                     CORIOLIS_RIGID, CORIOLIS_ADDED, ImuParams, IMU_GPSV_ELAPSED)
+                     CORIOLIS_RIGID, CORIOLIS_ADDED, ImuParams, IMU_GPSV_ELAPSED, RangeParams, InspectParams,
+                     INSPECT_STATE_DTYPE, INSPECT_STATS_DTYPE, INSPECT_SHARED_PID, INSPECT_FLOAT_YAW, RANGE_MAX_BOXES)
 
 from .ekf import BatchEkf, EkfParams  # noqa: F401,E402
 from .eskf import BatchEskf, EskfParams, closed_loop_eskf  # noqa: F401,E402
@@ -21,4 +22,5 @@ __all__ = ["SolverGroup", "GATHER_RECORDS", "GATHER_PACKED", "rccl_version", "un
            "NoDeviceError", "thrust_allocation", "PATH_AUTO", "PATH_STREAMING", "PATH_FUSED", "PATH_WINDOWED",
            "WRENCH_OFF", "WRENCH_CONSTANT", "WRENCH_PERIODIC", "WRENCH_TABLE",
            "CURRENT_OFF", "CURRENT_CONSTANT", "CURRENT_TABLE", "CURRENT_GAUSS_MARKOV", "current_from_angles", "rotor_coeffs", "CORIOLIS_RIGID", "CORIOLIS_ADDED",
-           "ImuParams", "IMU_GPSV_ELAPSED", "closed_loop_eskf"]
+           "ImuParams", "IMU_GPSV_ELAPSED", "closed_loop_eskf", "RangeParams", "InspectParams", "INSPECT_STATE_DTYPE", "INSPECT_STATS_DTYPE",
+           "INSPECT_SHARED_PID", "INSPECT_FLOAT_YAW", "RANGE_MAX_BOXES"]

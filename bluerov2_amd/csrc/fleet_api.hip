@@ -385,6 +385,11 @@ static int plant_modes_ok(const brov_fleet* f, const char* who) {
                       "which that stage never samples";
         return BROV_ERR_ARG;
     }
+    if (brov_inspect_enabled(f->s) == 1) {
+        g_fleet_err = std::string(who) + ": the inspection controller of the solver is on (brov_inspect_set_host); it writes the records the fleet "
+                      "selects among";
+        return BROV_ERR_ARG;
+    }
     if (brov_dist6_enabled(f->s) == 1) {
         g_fleet_err = std::string(who) + ": the 6-disturbance variant is on (brov_enable_dist6); the fleet's plant integrates the shipped model";
         return BROV_ERR_ARG;

@@ -944,6 +944,66 @@ extern "C" int brov_imu_last_seconds(brov_solver* s, double* seconds) {
     HIPCHK(hipSetDevice(s->device));
     return s->plant.im.last_seconds(seconds, sensor_ctx(s, "brov_imu_last_seconds"));
 }
+// ---- range stage and inspection controller (inspect_kernel.hip): thin forwards to their host side, inspect_source.hpp, with sensor_wait: a tick
+// runs on whatever stream it was given ---------------------------------------------------------------------------------------------------------
+extern "C" void brov_range_default_params(brov_range_params* p) {
+    if (p) *p = InspectSource::default_range();
+}
+extern "C" double brov_range_focal(double width, double hfov) { return InspectSource::focal(width, hfov); }
+extern "C" int brov_range_set_scene_host(brov_solver* s, int32_t n, const double* lo, const double* hi) {
+    return s ? s->plant.in.set_scene_host(n, lo, hi, sensor_ctx(s, "brov_range_set_scene_host")) : no_solver("brov_range_set_scene_host");
+}
+extern "C" int brov_range_set_host(brov_solver* s, const brov_range_params* p, const double* sigma) {
+    return s ? s->plant.in.set_range_host(p, sigma, sensor_ctx(s, "brov_range_set_host")) : no_solver("brov_range_set_host");
+}
+extern "C" int brov_range_eval_host(brov_solver* s, int64_t m, const double* x, double* range, int32_t* hits, double* rot, double* depth) {
+    if (!s) return no_solver("brov_range_eval_host");
+    return s->plant.in.range_eval_host(m, x, range, hits, rot, depth, s->last_stream, sensor_ctx(s, "brov_range_eval_host"));
+}
+extern "C" int brov_range_last_seconds(brov_solver* s, double* seconds) {
+    if (!s) return no_solver("brov_range_last_seconds");
+    HIPCHK(hipSetDevice(s->device));
+    return s->plant.in.range_last_seconds(seconds, sensor_ctx(s, "brov_range_last_seconds"));
+}
+extern "C" void brov_inspect_default_params(brov_inspect_params* p) {
+    if (p) *p = InspectSource::default_inspect();
+}
+extern "C" int brov_inspect_set_host(brov_solver* s, const brov_inspect_params* p) {
+    return s ? s->plant.in.set_host(p, sensor_ctx(s, "brov_inspect_set_host")) : no_solver("brov_inspect_set_host");
+}
+extern "C" int brov_inspect_off(brov_solver* s) { return s ? s->plant.in.set_off() : no_solver("brov_inspect_off"); }
+extern "C" int brov_inspect_enabled(const brov_solver* s) { return s && s->plant.in.on ? 1 : 0; }
+extern "C" int brov_inspect_reset(brov_solver* s) {
+    return s ? s->plant.in.reset(sensor_ctx(s, "brov_inspect_reset")) : no_solver("brov_inspect_reset");
+}
+extern "C" int brov_inspect_eval_host(brov_solver* s, const brov_inspect_state* state_in, const double* range, const double* z, const double* psi,
+                                      brov_inspect_state* state_out, brov_result* rec, brov_inspect_stats* stats) {
+    if (!s) return no_solver("brov_inspect_eval_host");
+    return s->plant.in.eval_host(state_in, range, z, psi, state_out, rec, stats, s->last_stream, sensor_ctx(s, "brov_inspect_eval_host"));
+}
+extern "C" int brov_inspect_get_state_host(brov_solver* s, brov_inspect_state* state, double* range) {
+    return s ? s->plant.in.get_state_host(state, range, sensor_ctx(s, "brov_inspect_get_state_host")) : no_solver("brov_inspect_get_state_host");
+}
+extern "C" int brov_inspect_get_stats_host(brov_solver* s, brov_inspect_stats* stats) {
+    return s ? s->plant.in.get_stats_host(stats, sensor_ctx(s, "brov_inspect_get_stats_host")) : no_solver("brov_inspect_get_stats_host");
+}
+extern "C" int brov_inspect_reset_stats(brov_solver* s) {
+    return s ? s->plant.in.reset_stats(sensor_ctx(s, "brov_inspect_reset_stats")) : no_solver("brov_inspect_reset_stats");
+}
+extern "C" int brov_inspect_last_seconds(brov_solver* s, double* seconds) {
+    if (!s) return no_solver("brov_inspect_last_seconds");
+    HIPCHK(hipSetDevice(s->device));
+    return s->plant.in.last_seconds(seconds, sensor_ctx(s, "brov_inspect_last_seconds"));
+}
+extern "C" int brov_inspect_step(brov_solver* s, void* stream) {
+    if (!s) return no_solver("brov_inspect_step");
+    if (int rc = s->plant.in.steps_ok(s->plant.tick(), 1, s->plant.dl.on ? s->plant.dl.ahead() : 0, sensor_ctx(s, "brov_inspect_step"))) return rc;
+    HIPCHK(hipSetDevice(s->device));
+    if (int rc = order_behind_last(s, (hipStream_t)stream)) return rc;
+    s->plant.in.step(s->x0, s->plant.controller_state(), s->res, s->plant.tick(), (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return BROV_OK;
+}
 // ---- delay stage between the controller's commands and the plant (delay_kernel.hip): thin forwards to its host side, delay_source.hpp, with
 // sensor_wait: the predictor runs on whatever stream a solve was given -----------------------------------------------------------------------
 extern "C" int brov_delay_set_host(brov_solver* s, const int32_t* delay, int32_t comp, double dt_pred, int32_t observer_applied) {
@@ -1329,6 +1389,35 @@ extern "C" int brov_closed_loop_eskf(brov_solver* s, brov_eskf* e, int ticks, in
         if (rc == BROV_OK) sub(brov_eskf_apply_to_solver(e, s, st));
     }
     return L.deliver(finish_loop(st, rc, g_err, ""), g_err, "brov_closed_loop_eskf: ");
+}
+
+// The inspection loop: per tick brov_inspect_step and brov_plant_step, on one stream, one host wait at the end.  Columns: the states behind the
+// start state, the commanded input, the mission status, the range
+extern "C" int brov_closed_loop_inspect(brov_solver* s, int ticks, double dt, int substeps, double* u_log, double* x_log, int32_t* st_log,
+                                        double* r_log) {
+    const char* who = "brov_closed_loop_inspect";
+    if (!s) return no_solver(who);
+    if (ticks < 1 || !(dt > 0.0) || substeps < 1) { g_err = "brov_closed_loop_inspect: bad argument (needs ticks >= 1, dt > 0, substeps >= 1)"; return BROV_ERR_ARG; }
+    if (int rc = s->plant.in.steps_ok(s->plant.tick(), ticks, s->plant.dl.on ? s->plant.dl.ahead() : 0, call_ctx(s, who))) return rc;
+    if (int rc = s->plant.dt_ok(dt, call_ctx(s, who))) return rc;
+    if (int rc = s->plant.steps_ok(ticks, call_ctx(s, who))) return rc;
+    HIPCHK(hipSetDevice(s->device));
+    hipStream_t st = s->last_stream;
+    LoopLog L;
+    const int log_x = L.column(12, x_log, 1), log_u = L.column(4, u_log), log_st = L.column(1, st_log), log_r = L.column(1, r_log);
+    int rc = L.alloc(s->B, ticks, g_err, "brov_closed_loop_inspect: ");
+    if (rc == BROV_OK) rc = L.init(s->x0, -1, st, g_err, "brov_closed_loop_inspect: ");
+    const InspectSource& in = s->plant.in;
+    for (int k = 0; k < ticks && rc == BROV_OK; k++) {
+        s->plant.in.step(s->x0, s->plant.controller_state(), s->res, s->plant.tick(), st);
+        if (int32_t* row = L.row<int32_t>(log_st, k))
+            if (hipMemcpyAsync(row, in.dev.status, s->B * sizeof(int32_t), hipMemcpyDeviceToDevice, st) != hipSuccess) rc = BROV_ERR_HIP;
+        if (double* row = L.row<double>(log_r, k))
+            if (hipMemcpyAsync(row, in.dev.range, s->B * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess) rc = BROV_ERR_HIP;
+        s->plant.ensure_params(st);
+        s->plant.step(dt, substeps, L.row<double>(log_x, k), L.row<double>(log_u, k), nullptr, st);
+    }
+    return L.deliver(finish_loop(st, rc, g_err, ""), g_err, "brov_closed_loop_inspect: ");
 }
 
 namespace brov {

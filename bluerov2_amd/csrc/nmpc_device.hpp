@@ -246,6 +246,27 @@ void launch_imu_measure(const ImuPar& P, const ImuDev& D, const ImuOut& O, int B
 void launch_imu_eval(const ImuPar& P, const ImuDev& D, const ImuOut& O, int B, long long m, const double* x, const double* vprev, const double* plast,
                      const int32_t* mlast, hipStream_t st);
 
+// range stage and inspection controller (inspect_kernel.hip; include/bluerov2_nmpc_inspect.h, brov_range_*, brov_inspect_*)
+struct RangeScene {               // shared by the batch and wave-uniform: passed by value in the kernel arguments, read with scalar loads
+    double lo[BROV_RANGE_MAX_BOXES][3], hi[BROV_RANGE_MAX_BOXES][3];
+    int32_t n;
+};
+struct InspectDev {               // per instance
+    brov_inspect_state* state = nullptr;   // [B]
+    brov_inspect_stats* stats = nullptr;   // [B]
+    double* range = nullptr;               // [B] the last range
+    int32_t* status = nullptr;             // [B] the mission status behind the last tick
+};
+// the range stage alone for the states x [B][12] at index m: range [B], hits [B], rot [B][9] or nullptr, depth [B][roi * roi] or nullptr
+void launch_range_eval(const brov_range_params& P, const RangeScene& S, const double* sigma, int B, long long m, const double* x, double* range,
+                       int32_t* hits, double* rot, double* depth, hipStream_t st);
+// the controller alone: one tick from state_in on range, z, psi [B] into state_out and rec; stats [B] in and out, or nullptr
+void launch_inspect_eval(const brov_inspect_params& C, int B, const brov_inspect_state* state_in, const double* range, const double* z,
+                         const double* psi, brov_inspect_state* state_out, brov_result* rec, brov_inspect_stats* stats, hipStream_t st);
+// one tick of the loop: rays from the true state x at index m, the controller on z and psi of y (what the controller sees), the record into res
+void launch_inspect_tick(const brov_range_params& P, const RangeScene& S, const double* sigma, const brov_inspect_params& C, const InspectDev& D,
+                         int B, long long m, const double* x, const double* y, brov_result* res, hipStream_t st);
+
 // delay stage of the plant (delay_kernel.hip; include/bluerov2_nmpc.h, brov_delay_*): a ring [B][D][10] of the last D commanded records
 // (u0[4] | thrust[6]), indexed by the stage's own step count n.
 // step n of the stage: applied[b] = res[b] with u0 and thrust of step n - delay[b] (zeros before the first), res[b]'s own into slot n mod D;

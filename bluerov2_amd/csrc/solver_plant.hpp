@@ -8,6 +8,7 @@
 #include "current_source.hpp"
 #include "delay_source.hpp"
 #include "imu_source.hpp"
+#include "inspect_source.hpp"
 #include "rotor_source.hpp"
 #include "sensor_source.hpp"
 #include "thruster_source.hpp"
@@ -39,14 +40,15 @@ struct SolverPlant {
     CoriolisSource co;             // Coriolis stage (brov_coriolis_*): the forces the OCP model drops, its buffers allocated on first use
     SensorSource sn;               // sensor stage (brov_sensor_*): the measured state, its buffers allocated on first use
     ImuSource im;                  // IMU/GPS stage (brov_imu_*): what the error-state filter reads, from the true state, its buffers allocated on first use
+    InspectSource in;              // range stage and inspection controller (brov_range_*, brov_inspect_*): writes the records in the solver's place, its buffers allocated on first use
     DelaySource dl;                // delay stage (brov_delay_*): the queue of commanded records and the predictor, its buffers allocated on first use
     RotorSource ro;                // rotor stage (brov_rotor_*): first-order dynamics of the thrusters behind the delay, its buffers allocated on first use
 
     void init(int B_, int N_, double* x0_, const brov_result* res_, const double* par_, double* const* par_rp_, const bool* dist6_) {
         B = B_; N = N_; x0 = x0_; res = res_; par = par_; par_rp = par_rp_; dist6 = dist6_;
-        wr.B = th.B = cu.B = co.B = sn.B = im.B = dl.B = ro.B = (size_t)B_;
+        wr.B = th.B = cu.B = co.B = sn.B = im.B = in.B = dl.B = ro.B = (size_t)B_;
     }
-    void destroy() { wr.destroy(); th.destroy(); cu.destroy(); co.destroy(); sn.destroy(); im.destroy(); dl.destroy(); ro.destroy(); }
+    void destroy() { wr.destroy(); th.destroy(); cu.destroy(); co.destroy(); sn.destroy(); im.destroy(); in.destroy(); dl.destroy(); ro.destroy(); }
 
     long long tick() const { return wr.tick; }   // plant steps so far (brov_plant_wrench_seek sets it): the wrench's tick, the sensor's index
     // may the next `n` steps run?  The wrench's generator, then the current's draws, then the sensor's index
@@ -56,10 +58,11 @@ struct SolverPlant {
         if (int rc = sn.steps_ok(wr.tick, n, c)) return rc;
         return im.steps_ok(wr.tick, n, c);
     }
-    // may a step of length `dt` run?  The rotor stage's coefficients hold for one step length alone, and so does the IMU stage's differencing
+    // may a step of length `dt` run?  The rotor stage's coefficients hold for one step length alone, and so do the IMU stage's differencing and the inspection controller's period
     int dt_ok(double dt, const CallCtx& c) const {
         if (int rc = ro.dt_ok(dt, c)) return rc;
-        return im.dt_ok(dt, c);
+        if (int rc = im.dt_ok(dt, c)) return rc;
+        return in.dt_ok(dt, c);
     }
     // no stage in force: the *_ticks kernels, which integrate the plant themselves and know none of them, can run the loop in one launch
     bool plain() const { return wr.off() && !th.on && cu.off() && !co.on && !sn.on && !im.on && !dl.on && !ro.on; }

@@ -14,6 +14,10 @@ import subprocess
 
 import numpy as np
 
+from . import inspect as _inspect
+from .inspect import (RangeParams, InspectParams, INSPECT_STATE_DTYPE, INSPECT_STATS_DTYPE, INSPECT_SHARED_PID,  # noqa: F401
+                      INSPECT_FLOAT_YAW, RANGE_MAX_BOXES)
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.join(HERE, "lib", "libbluerov2_nmpc.so")
 NX, NU, NP, NY = 12, 4, 16, 16
@@ -171,6 +175,7 @@ def _protos(L):
         "brov_rotor_get_coeffs_host": [vp, dp, dp, dp], "brov_rotor_eval_host": [vp, dp, dp, dp, dp], "brov_rotor_last_seconds": [vp, dp],
     })
     _bind(L, {"brov_thruster_default_matrix": [dp], "brov_imu_default_params": [C.POINTER(ImuParams)]}, None)
+    _inspect.protos(_bind, L)
 
 
 def _dp(a):
@@ -1009,6 +1014,114 @@ class BatchSolver(_Handle):
         sec = C.c_double(0.0)
         self._chk(self._L.brov_imu_last_seconds(self._h, C.byref(sec)), "imu_last_seconds")
         return sec.value
+
+    # ---- range stage and inspection controller: the reference's bridge demo (brov_range_*, brov_inspect_*) ---------------------------------
+    def set_range_scene(self, lo, hi):
+        """the scene of the range stage: n <= RANGE_MAX_BOXES axis-aligned world-frame boxes, lo and hi [n, 3], shared by the batch"""
+        lo, hi = np.ascontiguousarray(lo, dtype=np.float64).reshape(-1, 3), np.ascontiguousarray(hi, dtype=np.float64).reshape(-1, 3)
+        if lo.shape != hi.shape:
+            raise ValueError("lo and hi must have the same shape [n, 3]")
+        self._chk(self._L.brov_range_set_scene_host(self._h, len(lo), _dp(lo), _dp(hi)), "set_range_scene")
+
+    def set_range(self, params=None, sigma=None, **kw):
+        """the camera (RangeParams; None: the defaults, with the fields given as keywords changed; mount=(x, y, z)) and the standard deviation
+        of the range noise, a scalar or [B] (None: 0)"""
+        p = params if params is not None else _inspect.default_range_params()
+        for k, v in kw.items():
+            if k == "mount":
+                p.mount[:] = [float(a) for a in v]
+            else:
+                setattr(p, k, v)
+        sg = None if sigma is None else np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, dtype=np.float64), (self.B,)))
+        self._chk(self._L.brov_range_set_host(self._h, C.byref(p), _dp(sg)), "set_range")
+        self._roi = int(p.roi)
+
+    def range_eval(self, index, x, rot=False, depth=False):
+        """dict(range [B], hits [B] int32, and with rot / depth: rot [B, 9], depth [B, roi * roi] with 0.0 where a ray has no return): the
+        range stage alone at `index` for the states `x` [B, 12].  Moves nothing"""
+        roi = getattr(self, "_roi", 40)
+        o = dict(range=np.empty(self.B), hits=np.zeros(self.B, dtype=np.int32))
+        if rot:
+            o["rot"] = np.empty((self.B, 9))
+        if depth:
+            o["depth"] = np.empty((self.B, roi * roi))
+        self._chk(self._L.brov_range_eval_host(self._h, int(index), _dp(_arr(x, (self.B, NX))), _dp(o["range"]),
+                                               o["hits"].ctypes.data_as(C.POINTER(C.c_int32)), _dp(o.get("rot")), _dp(o.get("depth"))), "range_eval")
+        return o
+
+    def range_last_seconds(self):
+        sec = C.c_double(0.0)
+        self._chk(self._L.brov_range_last_seconds(self._h, C.byref(sec)), "range_last_seconds")
+        return sec.value
+
+    def set_inspect(self, params=None, **kw):
+        """the inspection controller comes into force with a fresh state and statistics (InspectParams; None: the node's values, with the
+        fields given as keywords changed; gains=[9]).  From now on inspect_step writes the records a solve would write"""
+        p = params if params is not None else _inspect.default_inspect_params()
+        for k, v in kw.items():
+            if k == "gains":
+                p.gains[:] = [float(a) for a in v]
+            else:
+                setattr(p, k, v)
+        self._chk(self._L.brov_inspect_set_host(self._h, C.byref(p)), "set_inspect")
+
+    def inspect_off(self):
+        self._chk(self._L.brov_inspect_off(self._h), "inspect_off")
+
+    def inspect_enabled(self):
+        return bool(self._L.brov_inspect_enabled(self._h))
+
+    def inspect_reset(self):
+        """the state of the node's constructor, k = 0; the statistics stay"""
+        self._chk(self._L.brov_inspect_reset(self._h), "inspect_reset")
+
+    def inspect_eval(self, state, range_, z, psi, stats=None):
+        """(state_out [B] of INSPECT_STATE_DTYPE, records [B] of RESULT_DTYPE, stats_out or None): the controller alone, one tick from
+        `state` on the given range, z and psi [B] with the parameters in force; `stats` [B] of INSPECT_STATS_DTYPE moves along.  Moves nothing"""
+        si = _arr(state, (self.B,), INSPECT_STATE_DTYPE)
+        so, rec = np.zeros(self.B, dtype=INSPECT_STATE_DTYPE), np.zeros(self.B, dtype=RESULT_DTYPE)
+        st = None if stats is None else _arr(stats, (self.B,), INSPECT_STATS_DTYPE).copy()
+        self._chk(self._L.brov_inspect_eval_host(self._h, C.c_void_p(si.ctypes.data), _dp(_arr(range_, (self.B,))), _dp(_arr(z, (self.B,))),
+                                                 _dp(_arr(psi, (self.B,))), C.c_void_p(so.ctypes.data), C.c_void_p(rec.ctypes.data),
+                                                 None if st is None else C.c_void_p(st.ctypes.data)), "inspect_eval")
+        return so, rec, st
+
+    def inspect_state(self):
+        """(state [B] of INSPECT_STATE_DTYPE, the last range [B])"""
+        s, r = np.zeros(self.B, dtype=INSPECT_STATE_DTYPE), np.empty(self.B)
+        self._chk(self._L.brov_inspect_get_state_host(self._h, C.c_void_p(s.ctypes.data), _dp(r)), "inspect_state")
+        return s, r
+
+    def inspect_stats(self):
+        """[B] of INSPECT_STATS_DTYPE: ticks per status, rounds, visits of the "failed" branch, first tick with the mission completed,
+        the sum of (range - safety_dis)^2 over the status-0 ticks, the smallest non-zero range"""
+        t = np.zeros(self.B, dtype=INSPECT_STATS_DTYPE)
+        self._chk(self._L.brov_inspect_get_stats_host(self._h, C.c_void_p(t.ctypes.data)), "inspect_stats")
+        return t
+
+    def inspect_reset_stats(self):
+        self._chk(self._L.brov_inspect_reset_stats(self._h), "inspect_reset_stats")
+
+    def inspect_last_seconds(self):
+        sec = C.c_double(0.0)
+        self._chk(self._L.brov_inspect_last_seconds(self._h, C.byref(sec)), "inspect_last_seconds")
+        return sec.value
+
+    def inspect_step(self, stream=0):
+        """one tick of the controller: rays from the true state at the plant's tick counter, then the record into results()"""
+        self._chk(self._L.brov_inspect_step(self._h, C.c_void_p(stream)), "inspect_step")
+
+    def closed_loop_inspect(self, ticks, dt=0.05, substeps=1, log=True):
+        """ticks x (inspect_step -> plant_step) on the device, one host wait; returns (u_log [ticks, B, 4], x_log [ticks + 1, B, 12],
+        status_log [ticks, B] the mission status, range_log [ticks, B]) or None"""
+        if not log:
+            self._chk(self._L.brov_closed_loop_inspect(self._h, int(ticks), float(dt), int(substeps), None, None, None, None), "closed_loop_inspect")
+            return None
+        ul, xl = np.empty((ticks, self.B, NU)), np.empty((ticks + 1, self.B, NX))
+        sl, rl = np.empty((ticks, self.B), dtype=np.int32), np.empty((ticks, self.B))
+        self._chk(self._L.brov_closed_loop_inspect(self._h, int(ticks), float(dt), int(substeps), _dp(ul), _dp(xl),
+                                                   sl.ctypes.data_as(C.POINTER(C.c_int32)), _dp(rl)), "closed_loop_inspect")
+        return ul, xl, sl, rl
 
     # ---- iterate ----------------------------------------------------------------------------------------------
     def set_iterate(self, x=None, u=None, pi=None, lam=None):

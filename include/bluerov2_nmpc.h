@@ -1007,6 +1007,10 @@ int brov_clearance_dev_slices(const brov_fleet* f);                   /* the cou
 /* The IMU/GPS stage of the solver's plant, brov_imu_*, and the filter at its sensors' own rates: the masked tick brov_imu_eskf_tick_*, the hand-off
  * brov_imu_eskf_tick_from_solver and the loop brov_closed_loop_eskf (DESIGN.md sections 4.9h and 4.4c).  Declared in bluerov2_nmpc_imu.h. */
 #include "bluerov2_nmpc_imu.h"
+/* The bridge-pier inspection loop of the reference's third demo: the depth camera's mean range against scene geometry, brov_range_*, the
+ * mission machine with its three PID loops, brov_inspect_*, and the loop brov_closed_loop_inspect.  Declared in
+ * bluerov2_nmpc_inspect.h. */
+#include "bluerov2_nmpc_inspect.h"
 
 #ifdef __cplusplus
 }
