@@ -365,6 +365,11 @@ static int plant_modes_ok(const brov_fleet* f, const char* who) {
                       "winner's command into force on the tick it was solved";
         return BROV_ERR_ARG;
     }
+    if (brov_curve_enabled(f->s) == 1) {
+        g_fleet_err = std::string(who) + ": the thrust-curve stage of the solver's plant is on (brov_curve_set_host); the fleet's plant turns "
+                      "every winner's command into force linearly";
+        return BROV_ERR_ARG;
+    }
     if (brov_current_mode(f->s) != BROV_CURRENT_OFF) {
         g_fleet_err = std::string(who) + ": an ocean current of the solver's plant is in force (brov_current_*); the fleet's plant integrates "
                       "the vehicles in still water";

@@ -147,7 +147,8 @@ SolverView solver_view(const brov_solver* s);
 const double* solver_measured_state(const brov_solver* s);
 // [B] the records whose thrusts brov_ekf_update_from_solver feeds the observer: the commanded ones, brov_results_device(), unless the solver's
 // delay stage is on with observer_applied set (brov_delay_set_host): then what the last plant step was given; the rotor stage with its
-// observer_applied set (brov_rotor_set_host) comes first: its applied records, the lagged ones
+// observer_applied set (brov_rotor_set_host) comes first: its applied records, the lagged ones;
+// the thrust-curve stage with its flag set (brov_curve_set_host) comes ahead of both: the delivered forces
 const brov_result* solver_observer_results(const brov_solver* s);
 // the solver's IMU/GPS stage (brov_imu_*) as brov_imu_eskf_tick_from_solver reads it: whether it is on, the step h it samples, whether a fix was due
 // at its last sample (else every flag is 0), and the DEVICE sample: imu [B][6], gps_p [B][3], gps_v [B][3], q_meas [B][4], fix [B]

@@ -1071,6 +1071,43 @@ extern "C" int brov_rotor_last_seconds(brov_solver* s, double* seconds) {
     HIPCHK(hipSetDevice(s->device));
     return s->plant.ro.last_seconds(seconds, sensor_ctx(s, "brov_rotor_last_seconds"));
 }
+// ---- thrust-curve stage around the rotor stage (curve_kernel.hip): thin forwards to its host side, curve_source.hpp, with sensor_wait ---------
+extern "C" void brov_curve_default_params(brov_curve_params* p) { CurveSource::default_params(p); }
+extern "C" int brov_curve_set_table_host(brov_solver* s, int32_t which, const double* x, const double* y, const double* amps, int32_t K) {
+    if (!s) return no_solver("brov_curve_set_table_host");
+    return s->plant.cv.set_table_host(which, x, y, amps, K, sensor_ctx(s, "brov_curve_set_table_host"));
+}
+extern "C" int brov_curve_get_table_host(brov_solver* s, int32_t which, double* x, double* y, double* slope, double* amps, double* amps_slope,
+                                         int32_t* K) {
+    if (!s) return no_solver("brov_curve_get_table_host");
+    return s->plant.cv.get_table_host(which, x, y, slope, amps, amps_slope, K, sensor_ctx(s, "brov_curve_get_table_host"));
+}
+extern "C" int brov_curve_set_host(brov_solver* s, const brov_curve_params* p, const double* eff) {
+    return s ? s->plant.cv.set_host(p, eff, sensor_ctx(s, "brov_curve_set_host")) : no_solver("brov_curve_set_host");
+}
+extern "C" int brov_curve_off(brov_solver* s) { return s ? s->plant.cv.set_off() : no_solver("brov_curve_off"); }
+extern "C" int brov_curve_enabled(const brov_solver* s) { return s && s->plant.cv.on ? 1 : 0; }
+extern "C" int brov_curve_reset(brov_solver* s) { return s ? s->plant.cv.reset(sensor_ctx(s, "brov_curve_reset")) : no_solver("brov_curve_reset"); }
+extern "C" int brov_curve_eval_host(brov_solver* s, int32_t part, const double* in, double* out, double* amps_out) {
+    if (!s) return no_solver("brov_curve_eval_host");
+    return s->plant.cv.eval_host(part, in, out, amps_out, s->last_stream, sensor_ctx(s, "brov_curve_eval_host"));
+}
+extern "C" int brov_curve_last_host(brov_solver* s, double* u0_applied, double* wanted, double* command, double* thrust) {
+    if (!s) return no_solver("brov_curve_last_host");
+    return s->plant.cv.last_host(u0_applied, wanted, command, thrust, sensor_ctx(s, "brov_curve_last_host"));
+}
+extern "C" int brov_curve_get_stats_host(brov_solver* s, double* err_sq, int32_t* dead_ticks, double* charge, int64_t* steps) {
+    if (!s) return no_solver("brov_curve_get_stats_host");
+    return s->plant.cv.get_stats_host(err_sq, dead_ticks, charge, steps, sensor_ctx(s, "brov_curve_get_stats_host"));
+}
+extern "C" int brov_curve_reset_stats(brov_solver* s) {
+    return s ? s->plant.cv.reset_stats(sensor_ctx(s, "brov_curve_reset_stats")) : no_solver("brov_curve_reset_stats");
+}
+extern "C" int brov_curve_last_seconds(brov_solver* s, double* command_s, double* thrust_s) {
+    if (!s) return no_solver("brov_curve_last_seconds");
+    HIPCHK(hipSetDevice(s->device));
+    return s->plant.cv.last_seconds(command_s, thrust_s, sensor_ctx(s, "brov_curve_last_seconds"));
+}
 // ---- the end of the forwards: from here on the plant is asked as one object ------------------------------------------------------------------
 extern "C" int brov_plant_step(brov_solver* s, double dt, int substeps, void* stream) {
     if (!s || !(dt > 0.0) || substeps < 1) return BROV_ERR_ARG;
@@ -1911,10 +1948,11 @@ extern "C" double* brov_x0_device(brov_solver* s) { return s ? s->x0 : nullptr; 
 namespace brov {
 // what the controller knows of the state: the measured state while the sensor stage is on, else the plant's own (for the observer and the estimator)
 const double* solver_measured_state(const brov_solver* s) { return s ? s->plant.controller_state() : nullptr; }
-// the records whose thrusts the observer is fed: the commanded ones, unless the rotor stage (the last to rewrite the record) or the delay
-// stage is on with observer_applied set
+// the records whose thrusts the observer is fed: the commanded ones, unless the thrust-curve stage (the last to rewrite the record), the
+// rotor stage or the delay stage is on with observer_applied set
 const brov_result* solver_observer_results(const brov_solver* s) {
     if (!s) return nullptr;
+    if (s->plant.cv.on && s->plant.cv.observer_applied) return s->plant.cv.applied;   // behind the rotors, or in their place
     if (s->plant.ro.on && s->plant.ro.observer_applied) return s->plant.ro.applied;
     return s->plant.dl.on && s->plant.dl.observer_applied ? s->plant.dl.applied : s->res;
 }

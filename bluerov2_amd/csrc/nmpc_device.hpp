@@ -291,4 +291,31 @@ void launch_rotor_shift(const brov_result* rec, brov_result* applied, const Roto
 void launch_rotor_eval(const RotorPar& P, const double* alpha, const double* beta, const double* commanded, const double* state, double* applied,
                        double* state_out, int B, hipStream_t st);
 
+// thrust-curve stage of the plant (curve_kernel.hip; include/bluerov2_nmpc_curve.h, brov_curve_*): the COMMAND part (pre-map, quantisation)
+// ahead of the rotor stage and the THRUST part (conversion curve, efficiency) behind it; with the rotor stage off both in one launch
+enum { CURVE_COMMAND = 1, CURVE_THRUST = 2, CURVE_BOTH = 3 };   // the parts a launch runs: the values of BROV_CURVE_PART_*
+struct CurvePar {                 // shared by the batch and wave-uniform: passed by value in the kernel arguments
+    int32_t kind, pre;            // BROV_CURVE_* / BROV_CURVE_PRE_*
+    int32_t Kc, Kp;               // knots of the curve table and of the pre table (0: none set)
+    int32_t amps, reserved_;      // the curve table carries the amps column
+    double quantum, inv_quantum, k, kl, kr, dl, dr;
+    double pre_poly[5];           // highest degree first
+};
+// a table as the kernels stage it in LDS, Ke = K rounded up to even so that every part starts on 16 bytes:
+//   x [Ke] | (y, slope) [K] pairs | (amps, amps_slope) [K] pairs, the last only with an amps column
+__host__ __device__ inline int curve_image_doubles(int K, bool amps) { return K <= 0 ? 0 : ((K + 1) & ~1) + 2 * K + (amps ? 2 * K : 0); }
+struct CurveBooks {               // [B][6] wanted, last_command, last_thrust, dead_ticks; [B] err_sq, charge
+    double *wanted, *last_command, *last_thrust, *err_sq, *charge;
+    int32_t* dead_ticks;
+};
+// one step of the part(s) `part`: applied[b] = rec[b] with thrust = the part's output and, where a bit of the six changed, u0 = the
+// allocation's left inverse of it.  COMMAND stores wanted and last_command; THRUST reads wanted, stores last_thrust and keeps err_sq,
+// dead_ticks and charge (dt: the plant step's); BOTH does both.  eff: [B][6]; img_curve / img_pre: the table images; ulog: [B][4] the
+// COMMANDED u0, or nullptr
+void launch_curve_shift(int part, const brov_result* rec, brov_result* applied, const CurvePar& P, const double* eff, const double* img_curve,
+                        const double* img_pre, const CurveBooks& bk, double dt, int B, double* ulog, hipStream_t st);
+// the part(s) alone: out [B][6] and amps_out [B][6] (zeros without an amps column or a THRUST part) for in [B][6]; moves nothing
+void launch_curve_eval(int part, const CurvePar& P, const double* eff, const double* img_curve, const double* img_pre, const double* in, double* out,
+                       double* amps_out, int B, hipStream_t st);
+
 }  // namespace brov

@@ -1,11 +1,12 @@
 // solver_plant.hpp -- the simulated plant of a brov_solver as one object: its true parameters, the world wrench it is under (WrenchSource),
-// the delay between the controller's commands and it (DelaySource), the rotors that answer them (RotorSource), the thruster stage ahead of it (ThrusterSource), the water it moves in (CurrentSource), the Coriolis forces on it (CoriolisSource), the sensor stage behind it (SensorSource), the IMU/GPS stage beside that (ImuSource), its step counter, and what the solver's entry
+// the delay between the controller's commands and it (DelaySource), the rotors that answer them (RotorSource), the thrust curve around those (CurveSource), the thruster stage ahead of it (ThrusterSource), the water it moves in (CurrentSource), the Coriolis forces on it (CoriolisSource), the sensor stage behind it (SensorSource), the IMU/GPS stage beside that (ImuSource), its step counter, and what the solver's entry
 // points ask of them: which state the controller sees, whether the next n steps may run, whether the loop's own kernels can integrate it, and
 // the one place that picks the plant kernel.  What it shares with the controller stays the solver's: non-owning pointers, given once at
-// create.  The public brov_plant_* / brov_delay_* / brov_rotor_* / brov_thruster_* / brov_current_* / brov_coriolis_* / brov_sensor_* forwards stay in nmpc_api.hip.  Host code only, header only.
+// create.  The public brov_plant_* / brov_delay_* / brov_rotor_* / brov_curve_* / brov_thruster_* / brov_current_* / brov_coriolis_* / brov_sensor_* forwards stay in nmpc_api.hip.  Host code only, header only.
 #pragma once
 #include "coriolis_source.hpp"
 #include "current_source.hpp"
+#include "curve_source.hpp"
 #include "delay_source.hpp"
 #include "imu_source.hpp"
 #include "inspect_source.hpp"
@@ -43,12 +44,13 @@ struct SolverPlant {
     InspectSource in;              // range stage and inspection controller (brov_range_*, brov_inspect_*): writes the records in the solver's place, its buffers allocated on first use
     DelaySource dl;                // delay stage (brov_delay_*): the queue of commanded records and the predictor, its buffers allocated on first use
     RotorSource ro;                // rotor stage (brov_rotor_*): first-order dynamics of the thrusters behind the delay, its buffers allocated on first use
+    CurveSource cv;                // thrust-curve stage (brov_curve_*): command map and ESC steps ahead of the rotors, conversion curve and efficiency behind them, its buffers allocated on first use
 
     void init(int B_, int N_, double* x0_, const brov_result* res_, const double* par_, double* const* par_rp_, const bool* dist6_) {
         B = B_; N = N_; x0 = x0_; res = res_; par = par_; par_rp = par_rp_; dist6 = dist6_;
-        wr.B = th.B = cu.B = co.B = sn.B = im.B = in.B = dl.B = ro.B = (size_t)B_;
+        wr.B = th.B = cu.B = co.B = sn.B = im.B = in.B = dl.B = ro.B = cv.B = (size_t)B_;
     }
-    void destroy() { wr.destroy(); th.destroy(); cu.destroy(); co.destroy(); sn.destroy(); im.destroy(); in.destroy(); dl.destroy(); ro.destroy(); }
+    void destroy() { wr.destroy(); th.destroy(); cu.destroy(); co.destroy(); sn.destroy(); im.destroy(); in.destroy(); dl.destroy(); ro.destroy(); cv.destroy(); }
 
     long long tick() const { return wr.tick; }   // plant steps so far (brov_plant_wrench_seek sets it): the wrench's tick, the sensor's index
     // may the next `n` steps run?  The wrench's generator, then the current's draws, then the sensor's index
@@ -65,7 +67,7 @@ struct SolverPlant {
         return in.dt_ok(dt, c);
     }
     // no stage in force: the *_ticks kernels, which integrate the plant themselves and know none of them, can run the loop in one launch
-    bool plain() const { return wr.off() && !th.on && cu.off() && !co.on && !sn.on && !im.on && !dl.on && !ro.on; }
+    bool plain() const { return wr.off() && !th.on && cu.off() && !co.on && !sn.on && !im.on && !dl.on && !ro.on && !cv.on; }
 
     // what the controller knows of the state: the measured state while the sensor stage is on, else the true one
     const double* controller_state() const { return sn.on ? sn.ymeas : x0; }
@@ -107,7 +109,11 @@ struct SolverPlant {
         const brov_result* rec = res;
         if (dl.on) { dl.shift(res, ulog, st); rec = dl.applied; ulog = nullptr; }
         // rotor stage on: behind the delay, ahead of the thruster stage; it lags the record that arrives and logs the commanded input likewise
+        // thrust-curve stage on: its COMMAND part ahead of the rotors and its THRUST part behind them; rotor stage off: both in one launch
+        if (cv.on && !ro.on) { cv.both(rec, dt, ulog, st); rec = cv.applied; ulog = nullptr; }
+        if (cv.on && ro.on) { cv.command(rec, ulog, st); rec = cv.applied_cmd; ulog = nullptr; }
         if (ro.on) { ro.shift(rec, ulog, st); rec = ro.applied; ulog = nullptr; }
+        if (cv.on && ro.on) { cv.thrust(rec, dt, st); rec = cv.applied; }
         if (co.on) {
             if (th.on) (void)th.timer.start(st);     // the thruster stage's timing and step count, as its own step() keeps them ...
             if (!cu.off()) (void)cu.timer.start(st);   // ... and the current's, as its own

@@ -50,6 +50,29 @@ class ImuParams(C.Structure):
 IMU_GPSV_ELAPSED = 1
 
 
+class CurveParams(C.Structure):
+    """brov_curve_params of include/bluerov2_nmpc_curve.h"""
+    _fields_ = [("kind", C.c_int32), ("pre", C.c_int32), ("quantum", C.c_double), ("k", C.c_double), ("kl", C.c_double), ("kr", C.c_double),
+                ("dl", C.c_double), ("dr", C.c_double), ("pre_poly", C.c_double * 5), ("observer_applied", C.c_int32), ("reserved_", C.c_int32)]
+
+    @classmethod
+    def default(cls):
+        p = cls()
+        _load().brov_curve_default_params(C.byref(p))
+        return p
+
+
+CURVE_LINEAR, CURVE_BASIC, CURVE_DEADZONE, CURVE_TABLE = 0, 1, 2, 3
+CURVE_PRE_NONE, CURVE_PRE_POLY, CURVE_PRE_TABLE = 0, 1, 2
+CURVE_PART_COMMAND, CURVE_PART_THRUST, CURVE_PART_BOTH = 1, 2, 3
+CURVE_WHICH_CURVE, CURVE_WHICH_PRE = 0, 1
+CURVE_MAX_KNOTS = 256
+_CURVE_KINDS = {"linear": CURVE_LINEAR, "basic": CURVE_BASIC, "deadzone": CURVE_DEADZONE, "table": CURVE_TABLE}
+_CURVE_PRES = {"none": CURVE_PRE_NONE, "poly": CURVE_PRE_POLY, "table": CURVE_PRE_TABLE}
+_CURVE_PARTS = {"command": CURVE_PART_COMMAND, "thrust": CURVE_PART_THRUST, "both": CURVE_PART_BOTH}
+_CURVE_WHICH = {"curve": CURVE_WHICH_CURVE, "pre": CURVE_WHICH_PRE}
+
+
 class _Opts(C.Structure):
     _fields_ = [("N", C.c_int32), ("qp_iter_max", C.c_int32), ("Ts", C.c_double), ("W", C.c_double * 16),
                 ("We", C.c_double * 12), ("lbu", C.c_double * 4), ("ubu", C.c_double * 4), ("qp_tol_mu", C.c_double),
@@ -173,8 +196,15 @@ def _protos(L):
         "brov_rotor_off": [vp], "brov_rotor_enabled": [vp], "brov_rotor_reset": [vp], "brov_rotor_set_state_host": [vp, dp],
         "brov_rotor_get_state_host": [vp, dp], "brov_rotor_last_host": [vp, dp, dp], "brov_rotor_get_stats_host": [vp, dp, C.POINTER(C.c_int64)],
         "brov_rotor_get_coeffs_host": [vp, dp, dp, dp], "brov_rotor_eval_host": [vp, dp, dp, dp, dp], "brov_rotor_last_seconds": [vp, dp],
+        "brov_curve_set_table_host": [vp, C.c_int32, dp, dp, dp, C.c_int32],
+        "brov_curve_get_table_host": [vp, C.c_int32, dp, dp, dp, dp, dp, C.POINTER(C.c_int32)],
+        "brov_curve_set_host": [vp, C.POINTER(CurveParams), dp], "brov_curve_off": [vp], "brov_curve_enabled": [vp], "brov_curve_reset": [vp],
+        "brov_curve_eval_host": [vp, C.c_int32, dp, dp, dp], "brov_curve_last_host": [vp, dp, dp, dp, dp],
+        "brov_curve_get_stats_host": [vp, dp, C.POINTER(C.c_int32), dp, C.POINTER(C.c_int64)], "brov_curve_reset_stats": [vp],
+        "brov_curve_last_seconds": [vp, dp, dp],
     })
-    _bind(L, {"brov_thruster_default_matrix": [dp], "brov_imu_default_params": [C.POINTER(ImuParams)]}, None)
+    _bind(L, {"brov_thruster_default_matrix": [dp], "brov_imu_default_params": [C.POINTER(ImuParams)],
+              "brov_curve_default_params": [C.POINTER(CurveParams)]}, None)
     _inspect.protos(_bind, L)
 
 
@@ -276,6 +306,39 @@ def rotor_coeffs(tau, h):
     if rc != 0:
         raise ValueError(f"rotor_coeffs({tau}, {h}): tau must be finite and >= 0, h finite and > 0")
     return al.value, be.value
+
+
+def curve_from_pwm_table(pwm, kgf, amps=None, neutral=1500.0):
+    """(x, y, amps): a thruster's measured table (PWM in microseconds, force, current; the columns of tests/golden/t200_16v.json) as a curve table
+    of the thrust-curve stage.  The abscissa is pwm - neutral, so that a command of 0 -- the rotor stage's zero state -- is a stopped
+    thruster; the ordinates stay in the table's units (eff carries the change to what K multiplies).  Needs no device."""
+    x = np.asarray(pwm, dtype=np.float64) - float(neutral)
+    y = np.array(kgf, dtype=np.float64)
+    if x.ndim != 1 or x.shape != y.shape or len(x) < 2 or not np.all(np.diff(x) > 0):
+        raise ValueError("pwm must be one strictly increasing column of at least two rows, kgf one of the same length")
+    a = None if amps is None else np.array(amps, dtype=np.float64)
+    if a is not None and a.shape != x.shape:
+        raise ValueError("amps must have the length of pwm")
+    return x, y, a
+
+
+def inverse_table(x, y):
+    """(y', x'): the table (x, y) with its columns swapped, as a pre-map that undoes the curve, after dropping every knot whose ordinate
+    does not exceed the last kept one, so that the new abscissae increase strictly.  Of a dead band -- a run of equal ordinates -- only
+    its FIRST knot survives: the inverse answers a wanted thrust of exactly 0 with the command at the band's lower edge, jumps across the
+    whole band to the first knot beyond it for the smallest positive thrust, and so never asks for a command inside the band; the curve
+    applied to it is the identity on the table's range up to the interpolation error of one table step, but a command that a quantisation
+    rounds back into the band is lost.  A non-monotone stretch of the curve is dropped likewise.  Needs no device."""
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    if x.ndim != 1 or x.shape != y.shape or len(x) < 2:
+        raise ValueError("x and y must be two columns of one length >= 2")
+    keep = [0]
+    for j in range(1, len(y)):
+        if y[j] > y[keep[-1]]:
+            keep.append(j)
+    if len(keep) < 2:
+        raise ValueError("the table has no two increasing ordinates")
+    return y[keep].copy(), x[keep].copy()
 
 
 def current_from_angles(speed, horizontal, vertical):
@@ -786,6 +849,85 @@ class BatchSolver(_Handle):
         if rc != -1:                           # (BROV_ERR_ARG: no plant step behind the stage yet)
             self._chk(rc, "rotor_last_seconds")
         return sec.value if rc == 0 else None
+
+    # ---- thrust-curve stage around the rotors: command map and ESC steps ahead, conversion curve and efficiency behind (brov_curve_*) ----------
+    def thrust_curve_table(self, which="curve", x=None, y=None, amps=None):
+        """with x and y: sets the table `which` ("curve" or "pre"; amps: the curve table's third column), which holds from the next plant
+        step on.  Returns dict(x, y, slope, amps, amps_slope) of [K] each: the values the stage uploaded (K = 0: no table set)"""
+        w = _CURVE_WHICH[which] if isinstance(which, str) else int(which)
+        if x is not None:
+            xa = np.ascontiguousarray(x, dtype=np.float64).ravel()
+            ya = _arr(y, xa.shape)
+            self._chk(self._L.brov_curve_set_table_host(self._h, w, _dp(xa), _dp(ya), _dp(_arr_opt(amps, xa.shape)), len(xa)), "thrust_curve_table")
+        cols = [np.zeros(CURVE_MAX_KNOTS) for _ in range(5)]
+        K = C.c_int32(0)
+        self._chk(self._L.brov_curve_get_table_host(self._h, w, *[_dp(c) for c in cols], C.byref(K)), "thrust_curve_table")
+        return dict(zip(("x", "y", "slope", "amps", "amps_slope"), (c[:K.value].copy() for c in cols)))
+
+    def set_thrust_curve(self, kind="linear", pre="none", quantum=0.0, k=1.0, kl=1.0, kr=1.0, dl=0.0, dr=0.0, pre_poly=None, eff=None,
+                         observer_applied=False):
+        """the plant steps from now on turn the commanded thrusts into force through the thrust-curve stage; its books start afresh.  The chain
+        is delay -> [pre-map, quantisation] -> rotors -> [conversion, efficiency] -> thruster stage -> model.
+            kind      "linear" (a copy), "basic" (k w |w|), "deadzone" (kl (v - dl) / 0 / kr (v - dr) of v = w |w|) or "table" (thrust_curve_table)
+            pre       "none", "poly" (pre_poly [5], highest degree first) or "table" (thrust_curve_table("pre", ...))
+            quantum   step of the command behind the pre-map (0: none)
+            eff       scalar, [6] or [B, 6] (None: 1): per-thruster efficiency and the unit change from the table's ordinate
+            observer_applied  BatchEkf.update_from_solver reads the delivered thrusts in place of the commanded ones"""
+        p = CurveParams.default()
+        p.kind = _CURVE_KINDS[kind] if isinstance(kind, str) else int(kind)
+        p.pre = _CURVE_PRES[pre] if isinstance(pre, str) else int(pre)
+        p.quantum, p.k, p.kl, p.kr, p.dl, p.dr = float(quantum), float(k), float(kl), float(kr), float(dl), float(dr)
+        if pre_poly is not None:
+            for i, v in enumerate(_arr(pre_poly, (5,))):
+                p.pre_poly[i] = float(v)
+        p.observer_applied = int(bool(observer_applied))
+        e = None if eff is None else np.ascontiguousarray(np.broadcast_to(np.asarray(eff, dtype=np.float64), (self.B, 6)))
+        self._chk(self._L.brov_curve_set_host(self._h, C.byref(p), _dp(e)), "set_thrust_curve")
+
+    def thrust_curve_off(self):
+        """every launch as it was without the stage; the books stay readable"""
+        self._chk(self._L.brov_curve_off(self._h), "thrust_curve_off")
+
+    def thrust_curve_enabled(self):
+        return bool(self._L.brov_curve_enabled(self._h))
+
+    def thrust_curve_reset(self, stats_only=False):
+        """zeroes the books and the stage's step count (stats_only: err_sq, dead_ticks, charge and the step count alone)"""
+        if stats_only:
+            self._chk(self._L.brov_curve_reset_stats(self._h), "thrust_curve_reset")
+        else:
+            self._chk(self._L.brov_curve_reset(self._h), "thrust_curve_reset")
+
+    def thrust_curve_eval(self, values, part="both"):
+        """(out [B, 6], amps [B, 6]) of the part(s) "command", "thrust" or "both" alone for `values` [B, 6]; moves nothing"""
+        v = _arr(values, (self.B, 6))
+        o, a = np.empty((self.B, 6)), np.empty((self.B, 6))
+        pt = _CURVE_PARTS[part] if isinstance(part, str) else int(part)
+        self._chk(self._L.brov_curve_eval_host(self._h, pt, _dp(v), _dp(o), _dp(a)), "thrust_curve_eval")
+        return o, a
+
+    def thrust_curve_last(self):
+        """dict(u0 [B, 4], wanted [B, 6], command [B, 6], thrust [B, 6]): what the last plant step behind the stage was given and made of it"""
+        u, w, c, t = np.empty((self.B, NU)), np.empty((self.B, 6)), np.empty((self.B, 6)), np.empty((self.B, 6))
+        self._chk(self._L.brov_curve_last_host(self._h, _dp(u), _dp(w), _dp(c), _dp(t)), "thrust_curve_last")
+        return dict(u0=u, wanted=w, command=c, thrust=t)
+
+    def thrust_curve_stats(self):
+        """dict(err_sq [B]: running sum of |wanted - delivered|^2; dead_ticks [B, 6]: steps a wanted thrust gave none; charge [B] in A s;
+        steps: steps of the stage since it was set or reset)"""
+        e, d, q, steps = np.empty(self.B), np.empty((self.B, 6), dtype=np.int32), np.empty(self.B), C.c_int64(0)
+        self._chk(self._L.brov_curve_get_stats_host(self._h, _dp(e), d.ctypes.data_as(C.POINTER(C.c_int32)), _dp(q), C.byref(steps)),
+                  "thrust_curve_stats")
+        return dict(err_sq=e, dead_ticks=d, charge=q, steps=int(steps.value))
+
+    def thrust_curve_last_seconds(self):
+        """(command, thrust): duration of the last launch of either part (HIP events; one launch does both while the rotor stage is off);
+        None where none was launched yet"""
+        a, b = C.c_double(0.0), C.c_double(0.0)
+        rc = self._L.brov_curve_last_seconds(self._h, C.byref(a), C.byref(b))
+        if rc != -1:                           # (BROV_ERR_ARG: no plant step behind the stage yet)
+            self._chk(rc, "thrust_curve_last_seconds")
+        return (a.value, b.value) if rc == 0 else None
 
     # ---- ocean current on the plant: a world-frame water velocity, drag on the velocity through the water (brov_current_*) ------------------
     def set_current(self, constant=None, table=None, gain=None, gauss_markov=None):

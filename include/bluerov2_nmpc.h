@@ -312,7 +312,7 @@ int brov_delay_last_seconds(brov_solver* s, double* shift_s, double* predict_s);
  * (ahead of the delay stage's flag).  The one-launch closed loop and the *_ticks kernels know no rotors, so the loops take their
  * launch-per-tick branch; a brov_fleet refuses such a solver.  Stage off (the default, and after brov_rotor_off): every launch is the one of
  * a solver without the stage.  Before any brov_rotor_set_host the configuration is tau = 0 everywhere, no limits, h = 0.
- * Out of scope: quadratic speed-to-thrust conversion, slew-rate limits, the plugin's propeller efficiency, a lead compensator, the fleet.
+ * Out of scope: slew-rate limits, the plugin's propeller efficiency, a lead compensator, the fleet.
  * Refused with BROV_ERR_ARG and a text in brov_last_error() that starts with the call's name (nothing changes, nothing is waited for): a NULL
  * handle, a negative or non-finite tau, a non-finite h, a NaN limit, cmd_lo[i] > cmd_hi[i], a non-finite state. */
 int brov_rotor_coeffs(double tau, double h, double* alpha, double* beta);   /* pure host function, needs no device; tau == 0: (0, 0); BROV_ERR_ARG for tau < 0 or not finite, h not finite or <= 0 */
@@ -1011,6 +1011,10 @@ int brov_clearance_dev_slices(const brov_fleet* f);                   /* the cou
  * mission machine with its three PID loops, brov_inspect_*, and the loop brov_closed_loop_inspect.  Declared in
  * bluerov2_nmpc_inspect.h. */
 #include "bluerov2_nmpc_inspect.h"
+/* The thrust-curve stage of the solver's plant, brov_curve_*: the controller's command map and the ESC's steps ahead of the rotor stage, the
+ * speed-to-thrust conversion (quadratic, dead-zone quadratic or a measured table with its current draw) and an efficiency behind it
+ * (DESIGN.md section 4.9j).  Declared in bluerov2_nmpc_curve.h. */
+#include "bluerov2_nmpc_curve.h"
 
 #ifdef __cplusplus
 }
