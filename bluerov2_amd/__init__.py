@@ -9,7 +9,7 @@ from .solver import (BatchSolver, SolverOptions, RESULT_DTYPE, P_NOMINAL, build_
                      WRENCH_OFF, WRENCH_CONSTANT, WRENCH_PERIODIC, WRENCH_TABLE,
                      CURRENT_OFF, CURRENT_CONSTANT, CURRENT_TABLE, CURRENT_GAUSS_MARKOV, current_from_angles, rotor_coeffs,
                      CORIOLIS_RIGID, CORIOLIS_ADDED, ImuParams, IMU_GPSV_ELAPSED, RangeParams, InspectParams,
-                     INSPECT_STATE_DTYPE, INSPECT_STATS_DTYPE, INSPECT_SHARED_PID, INSPECT_FLOAT_YAW, RANGE_MAX_BOXES,
+                     INSPECT_STATE_DTYPE, INSPECT_STATS_DTYPE, INSPECT_SHARED_PID, INSPECT_FLOAT_YAW, RANGE_MAX_BOXES, MeshInfo, load_stl, MESH_MAX_TRIANGLES,
                      CurveParams, curve_from_pwm_table, inverse_table, CURVE_LINEAR, CURVE_BASIC, CURVE_DEADZONE, CURVE_TABLE,
                      CURVE_PRE_NONE, CURVE_PRE_POLY, CURVE_PRE_TABLE, CURVE_PART_COMMAND, CURVE_PART_THRUST, CURVE_PART_BOTH,
                      CURVE_WHICH_CURVE, CURVE_WHICH_PRE, CURVE_MAX_KNOTS)
@@ -26,7 +26,7 @@ __all__ = ["SolverGroup", "GATHER_RECORDS", "GATHER_PACKED", "rccl_version", "un
            "WRENCH_OFF", "WRENCH_CONSTANT", "WRENCH_PERIODIC", "WRENCH_TABLE",
            "CURRENT_OFF", "CURRENT_CONSTANT", "CURRENT_TABLE", "CURRENT_GAUSS_MARKOV", "current_from_angles", "rotor_coeffs", "CORIOLIS_RIGID", "CORIOLIS_ADDED",
            "ImuParams", "IMU_GPSV_ELAPSED", "closed_loop_eskf", "RangeParams", "InspectParams", "INSPECT_STATE_DTYPE", "INSPECT_STATS_DTYPE",
-           "INSPECT_SHARED_PID", "INSPECT_FLOAT_YAW", "RANGE_MAX_BOXES",
+           "INSPECT_SHARED_PID", "INSPECT_FLOAT_YAW", "RANGE_MAX_BOXES", "MeshInfo", "load_stl", "MESH_MAX_TRIANGLES",
            "CurveParams", "curve_from_pwm_table", "inverse_table", "CURVE_LINEAR", "CURVE_BASIC", "CURVE_DEADZONE", "CURVE_TABLE",
            "CURVE_PRE_NONE", "CURVE_PRE_POLY", "CURVE_PRE_TABLE", "CURVE_PART_COMMAND", "CURVE_PART_THRUST", "CURVE_PART_BOTH",
            "CURVE_WHICH_CURVE", "CURVE_WHICH_PRE", "CURVE_MAX_KNOTS"]

@@ -11,6 +11,7 @@
 
 #include "host_common.hpp"
 #include "nmpc_device.hpp"
+#include "mesh_source.hpp"
 
 namespace brov {
 
@@ -18,6 +19,7 @@ struct InspectSource : PlantStage {
     static constexpr long long kMaxIndex = 1LL << 24;   // the measurement index has 24 bits of the noise counter
     brov_range_params cam = default_range();
     RangeScene scene{};
+    MeshSource mesh;                    // the triangle mesh beside the boxes (brov_mesh_*): while one is set the mesh kernels cast the rays
     brov_inspect_params ctl = default_inspect();
     InspectDev dev;
     double* sigma = nullptr;            // [B]
@@ -61,7 +63,7 @@ struct InspectSource : PlantStage {
         return t;
     }
 
-    void destroy() { rtimer.destroy(); PlantStage::destroy(); }
+    void destroy() { mesh.destroy(); rtimer.destroy(); PlantStage::destroy(); }
     static int index_ok(long long m, const CallCtx& c) {
         if (m < 0 || m >= kMaxIndex) return c.refuse("the range stage's measurement index (the plant's tick counter) must stay in [0, 2^24)");
         return BROV_OK;
@@ -73,7 +75,7 @@ struct InspectSource : PlantStage {
     // may `n` ticks of the loop run from the counter's value `tick`, behind a delay stage that predicts `comp` steps?
     int steps_ok(long long tick, long long n, int comp, const CallCtx& c) const {
         if (!on) return c.refuse("the inspection controller is off (brov_inspect_set_host)");
-        if (scene.n < 1) return c.refuse("the scene has no box (brov_range_set_scene_host)");
+        if (scene.n < 1 && !mesh.set()) return c.refuse("the scene has no box (brov_range_set_scene_host)");
         if (comp > 0) return c.refuse("the delay stage predicts comp > 0 steps ahead (brov_delay_set_host): the controller has no solve to predict for");
         return index_ok(tick + n - 1, c);
     }
@@ -145,17 +147,23 @@ struct InspectSource : PlantStage {
         cam.reserved_ = 0;
         return BROV_OK;
     }
-    int range_eval_host(int64_t m, const double* x, double* range, int32_t* hits, double* rot, double* depth, const hipStream_t& st, const CallCtx& c) {
+    // visits: [B][2] node tests and triangle tests per instance (brov_mesh_eval_host, which needs a mesh: need_mesh), or nullptr
+    int range_eval_host(int64_t m, const double* x, double* range, int32_t* hits, double* rot, double* depth, const hipStream_t& st, const CallCtx& c,
+                        int64_t* visits = nullptr, bool need_mesh = false) {
         if (!x || !range || !hits) return c.refuse("null argument");
+        if (need_mesh && !mesh.set()) return c.refuse("no mesh is set (brov_mesh_set_host)");
         if (int rc = index_ok((long long)m, c)) return rc;
         if (int rc = ready(c)) return rc;
         double *xd = eval_d, *rd = eval_d + B * 12, *rotd = eval_d + B * 13;
         const size_t rays = (size_t)cam.roi * cam.roi;
         ScopedDeviceBuffer<double> dd;
         if (depth) BROV_HIPCHK(c.err, dd.init(B * rays));
+        ScopedDeviceBuffer<long long> vd;
+        if (visits) BROV_HIPCHK(c.err, vd.init(B * 2));
         BROV_HIPCHK(c.err, hipMemcpy(xd, x, B * 12 * sizeof(double), hipMemcpyHostToDevice));
         (void)rtimer.start(st);
-        launch_range_eval(cam, scene, sigma, (int)B, (long long)m, xd, rd, eval_hits, rot ? rotd : nullptr, dd.p, st);
+        if (mesh.set()) launch_mesh_eval(cam, scene, mesh.dev, sigma, (int)B, (long long)m, xd, rd, eval_hits, rot ? rotd : nullptr, dd.p, vd.p, st);
+        else launch_range_eval(cam, scene, sigma, (int)B, (long long)m, xd, rd, eval_hits, rot ? rotd : nullptr, dd.p, st);
         (void)rtimer.stop(st);
         BROV_HIPCHK(c.err, hipGetLastError());
         BROV_HIPCHK(c.err, hipStreamSynchronize(st));
@@ -163,6 +171,7 @@ struct InspectSource : PlantStage {
         BROV_HIPCHK(c.err, hipMemcpy(hits, eval_hits, B * sizeof(int32_t), hipMemcpyDeviceToHost));
         if (rot) BROV_HIPCHK(c.err, hipMemcpy(rot, rotd, B * 9 * sizeof(double), hipMemcpyDeviceToHost));
         if (depth) BROV_HIPCHK(c.err, hipMemcpy(depth, dd.p, B * rays * sizeof(double), hipMemcpyDeviceToHost));
+        if (visits) BROV_HIPCHK(c.err, hipMemcpy(visits, vd.p, B * 2 * sizeof(long long), hipMemcpyDeviceToHost));
         return BROV_OK;
     }
     int range_last_seconds(double* seconds, const CallCtx& c) {
@@ -232,7 +241,8 @@ struct InspectSource : PlantStage {
     void step(const double* x, const double* y, brov_result* res, long long m, hipStream_t st) {
         (void)timer.start(st);
         (void)rtimer.start(st);
-        launch_inspect_tick(cam, scene, sigma, ctl, dev, (int)B, m, x, y, res, st);
+        if (mesh.set()) launch_inspect_mesh_tick(cam, scene, mesh.dev, sigma, ctl, dev, (int)B, m, x, y, res, st);
+        else launch_inspect_tick(cam, scene, sigma, ctl, dev, (int)B, m, x, y, res, st);
         (void)rtimer.stop(st);
         (void)timer.stop(st);
     }

@@ -1004,6 +1004,19 @@ extern "C" int brov_inspect_step(brov_solver* s, void* stream) {
     HIPCHK(hipGetLastError());
     return BROV_OK;
 }
+// ---- the triangle mesh of the range stage's scene (mesh_kernel.hip): thin forwards to its host side, mesh_source.hpp, a member of the
+// inspection stage's: while a mesh is set that stage launches the mesh kernels ------------------------------------------------------------
+extern "C" int brov_mesh_set_host(brov_solver* s, int64_t n, const double* tri, int32_t leaf) {
+    return s ? s->plant.in.mesh.set_host(n, tri, leaf, sensor_ctx(s, "brov_mesh_set_host")) : no_solver("brov_mesh_set_host");
+}
+extern "C" int brov_mesh_info(brov_solver* s, brov_mesh_summary* info) {
+    return s ? s->plant.in.mesh.get_info(info, sensor_ctx(s, "brov_mesh_info")) : no_solver("brov_mesh_info");
+}
+extern "C" int brov_mesh_eval_host(brov_solver* s, int64_t m, const double* x, double* range, int32_t* hits, double* rot, double* depth,
+                                   int64_t* visits) {
+    if (!s) return no_solver("brov_mesh_eval_host");
+    return s->plant.in.range_eval_host(m, x, range, hits, rot, depth, s->last_stream, sensor_ctx(s, "brov_mesh_eval_host"), visits, true);
+}
 // ---- delay stage between the controller's commands and the plant (delay_kernel.hip): thin forwards to its host side, delay_source.hpp, with
 // sensor_wait: the predictor runs on whatever stream a solve was given -----------------------------------------------------------------------
 extern "C" int brov_delay_set_host(brov_solver* s, const int32_t* delay, int32_t comp, double dt_pred, int32_t observer_applied) {

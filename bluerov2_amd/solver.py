@@ -15,6 +15,8 @@ import subprocess
 import numpy as np
 
 from . import inspect as _inspect
+from . import mesh as _mesh
+from .mesh import MeshInfo, load_stl, MESH_MAX_TRIANGLES  # noqa: F401
 from .inspect import (RangeParams, InspectParams, INSPECT_STATE_DTYPE, INSPECT_STATS_DTYPE, INSPECT_SHARED_PID,  # noqa: F401
                       INSPECT_FLOAT_YAW, RANGE_MAX_BOXES)
 
@@ -206,6 +208,7 @@ def _protos(L):
     _bind(L, {"brov_thruster_default_matrix": [dp], "brov_imu_default_params": [C.POINTER(ImuParams)],
               "brov_curve_default_params": [C.POINTER(CurveParams)]}, None)
     _inspect.protos(_bind, L)
+    _mesh.protos(_bind, L)
 
 
 def _dp(a):
@@ -1178,15 +1181,37 @@ class BatchSolver(_Handle):
         self._chk(self._L.brov_range_set_host(self._h, C.byref(p), _dp(sg)), "set_range")
         self._roi = int(p.roi)
 
-    def range_eval(self, index, x, rot=False, depth=False):
+    def set_range_mesh(self, tri, leaf=0):
+        """the triangle mesh of the range stage's scene, beside the boxes: tri [T, 3, 3] world-frame vertices (mesh.load_stl reads a binary
+        STL file), shared by the batch; leaf: the largest number of triangles in a leaf of the hierarchy, 1 ... 8 (0: 4), which changes no
+        result.  None or an empty array removes the mesh"""
+        t = np.zeros((0, 3, 3)) if tri is None else np.ascontiguousarray(tri, dtype=np.float64)
+        if t.ndim != 3 or t.shape[1:] != (3, 3):
+            raise ValueError("tri must have the shape [T, 3, 3]")
+        self._chk(self._L.brov_mesh_set_host(self._h, len(t), _dp(t) if len(t) else None, int(leaf)), "set_range_mesh")
+
+    def range_mesh_info(self):
+        """MeshInfo: triangles, nodes, leaves, depth, device bytes and pad of the mesh in force (zeros: none)"""
+        info = MeshInfo()
+        self._chk(self._L.brov_mesh_info(self._h, C.byref(info)), "range_mesh_info")
+        return info
+
+    def range_eval(self, index, x, rot=False, depth=False, visits=False):
         """dict(range [B], hits [B] int32, and with rot / depth: rot [B, 9], depth [B, roi * roi] with 0.0 where a ray has no return): the
-        range stage alone at `index` for the states `x` [B, 12].  Moves nothing"""
+        range stage alone at `index` for the states `x` [B, 12].  Moves nothing.  visits (needs a mesh): visits [B, 2] int64, the node tests
+        and triangle tests the rays of each instance made"""
         roi = getattr(self, "_roi", 40)
         o = dict(range=np.empty(self.B), hits=np.zeros(self.B, dtype=np.int32))
         if rot:
             o["rot"] = np.empty((self.B, 9))
         if depth:
             o["depth"] = np.empty((self.B, roi * roi))
+        if visits:
+            o["visits"] = np.zeros((self.B, 2), dtype=np.int64)
+            self._chk(self._L.brov_mesh_eval_host(self._h, int(index), _dp(_arr(x, (self.B, NX))), _dp(o["range"]),
+                                                  o["hits"].ctypes.data_as(C.POINTER(C.c_int32)), _dp(o.get("rot")), _dp(o.get("depth")),
+                                                  o["visits"].ctypes.data_as(C.POINTER(C.c_int64))), "range_eval")
+            return o
         self._chk(self._L.brov_range_eval_host(self._h, int(index), _dp(_arr(x, (self.B, NX))), _dp(o["range"]),
                                                o["hits"].ctypes.data_as(C.POINTER(C.c_int32)), _dp(o.get("rot")), _dp(o.get("depth"))), "range_eval")
         return o

@@ -1015,6 +1015,10 @@ int brov_clearance_dev_slices(const brov_fleet* f);                   /* the cou
  * speed-to-thrust conversion (quadratic, dead-zone quadratic or a measured table with its current draw) and an efficiency behind it
  * (DESIGN.md section 4.9j).  Declared in bluerov2_nmpc_curve.h. */
 #include "bluerov2_nmpc_curve.h"
+/* Triangle meshes in the scene of the range stage, brov_mesh_*: a world-frame mesh beside the boxes, a Moeller-Trumbore test restated bit for
+ * bit, and a skip-link bounding-volume hierarchy whose only contract is the result of testing every triangle.
+ * Declared in bluerov2_nmpc_mesh.h. */
+#include "bluerov2_nmpc_mesh.h"
 
 #ifdef __cplusplus
 }
