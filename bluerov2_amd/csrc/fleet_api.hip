@@ -6,7 +6,8 @@
 // reaches the solver through its public calls (brov_order_stream, brov_set_yref_candidates, brov_solve, the DEVICE pointers) and solver_view()
 // of host_common.hpp, the observer through brov_ekf_update_device and brov_ekf_mpc_p_device.  The inter-vehicle clearance term
 // (brov_clearance_*; kernels: clearance_kernel.hip) lives here too: its plan, buffers and statistics are the fleet's, and a step with the term on
-// re-scores the records ahead of the select and publishes the plan behind it.
+// re-scores the records ahead of the select and publishes the plan behind it.  So does the stand-off term (brov_standoff_*; kernels:
+// standoff_kernel.hip), which prices the candidates by their closest approach to the solver's scene (solver_scene(), standoff_kernel.hpp).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -21,6 +22,7 @@
 #include "fleet_kernel.hpp"
 #include "host_common.hpp"
 #include "nmpc_device.hpp"
+#include "standoff_kernel.hpp"
 #include "wrench_source.hpp"
 
 using namespace brov;
@@ -61,6 +63,19 @@ struct brov_fleet {
         int32_t* below = nullptr;      // [V]
         KernelTimer timer;             // around the last distance kernel
     } cl;
+    // the stand-off term (brov_standoff_*): the candidates kept clear of the solver's scene; its buffers reserved at create; off by default
+    struct Standoff {
+        bool on = false;
+        double radius = 0.0, weight = 0.0, r2 = 0.0, reach = 0.0, reach2 = 0.0;
+        int first = 1;
+        double* part = nullptr;        // [N+1][B], [N+1-first][B] used: the distance kernel's minima per stage
+        double* s2 = nullptr;          // [B] of the last step or brov_standoff_eval_host
+        brov_result* rec = nullptr;    // [B] the re-scored records a step selects from
+        long long* visits = nullptr;   // [B][2] brov_standoff_eval_host
+        double *last_s2 = nullptr, *min_s2 = nullptr;   // [V] statistics
+        int32_t* below = nullptr;      // [V]
+        KernelTimer timer;             // around the last distance kernel
+    } so;
     hipStream_t last_stream = nullptr;
     KernelTimer timer;                 // around the last select kernel
     hipEvent_t ev_done = nullptr;      // behind the last enqueued work
@@ -88,6 +103,7 @@ extern "C" void brov_fleet_destroy(brov_fleet* f) {
     f->co.destroy();
     f->timer.destroy();
     f->cl.timer.destroy();
+    f->so.timer.destroy();
     if (f->ev_done) (void)hipEventDestroy(f->ev_done);
     delete f;
 }
@@ -135,6 +151,10 @@ static int clearance_hold(brov_fleet* f, const double* xv) {
     HIPCHK(hipMemcpy(f->cl.last_d2, last.data(), V * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(f->cl.min_d2, lowest.data(), V * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemset(f->cl.below, 0, V * sizeof(int32_t)));
+    // the stand-off term's statistics are reset where the clearance term's are
+    HIPCHK(hipMemcpy(f->so.last_s2, last.data(), V * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(f->so.min_s2, lowest.data(), V * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(f->so.below, 0, V * sizeof(int32_t)));
     return BROV_OK;
 }
 
@@ -190,11 +210,18 @@ extern "C" int brov_fleet_create(brov_fleet** out, brov_solver* s, int candidate
     if (rc == BROV_OK) rc = f->mem.alloc(&f->cl.last_d2, V, g_fleet_err);
     if (rc == BROV_OK) rc = f->mem.alloc(&f->cl.min_d2, V, g_fleet_err);
     if (rc == BROV_OK) rc = f->mem.alloc(&f->cl.below, V, g_fleet_err);
+    if (rc == BROV_OK) rc = f->mem.alloc(&f->so.part, ((size_t)f->N + 1) * B, g_fleet_err);
+    if (rc == BROV_OK) rc = f->mem.alloc(&f->so.s2, (size_t)B, g_fleet_err);
+    if (rc == BROV_OK) rc = f->mem.alloc(&f->so.rec, (size_t)B, g_fleet_err);
+    if (rc == BROV_OK) rc = f->mem.alloc(&f->so.visits, (size_t)B * 2, g_fleet_err);
+    if (rc == BROV_OK) rc = f->mem.alloc(&f->so.last_s2, V, g_fleet_err);
+    if (rc == BROV_OK) rc = f->mem.alloc(&f->so.min_s2, V, g_fleet_err);
+    if (rc == BROV_OK) rc = f->mem.alloc(&f->so.below, V, g_fleet_err);
     if (rc == BROV_OK) rc = f->mem.alloc(&f->co_pp, V * 16, g_fleet_err);
     f->wr.B = f->cu.B = f->co.B = V;
     if (rc == BROV_OK) rc = f->wr.reserve(call_ctx(f, "brov_fleet_create"));   // eager: a step reads the eval buffer without a host wait
     if (rc != BROV_OK) { g_fleet_err = "brov_fleet_create: " + g_fleet_err; brov_fleet_destroy(f); return rc; }
-    if (f->timer.create() != hipSuccess || f->cl.timer.create() != hipSuccess || hipEventCreateWithFlags(&f->ev_done, hipEventDisableTiming) != hipSuccess) {
+    if (f->timer.create() != hipSuccess || f->cl.timer.create() != hipSuccess || f->so.timer.create() != hipSuccess || hipEventCreateWithFlags(&f->ev_done, hipEventDisableTiming) != hipSuccess) {
         g_fleet_err = "brov_fleet_create: device initialisation failed";
         brov_fleet_destroy(f);
         return BROV_ERR_HIP;
@@ -414,6 +441,29 @@ static int clearance_on(brov_fleet* f, const double* x, const brov_result* rec, 
     return BROV_OK;
 }
 
+// may a step run as far as the stand-off term goes?  With the term on the solver's scene must still hold a box or a mesh
+static int standoff_ok(const brov_fleet* f, const char* who) {
+    if (!f->so.on || !solver_scene(f->s).empty()) return BROV_OK;
+    g_fleet_err = std::string(who) + ": the stand-off term is on and the solver's scene holds neither a box nor a mesh (brov_range_set_scene_host, "
+                  "brov_mesh_set_host); brov_standoff_off turns the term off";
+    return BROV_ERR_ARG;
+}
+
+// the stand-off kernels on `st` (ordered by the caller) against the solver's scene as it stands: the distance kernel, timed, then the fold of
+// its slices into s2 and, with `out`, the re-scored records (the clearance term's kernel: the layout and the rule are the same).  Without
+// `visits` every stage is a slice of the grid; with them one lane walks all stages of its candidate and counts
+static int standoff_on(brov_fleet* f, const double* x, const brov_result* rec, double* s2, brov_result* out, long long* visits, hipStream_t st) {
+    const SceneView sc = solver_scene(f->s);
+    const int per = visits ? f->N + 1 : 1;
+    HIPCHK(f->so.timer.start(st));
+    launch_standoff_dist(x, sc.boxes, sc.mesh, f->B, f->N, f->so.first, per, f->so.reach2, f->so.part, visits, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(f->so.timer.stop(st));
+    launch_clearance_rescore(f->so.part, standoff_slices(f->N, f->so.first, per), f->B, rec, f->so.r2, f->so.weight, s2, out, st);
+    HIPCHK(hipGetLastError());
+    return BROV_OK;
+}
+
 // select + plant + broadcast on `st` (ordered by the caller, who has checked the wrench and the current tick), with optional DEVICE log rows of
 // this tick.  Under a wrench mode the wrench of the tick is evaluated into wlog's row (or the source's eval buffer): the plant's input and the
 // log row are one.  In moving water (a current mode in force or the Coriolis stage on) the plant is fleet_plant_water_kernel, which evaluates
@@ -424,6 +474,10 @@ static int step_on(brov_fleet* f, const brov_result* rec, double dt, int substep
     if (f->cl.on) {   // the candidates priced by their clearance from the other vehicles' plans: the select, the plant and the logs see these records
         if (int rc = clearance_on(f, brov_x_device(f->s), rec, f->cl.d2min, f->cl.rec, st)) return rc;
         rec = f->cl.rec;
+    }
+    if (f->so.on) {   // ... and by their closest approach to the scene: the stand-off term re-scores what the clearance term hands on
+        if (int rc = standoff_on(f, brov_x_device(f->s), rec, f->so.s2, f->so.rec, nullptr, st)) return rc;
+        rec = f->so.rec;
     }
     if (int rc = select_on(f, rec, f->winner, nullptr, st)) return rc;
     FleetPlantArgs a;
@@ -449,6 +503,10 @@ static int step_on(brov_fleet* f, const brov_result* rec, double dt, int substep
                                  f->cl.min_d2, f->cl.below, st);
         HIPCHK(hipGetLastError());
     }
+    if (f->so.on) {
+        launch_standoff_stats(f->winner, f->so.s2, f->V, f->C, f->so.r2, f->so.last_s2, f->so.min_s2, f->so.below, st);
+        HIPCHK(hipGetLastError());
+    }
     f->wr.tick++;
     return enqueued_on(f, st);
 }
@@ -459,6 +517,7 @@ extern "C" int brov_fleet_step(brov_fleet* f, const brov_result* rec, double dt,
         return BROV_ERR_ARG;
     }
     if (int rc = plant_modes_ok(f, "brov_fleet_step")) return rc;
+    if (int rc = standoff_ok(f, "brov_fleet_step")) return rc;
     if (int rc = f->wr.steps_ok(1, call_ctx(f, "brov_fleet_step"))) return rc;
     if (int rc = f->cu.steps_ok(f->wr.tick, 1, call_ctx(f, "brov_fleet_step"))) return rc;
     HIPCHK(hipSetDevice(f->device));
@@ -548,6 +607,7 @@ static int fleet_loop(brov_fleet* f, brov_ekf* e, const char* who, int ticks, do
     }
     if (!e && est_log) { g_fleet_err = pre + "an estimate log without an observer"; return BROV_ERR_ARG; }
     if (int rc = plant_modes_ok(f, who)) return rc;
+    if (int rc = standoff_ok(f, who)) return rc;
     if (e) {
         if (int rc = observer_ok(f, e, who)) return rc;
         if (int rc = apply_ok(f, who)) return rc;
@@ -711,4 +771,87 @@ extern "C" int brov_clearance_last_seconds(brov_fleet* f, double* seconds) {
     if (!f || !seconds || !f->cl.timer.valid) { g_fleet_err = "brov_clearance_last_seconds: no distance kernel yet"; return BROV_ERR_ARG; }
     HIPCHK(hipSetDevice(f->device));
     return f->cl.timer.seconds(seconds, g_fleet_err);
+}
+
+// ---- the stand-off term (kernels: standoff_kernel.hip) -------------------------------------------------------------
+static int no_standoff(const char* who) { g_fleet_err = std::string(who) + ": null argument"; return BROV_ERR_ARG; }
+
+extern "C" int brov_standoff_set(brov_fleet* f, double radius, double weight, double reach, int first) {
+    if (!f) return no_standoff("brov_standoff_set");
+    const double r2 = radius * radius;   // what the kernels compare against: a radius whose square overflows or underflows is refused
+    if (!(radius > 0.0) || !std::isfinite(radius) || !(r2 > 0.0) || !std::isfinite(r2) || !(weight > 0.0) || !(reach >= radius) || first < 0 ||
+        first > f->N) {
+        g_fleet_err = "brov_standoff_set: bad argument (needs a finite radius > 0 whose square is finite and > 0, a weight > 0 that may be +Inf, "
+                      "a reach >= radius that may be +Inf, and 0 <= first <= N = " + std::to_string(f->N) + ")";
+        return BROV_ERR_ARG;
+    }
+    if (solver_scene(f->s).empty()) {
+        g_fleet_err = "brov_standoff_set: the solver's scene holds neither a box nor a mesh (brov_range_set_scene_host, brov_mesh_set_host)";
+        return BROV_ERR_ARG;
+    }
+    f->so.radius = radius; f->so.weight = weight; f->so.reach = reach; f->so.first = first;
+    f->so.r2 = r2;
+    f->so.reach2 = reach * reach;   // formed once, here; +Inf for a reach that is
+    f->so.on = true;
+    return BROV_OK;
+}
+
+extern "C" int brov_standoff_off(brov_fleet* f) {
+    if (!f) return no_standoff("brov_standoff_off");
+    f->so.on = false;
+    return BROV_OK;
+}
+
+extern "C" int brov_standoff_enabled(const brov_fleet* f) { return f && f->so.on ? 1 : 0; }
+
+// the term is on and the scene still holds something to keep clear of
+static int standoff_is_set(const brov_fleet* f, const char* who) {
+    if (f->so.on) return standoff_ok(f, who);
+    g_fleet_err = std::string(who) + ": the stand-off term is off (brov_standoff_set gives the radius, the weight, the reach and the first stage)";
+    return BROV_ERR_ARG;
+}
+
+extern "C" int brov_standoff_eval_device(brov_fleet* f, const double* x, const brov_result* rec, double* s2, brov_result* out, int64_t* visits,
+                                         void* stream) {
+    if (!f || !s2) return no_standoff("brov_standoff_eval_device");
+    if (int rc = standoff_is_set(f, "brov_standoff_eval_device")) return rc;
+    HIPCHK(hipSetDevice(f->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = order_both(f, st, "brov_standoff_eval_device")) return rc;
+    if (int rc = standoff_on(f, x ? x : brov_x_device(f->s), rec ? rec : brov_results_device(f->s), s2, out, (long long*)visits, st)) return rc;
+    return enqueued_on(f, st);
+}
+
+extern "C" int brov_standoff_eval_host(brov_fleet* f, const brov_result* rec_host, double* s2, brov_result* out, int64_t* visits) {
+    if (!f || !s2) return no_standoff("brov_standoff_eval_host");
+    if (int rc = standoff_is_set(f, "brov_standoff_eval_host")) return rc;
+    HIPCHK(hipSetDevice(f->device));
+    if (int rc = wait_all(f, "brov_standoff_eval_host")) return rc;   // the staging buffer and the fleet's own s2 may still be in use
+    if (rec_host) HIPCHK(hipMemcpy(f->stage_rec, rec_host, (size_t)f->B * sizeof(brov_result), hipMemcpyHostToDevice));
+    if (int rc = standoff_on(f, brov_x_device(f->s), rec_host ? f->stage_rec : brov_results_device(f->s), f->so.s2, out ? f->so.rec : nullptr,
+                             visits ? f->so.visits : nullptr, nullptr))
+        return rc;
+    if (int rc = enqueued_on(f, nullptr)) return rc;
+    HIPCHK(hipStreamSynchronize(nullptr));
+    HIPCHK(hipMemcpy(s2, f->so.s2, (size_t)f->B * sizeof(double), hipMemcpyDeviceToHost));
+    if (out) HIPCHK(hipMemcpy(out, f->so.rec, (size_t)f->B * sizeof(brov_result), hipMemcpyDeviceToHost));
+    if (visits) HIPCHK(hipMemcpy(visits, f->so.visits, (size_t)f->B * 2 * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return BROV_OK;
+}
+
+extern "C" int brov_standoff_get_stats_host(brov_fleet* f, double* last_s2, double* min_s2, int32_t* below) {
+    if (!f) return no_standoff("brov_standoff_get_stats_host");
+    HIPCHK(hipSetDevice(f->device));
+    HIPCHK(hipStreamSynchronize(f->last_stream));
+    const size_t V = (size_t)f->V;
+    if (last_s2) HIPCHK(hipMemcpy(last_s2, f->so.last_s2, V * sizeof(double), hipMemcpyDeviceToHost));
+    if (min_s2) HIPCHK(hipMemcpy(min_s2, f->so.min_s2, V * sizeof(double), hipMemcpyDeviceToHost));
+    if (below) HIPCHK(hipMemcpy(below, f->so.below, V * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return BROV_OK;
+}
+
+extern "C" int brov_standoff_last_seconds(brov_fleet* f, double* seconds) {
+    if (!f || !seconds || !f->so.timer.valid) { g_fleet_err = "brov_standoff_last_seconds: no distance kernel yet"; return BROV_ERR_ARG; }
+    HIPCHK(hipSetDevice(f->device));
+    return f->so.timer.seconds(seconds, g_fleet_err);
 }

@@ -18,6 +18,7 @@
 #include "nmpc_device.hpp"
 #include "select_device.hpp"
 #include "solver_plant.hpp"
+#include "standoff_kernel.hpp"
 
 using namespace brov;
 
@@ -403,6 +404,12 @@ namespace brov {
 SolverView solver_view(const brov_solver* s) {
     SolverView v;
     v.device = s->device; v.par = s->par; v.cand_set = s->cand_set; v.last_stream = s->last_stream;
+    return v;
+}
+// the scene of the range stage as the next launch would be handed it (standoff_kernel.hpp): the fleet's stand-off term reads it per step
+SceneView solver_scene(const brov_solver* s) {
+    SceneView v;
+    v.boxes = s->plant.in.scene; v.mesh = s->plant.in.mesh.dev;
     return v;
 }
 }  // namespace brov

@@ -43,6 +43,16 @@ def _protos(L):
         "brov_clearance_get_stats_host": [vp, dp, dp, ip], "brov_clearance_last_seconds": [vp, dp],
         "brov_clearance_dev_set_slices": [vp, C.c_int], "brov_clearance_dev_slices": [vp],
     })
+    _bind(L, STANDOFF_PROTOS)
+
+
+# the stand-off term, include/bluerov2_nmpc_standoff.h: name -> argument types (every call returns int)
+_VP, _DP = C.c_void_p, C.POINTER(C.c_double)
+STANDOFF_PROTOS = {
+    "brov_standoff_set": [_VP, C.c_double, C.c_double, C.c_double, C.c_int], "brov_standoff_off": [_VP], "brov_standoff_enabled": [_VP],
+    "brov_standoff_eval_device": [_VP, _VP, _VP, _VP, _VP, _VP, _VP], "brov_standoff_eval_host": [_VP, _VP, _DP, _VP, C.POINTER(C.c_int64)],
+    "brov_standoff_get_stats_host": [_VP, _DP, _DP, C.POINTER(C.c_int32)], "brov_standoff_last_seconds": [_VP, _DP],
+}
 
 
 def _fleet_lib():
@@ -320,6 +330,51 @@ class Fleet(_Handle):
         """seconds of the last distance kernel"""
         s = C.c_double()
         self._chk(self._L.brov_clearance_last_seconds(self._h, C.byref(s)), "clearance_seconds")
+        return s.value
+
+    # ---- the stand-off term (brov_standoff_*) ---------------------------------------------------------------------------------------
+    def set_standoff(self, radius, weight=float("inf"), reach=None, first=1):
+        """turns the term on: candidates whose predicted path (stages first ... N) comes closer than `radius` to the solver's scene -- the boxes
+        of set_range_scene and the mesh of set_range_mesh, as they stand at every step -- pay weight * (radius^2 - s2) on their cost ahead of
+        the select (weight=inf: they are ineligible).  Distances are capped at `reach` >= radius (None: radius; inf allowed): a small reach
+        is what makes the walk over the mesh cheap"""
+        self._chk(self._L.brov_standoff_set(self._h, float(radius), float(weight), float(radius if reach is None else reach), int(first)),
+                  "set_standoff")
+
+    def standoff_off(self):
+        """today's step again; statistics and parameters are kept"""
+        self._chk(self._L.brov_standoff_off(self._h), "standoff_off")
+
+    def standoff_enabled(self):
+        return bool(self._L.brov_standoff_enabled(self._h))
+
+    def standoff_eval(self, records=None, visits=False):
+        """(s2 [V * C], re-scored records [V * C]) of the solver's iterate against the scene as it stands, from host records (None: the
+        solver's own); with visits a third item, [V * C, 2] int64: the node tests and triangle tests each candidate's walks made.  Moves
+        nothing"""
+        B = self.V * self.C
+        rp = None
+        if records is not None:
+            records = _arr(records, (B,), RESULT_DTYPE)
+            rp = records.ctypes.data_as(C.c_void_p)
+        s2 = np.empty(B)
+        out = np.empty(B, dtype=RESULT_DTYPE)
+        vis = np.zeros((B, 2), dtype=np.int64) if visits else None
+        self._chk(self._L.brov_standoff_eval_host(self._h, rp, _dp(s2), out.ctypes.data_as(C.c_void_p),
+                                                  None if vis is None else vis.ctypes.data_as(C.POINTER(C.c_int64))), "standoff_eval")
+        return (s2, out, vis) if visits else (s2, out)
+
+    def standoff_stats(self):
+        """dict(last_s2 [V]: s2 of the last step's winner or -1, min_s2 [V]: its minimum over the steps with a winner, below [V]: steps
+        whose winner was inside the radius)"""
+        last, low, below = np.empty(self.V), np.empty(self.V), np.empty(self.V, dtype=np.int32)
+        self._chk(self._L.brov_standoff_get_stats_host(self._h, _dp(last), _dp(low), _ip(below)), "standoff_stats")
+        return dict(last_s2=last, min_s2=low, below=below)
+
+    def standoff_seconds(self):
+        """seconds of the last distance kernel"""
+        s = C.c_double()
+        self._chk(self._L.brov_standoff_last_seconds(self._h, C.byref(s)), "standoff_seconds")
         return s.value
 
     def last_seconds(self):

@@ -1019,6 +1019,9 @@ int brov_clearance_dev_slices(const brov_fleet* f);                   /* the cou
  * bit, and a skip-link bounding-volume hierarchy whose only contract is the result of testing every triangle.
  * Declared in bluerov2_nmpc_mesh.h. */
 #include "bluerov2_nmpc_mesh.h"
+/* The stand-off term of the fleet loop, brov_standoff_*: every candidate priced by the closest approach of its predicted path to the scene of
+ * the range stage, mesh and boxes, ahead of the select.  Declared in bluerov2_nmpc_standoff.h. */
+#include "bluerov2_nmpc_standoff.h"
 
 #ifdef __cplusplus
 }
