@@ -916,7 +916,9 @@ __device__ __forceinline__ void adj_chunk(const IT& I, d4& atpi, const double* v
             wr = I.Ts * I.Wr[3];
         }
 #pragma unroll
-        for (int r = 0; r < 3; r++) pi[r] = wq[r] * (in.dx[r] + in.xn[r] - in.yn[r]) + atpi[r];
+        // (x - yref first: the tracking error is small and that difference close to exact; dx + x would round at the size of x itself, ulp(20 m)
+        // times a weight of hundreds -- ten to twenty-five times the oracle's error in pi against the exact minimiser, tests/test_gpu_qp_exact.py)
+        for (int r = 0; r < 3; r++) pi[r] = wq[r] * (in.dx[r] + (in.xn[r] - in.yn[r])) + atpi[r];
         pi[3] = 0.0;
         if (COMMIT) store_vec12(pi_out + (size_t)i * 12, pi, rg, cl);
         d4 G = tn<3>(in.ba, pi, z4);
